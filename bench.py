@@ -24,6 +24,11 @@ that it overlaps with the next pass.
     python bench.py [--gpus N] [--steps K] [--warmup W] [--config 2|4|5] [--streams S]      (N > 1: starts its own N ranks)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...  (a launcher's ranks are used as is)
 
+A plain run times the headline only: set-up (stream calibration included), warm-up, K timed steps, the JSON line.  --full adds,
+after the timed region, the lockstep kernel probe, the oracle parity at bench size, the CPU baseline and (config 2, one GPU)
+other_configs.  --dump-outputs DIR writes what the last timed step computed as DIR/<name>.npy (float32 / float64; at most 64 MB,
+a fixed seeded sample of the envs beyond that): same arguments, same inputs, so two builds can be compared output for output.
+
 --streams S: the rank's env block is cut into S contiguous sub-batches, each with its own handle and HIP stream.  A pass
 is then S launches; a launch lasts as long as its slowest env, and with several independent streams one sub-batch's tail
 (few live waves) overlaps with the body of the others instead of idling the machine (DESIGN.md §6 "launch tail").  Default
@@ -354,7 +359,7 @@ def config3_probe(dev, B=4096, A=20, T=50, warm=30, n=150):
 def other_config_shards(dev, visibility, passes=12):
     """BASELINE configs[3] and configs[4] on their per-GPU shard of an 8-GPU node (8192 envs x 50A/200T rollout; 8192 envs x
     100A/500T route replay with dynamic arrivals), one mid-size shape (4096 envs x 70A/130T) and BASELINE configs[2] (attention
-    policy in the loop), timed inside the DEFAULT run so that whoever clocks `python bench.py` also clocks them: one warm pass,
+    policy in the loop), timed inside a --full run of the headline workload: one warm pass,
     then `passes` passes back to back, inputs resident in HBM.  Each entry carries its issue roofline (committed
     counters of that kernel), a CPU baseline (the oracle on the same shard, all usable cores) and the oracle parity of the
     shard.  The full lines of these configs (sharding, streams) are `bench.py --config 4` / `--config 5`."""
@@ -531,9 +536,50 @@ class SubBatch:
         """One pass of this sub-batch; returns (steps int64[B], returns f64[B, episodes])."""
         if self.replay:
             out = self.env.execute_routes(self.reactive, fields=())
+            self.last_out = out
             self.last_flags = out["flags"]                # (checked after the timed region: no extra launch for it)
             return out["steps"], out["summary"][:, :1]
         return self.env.rollout_random(episodes=episodes, write_obs=write_obs), self.ring
+
+
+DUMP_LIMIT_BYTES = 64 * 10**6
+
+
+def dump_outputs(subs, out_dir, first, write_obs, suffix="", limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: what the last timed pass handed its caller, one DIR/<name><suffix>.npy per array, rows = envs in block order.
+    Rollout: decisions per env, the return of every episode of the pass, summary() (last-episode reward, finished tasks, six
+    metrics) and, with observation stores on, the observation buffers; replay: agent_step calls, flags and summary() of
+    execute_routes.  Integers are stored as float64, the observation mask as float32.  Beyond `limit` bytes a fixed, seeded
+    sample of the envs is written; env_index holds the global index of every row."""
+    def arrays(sb):
+        if sb.replay:
+            o = sb.last_out
+            yield from (("steps", o["steps"]), ("flags", o["flags"]), ("summary", o["summary"]))
+            return
+        yield from (("steps", sb.counts[-1]), ("returns", sb.ring), ("summary", sb.env.summary()))
+        if write_obs:
+            ob = sb.env.obs()
+            yield from (("obs_agents", ob.agents), ("obs_tasks", ob.tasks), ("obs_mask", ob.mask))
+    B = sum(sb.B for sb in subs)
+    first_arrays = list(arrays(subs[0]))
+    row_bytes = sum((4 if v.dtype in (torch.float32, torch.bool) else 8) * (v.numel() // v.shape[0]) for _, v in first_arrays) + 8
+    budget = limit - 1024 * (len(first_arrays) + 1)          # (room for the .npy headers)
+    keep = np.arange(B)
+    if B * row_bytes > budget:
+        keep = np.sort(np.random.default_rng(0).choice(B, budget // row_bytes, replace=False))
+    parts = {"env_index": [first + keep.astype(np.float64)]}
+    lo = 0
+    for sb in subs:
+        rows = keep[(keep >= lo) & (keep < lo + sb.B)] - lo
+        idx = torch.from_numpy(rows).to(sb.env.device)
+        for name, v in arrays(sb):
+            v = v.index_select(0, idx)
+            v = v.float() if v.dtype in (torch.float32, torch.bool) else v.double()
+            parts.setdefault(name, []).append(v.cpu().numpy())
+        lo += sb.B
+    os.makedirs(out_dir, exist_ok=True)
+    for name, p in parts.items():
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), np.concatenate(p))
 
 
 def main():
@@ -556,12 +602,22 @@ def main():
                          "(default: $DCM_DIST_TIMEOUT, else 120)")
     ap.add_argument("--launch-timeout", type=float, default=None,
                     help="N > 1, self-launched: wall-clock limit of the whole job (dcmrta_amd/launch.py; default 1500 s, 0 = none)")
-    ap.add_argument("--no-cpu-baseline", action="store_true", help="skip the oracle legs (cpu_baseline AND the bench-size parity check)")
-    ap.add_argument("--no-lockstep-probe", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed region also run the lockstep kernel probe, the bench-size oracle parity, the CPU baseline "
+                         "and (config 2, one GPU) other_configs; a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step computed as DIR/<name>.npy (float32 / float64, at most 64 MB)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the oracle legs (cpu_baseline AND the bench-size parity check)")
+    ap.add_argument("--no-lockstep-probe", action="store_true", help="--full: skip the lockstep kernel probe (and other_configs)")
     ap.add_argument("--no-obs", action="store_true", help="skip the observation stores (ablation, not the metric)")
     ap.add_argument("--no-other-configs", action="store_true",
-                    help="config 2, one GPU: do not time the per-GPU shards of configs 4 / 5 (other_configs) after the run")
+                    help="--full, config 2, one GPU: do not time the per-GPU shards of configs 4 / 5 (other_configs) after the run")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if not args.full:
+        # a plain run does only what the headline needs: every auxiliary leg after the timed region is --full's
+        args.no_cpu_baseline = args.no_lockstep_probe = args.no_other_configs = True
     cfg = dict(CONFIGS[args.config])
     for k in ("envs", "agents", "tasks", "episodes"):
         if getattr(args, k) is not None:
@@ -717,6 +773,10 @@ def main():
             lockstep = lockstep_kernel_probe(A, T, dev)
         except Exception as ex:      # (an auxiliary probe must never take the headline line down with it)
             lockstep = {"error": f"{type(ex).__name__}: {ex}"[:300]}
+    # (before the parity leg: it replays the sub-batches from their seeds)
+    if args.dump_outputs:
+        dump_outputs(subs, args.dump_outputs, first, not args.no_obs, suffix=f".rank{ctx.rank}" if ctx.world > 1 else "",
+                     limit=DUMP_LIMIT_BYTES // ctx.world)
     # Oracle parity at bench size (part of the cpu_baseline leg, after the timed region): every env of this rank's block.
     parity = None
     if not args.no_cpu_baseline:
@@ -818,7 +878,7 @@ def main():
                                        "(COALITION_SIZE 5, 20A/50T..100A/500T) none of these limits is reached"}
     if lockstep is not None:
         out["lockstep_kernel"] = lockstep
-    # (only in the full default run: the profiling / A-B tools pass --no-lockstep-probe --no-cpu-baseline and must see one kernel)
+    # (only in a --full run that keeps every leg: the profiling / A-B tools pass --no-lockstep-probe --no-cpu-baseline and must see one kernel)
     if ctx.world == 1 and args.config == "2" and not (args.no_other_configs or args.no_lockstep_probe or args.no_cpu_baseline) and \
             all(getattr(args, k) is None for k in ("envs", "agents", "tasks")):
         for sb in subs:

@@ -31,8 +31,8 @@ def test_two_rank_bench_line(gpu_device):
 
 
 def test_single_gpu_bench_contract_line(gpu_device):
-    """python bench.py (N = 1): one JSON line with the contract keys, the roofline object and the bounded CPU baseline."""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1", "--no-lockstep-probe"],
+    """python bench.py --full (N = 1): one JSON line with the contract keys, the roofline object and the bounded CPU baseline."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1", "--no-lockstep-probe"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:] + out.stderr[-2000:]
@@ -57,6 +57,35 @@ def test_single_gpu_bench_contract_line(gpu_device):
     assert c["kind"] == "port" and c["cores"] >= 1 and c["value"] > 0 and c["unit"] == "steps/s" and "sample" in c
     assert c["at_8_threads"]["cores"] <= 8 and c["at_8_threads"]["value"] > 0   # mirror of NUM_META_AGENT = 8 (runner.py:74)
     assert j["value"] > 1e6          # the north-star floor (1M env-steps/s on one MI355X)
+
+
+def test_plain_run_is_lean_and_dumps_repeatable_outputs(gpu_device, tmp_path):
+    """A plain `python bench.py` times the headline only (no auxiliary legs) and --dump-outputs writes the last timed pass: the same
+    arrays for the same number of passes, whatever the warm-up / timed split and the stream count; config 5 dumps its replay results."""
+    import numpy as np
+
+    def run(*extra):
+        out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py")] + list(extra), capture_output=True, text=True, timeout=600,
+                             cwd=ROOT)
+        lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
+        assert out.returncode == 0 and len(lines) == 1, out.stdout[-2000:] + out.stderr[-3000:]
+        return json.loads(lines[0])
+
+    def load(d):
+        return {f[:-4]: np.load(os.path.join(d, f)) for f in sorted(os.listdir(d))}
+    j = run("--steps", "3", "--warmup", "1", "--dump-outputs", str(tmp_path / "a"))
+    assert j["steps"] == 3 and j["ms_per_step"] > 0 and j["value"] > 1e6 and j["dtype"] == "f64" and j["parity"] is None
+    assert not {"cpu_baseline", "other_configs", "lockstep_kernel"} & set(j)
+    run("--steps", "2", "--warmup", "2", "--streams", "1", "--dump-outputs", str(tmp_path / "b"))
+    a, b = load(tmp_path / "a"), load(tmp_path / "b")
+    assert sorted(a) == ["env_index", "obs_agents", "obs_mask", "obs_tasks", "returns", "steps", "summary"] and sorted(b) == sorted(a)
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20 and len(a["steps"]) == 4096
+    for k in a:
+        assert a[k].dtype in (np.float32, np.float64) and a[k].tobytes() == b[k].tobytes(), k
+    assert a["steps"].min() > 0 and np.isfinite(a["returns"]).all() and a["returns"].shape == (4096, 3)
+    run("--config", "5", "--envs", "256", "--steps", "2", "--warmup", "1", "--dump-outputs", str(tmp_path / "c"))
+    c = load(tmp_path / "c")
+    assert sorted(c) == ["env_index", "flags", "steps", "summary"] and c["summary"].shape == (256, 8) and c["steps"].min() > 0
 
 
 def test_rccl_branch_runs_on_one_rank(gpu_device):
@@ -110,7 +139,7 @@ def test_config5_replay_line(gpu_device):
     assert j["roofline"]["kernel"] == "k_replay_fast" and "agent_step" in j["config"]["step_definition"]
     per_pass = j["value"] * j["ms_per_step"] / 1e3
     assert 301 * 100 < per_pass < 301 * 2000          # every agent takes a few steps (routes over the 100 visible tasks + depot)
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--config", "5", "--envs", "256", "--steps", "2",
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--config", "5", "--envs", "256", "--steps", "2",
                           "--warmup", "1", "--visibility", "100,100,10,500"], capture_output=True, text=True, timeout=900, cwd=ROOT)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:] + out.stderr[-3000:]
@@ -131,7 +160,7 @@ def test_plain_command_launches_its_own_ranks(gpu_device, extra, check):
     it.  Two ranks share the test box's one GPU over gloo; on a multi-GPU node the same command runs one rank per GPU over RCCL."""
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_PORT")}
     env.update(DCM_FORCE_DEVICE="0", DCM_DIST_BACKEND="gloo")
-    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1"] + extra
+    cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--gpus", "2", "--steps", "3", "--warmup", "1"] + extra
     out = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=900, cwd=ROOT)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert out.returncode == 0 and len(lines) == 1, out.stdout[-2000:] + out.stderr[-3000:]
@@ -155,9 +184,9 @@ def test_plain_command_propagates_rank_failure(gpu_device):
 
 
 def test_default_line_times_the_other_baseline_configs(gpu_device):
-    """The full default run (what the driver clocks) also times the per-GPU shards of BASELINE configs[3] and configs[4] and the
-    HBM-bound lockstep kernel, after the timed region."""
-    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "2", "--warmup", "1"],
+    """The --full run also times the per-GPU shards of BASELINE configs[3] and configs[4] and the HBM-bound lockstep kernel, after
+    the timed region."""
+    out = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--full", "--steps", "2", "--warmup", "1"],
                          capture_output=True, text=True, timeout=900, cwd=ROOT)
     lines = [l for l in out.stdout.splitlines() if l.startswith("{")]
     assert len(lines) == 1, out.stdout[-2000:] + out.stderr[-2000:]
