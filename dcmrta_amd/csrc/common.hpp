@@ -269,14 +269,37 @@ __device__ __forceinline__ double wave_nanmax(double v) {
     const int lo = __builtin_amdgcn_readlane(__double2loint(v), 63), hi = __builtin_amdgcn_readlane(__double2hiint(v), 63);
     return __hiloint2double(hi, lo);
 }
+// ---------------------------------------------------------------------------------- lane primitives
 // position of the idx-th (0-based) set bit of a wave-uniform mask, 0 <= idx < popcount(m); all 64 lanes must call.
 // v_mbcnt_lo/hi gives every lane the number of set bits below it; the lanes up to and including the wanted bit are exactly those
 // with at most idx of them, so one compare + one scalar popcount find it (an out-of-range idx gives -1 / 63: callers that probe
 // several mask words discard those).
-__device__ __forceinline__ int nth_set_bit(uint64_t m, int idx, int lane) {
-    (void)lane;
+__device__ __forceinline__ int nth(uint64_t m, int idx) {
     const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
     return __popcll(__ballot(rank <= idx)) - 1;
+}
+// v_readlane: lane src's value (src wave-uniform) as a wave-uniform scalar
+__device__ __forceinline__ double rl(double v, int src) {
+    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), src), __builtin_amdgcn_readlane(__double2loint(v), src));
+}
+__device__ __forceinline__ uint64_t rl(uint64_t v, int src) {
+    return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(v >> 32), src) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, src);
+}
+__device__ __forceinline__ uint32_t rl(uint32_t v, int src) { return (uint32_t)__builtin_amdgcn_readlane((int)v, src); }
+__device__ __forceinline__ int rli(int v, int src) { return __builtin_amdgcn_readlane(v, src); }
+// value of a per-chunk register array at the wave-uniform position (chunk, lane): every chunk's lane is read, scalar selects pick
+// (branches around two v_readlane cost more than the reads)
+__device__ __forceinline__ uint32_t sel(bool c, uint32_t a, uint32_t b) { return c ? a : b; }
+__device__ __forceinline__ uint64_t sel(bool c, uint64_t a, uint64_t b) { return c ? a : b; }
+__device__ __forceinline__ double sel(bool c, double a, double b) {
+    return __longlong_as_double((long long)sel(c, (uint64_t)__double_as_longlong(a), (uint64_t)__double_as_longlong(b)));
+}
+template <class V, int N>
+__device__ __forceinline__ V rlc(const V (&v)[N], int chunk, int src) {
+    V out = rl(v[0], src);
+#pragma unroll
+    for (int c = 1; c < N; c++) out = sel(c == chunk, rl(v[c], src), out);
+    return out;
 }
 
 // ---------------------------------------------------------------------------------- numpy add.reduce

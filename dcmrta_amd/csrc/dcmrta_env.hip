@@ -42,11 +42,20 @@ int fail(int code, const char* fmt, const char* a, const char* b) {
     return code;
 }
 #endif
-// k_rollout_fast_g<NAC, NTC, OBS> (rollout_fast_g.hpp): same arguments as the kernel behind the launch geometry
-void launch_rollout_fast_g(int nac, int ntc, bool obs, unsigned grid, unsigned lds_bytes, hipStream_t stream, int A, int T, int PA, int PT,
-                           KP kp, unsigned char* state, int episodes, float* agents_out, float* tasks_out, uint8_t* mask_out,
-                           int64_t* steps_out, double* summary, uint16_t* ablog, const int32_t* sizes, int64_t budget_all,
-                           const int64_t* budget_in, unsigned char* gscr, double* retlog, int retcap);
+// The arguments of every persistent rollout kernel (k_rollout_random, k_rollout_fast, k_rollout_fast_mc, k_rollout_fast_g), in
+// their order
+struct RolloutArgs {
+    int A, T, PA, PT;
+    KP kp;
+    unsigned char* state;
+    int episodes;
+    float* agents_out; float* tasks_out; uint8_t* mask_out;
+    int64_t* steps_out; double* summary; uint16_t* ablog;
+    const int32_t* sizes; int64_t budget_all; const int64_t* budget_in;
+    unsigned char* gscr; double* retlog; int retcap;
+};
+// k_rollout_fast_g<NAC, NTC, OBS> (rollout_fast_g.hpp, its own translation unit)
+void launch_rollout_fast_g(int nac, int ntc, bool obs, unsigned grid, unsigned lds_bytes, hipStream_t stream, const RolloutArgs& a);
 }  // namespace dcm
 
 namespace {
@@ -227,8 +236,8 @@ struct Sim {
             x = 0.; y = 0.;
 #pragma unroll
             for (int c = 0; c < NTC; c++) if (c == kc) {
-                x = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(xy.x[c]), kl), __builtin_amdgcn_readlane(__double2loint(xy.x[c]), kl));
-                y = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(xy.y[c]), kl), __builtin_amdgcn_readlane(__double2loint(xy.y[c]), kl));
+                x = rl(xy.x[c], kl);
+                y = rl(xy.y[c], kl);
             }
         } else { x = tx()[k]; y = ty()[k]; }
     }
@@ -315,12 +324,12 @@ struct Sim {
 #pragma unroll
         for (int i = 0; i < NAW; i++) if (i == (a >> 6)) m.w[i] |= (1ull << (a & 63)); }
     __device__ __forceinline__ static int am_nth(const AMask& m, int idx, int lane) {
-        if constexpr (NAW == 1) return nth_set_bit(m.w[0], idx, lane);
+        if constexpr (NAW == 1) return nth(m.w[0], idx);
         int b = 0, res = -1;
 #pragma unroll
         for (int i = 0; i < NAW; i++) {
             const int c = __popcll(m.w[i]);
-            const int p = nth_set_bit(m.w[i], idx - b, lane);
+            const int p = nth(m.w[i], idx - b);
             if (res < 0 && idx - b >= 0 && idx - b < c) res = i * 64 + p;
             b += c;
         }
@@ -810,13 +819,10 @@ struct Sim {
                 r += __shfl_xor(r, 4);
                 for (int i = nb; i < n; i++) r += arr4[i];
             }
-            auto lane_value = [&](int src) {
-                return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(r), src), __builtin_amdgcn_readlane(__double2loint(r), src));
-            };
-            m2 = lane_value(0) / Td;                   // np.nanmean(time_start)      worker.py:105
-            m3 = lane_value(8) / Ad;                   // np.mean(agent sum_waiting)  :106
-            m4 = lane_value(16);                       // np.sum(travel_dist)         :107
-            m5 = lane_value(24) / Td;                  // np.mean(task sum_waiting)   :108
+            m2 = rl(r, 0) / Td;                        // np.nanmean(time_start)      worker.py:105
+            m3 = rl(r, 8) / Ad;                        // np.mean(agent sum_waiting)  :106
+            m4 = rl(r, 16);                            // np.sum(travel_dist)         :107
+            m5 = rl(r, 24) / Td;                       // np.mean(task sum_waiting)   :108
         } else {
             m2 = psum<4>(ts(), T_) / Td;
             m3 = psum_block(aw(), A_) / Ad;
@@ -1110,7 +1116,7 @@ struct Sim {
             const uint64_t bm = __ballot((lane < T_) && !(info & T_FEAS) && ((int)(int8_t)((info >> 8) & 0xFF) > 0));
             const int nv = __popcll(bm);
             if (nv == 0) return 0;  // only the depot is unmasked
-            return nth_set_bit(bm, below((uint32_t)k1, nv), lane) + 1;
+            return nth(bm, below((uint32_t)k1, nv)) + 1;
         } else {
             int nv = 0;
             for (int t0 = 0; t0 < T_; t0 += WAVE) {
@@ -1126,7 +1132,7 @@ struct Sim {
                 const uint32_t info = tinfo()[t < T_ ? t : 0];
                 const uint64_t bm = __ballot((t < T_) && !(info & T_FEAS) && ((int)(int8_t)((info >> 8) & 0xFF) > 0));
                 const int c = __popcll(bm);
-                const int p = nth_set_bit(bm, idx, lane);
+                const int p = nth(bm, idx);
                 if (action == 0 && idx >= 0 && idx < c) action = t0 + p + 1;
                 idx -= c;
             }
@@ -1573,10 +1579,23 @@ __global__ __launch_bounds__(WAVE) void k_step(int A, int T, int PA, int PT, KP 
     PHK_TOTAL(6);
 }
 
-// Config-2 hot path: whole episodes in one persistent launch, record resident in LDS.
+// ================================================================================== the persistent rollout kernels' budget and error stop
+// Shared by k_rollout_random below and the register-resident k_rollout_fast, k_rollout_fast_mc and k_rollout_fast_g.
+
+// errors that end an env's rollout at the next episode boundary (instead of the restart of a finished episode)
+constexpr uint32_t ROLLOUT_ERR = DCM_FLAG_BAD_ACTION | DCM_FLAG_OVERFLOW | DCM_FLAG_BAD_LEADER | DCM_FLAG_BAD_INSTANCE;
+
 // budget (per env: budget_in[e] if given, else budget_all; < 0 = unlimited): an env takes at most that many decisions in
 // this launch; when the budget runs out the env stays at the decision point it has reached (a later call -- dcm_rollout_random,
 // dcm_observe or dcm_step -- carries on from it) and the observation buffers hold what the last decision TAKEN saw.
+// Returns the decisions left in this launch: a 32-bit countdown is the only loop-carried counter (steps = budget - left afterwards).
+__device__ __forceinline__ int rollout_budget(int e, int64_t budget_all, const int64_t* budget_in) {
+    constexpr int NO_BUDGET = 0x7FFFFFFF;
+    const int64_t bud = budget_in ? budget_in[e] : budget_all;
+    return uni((int)((bud < 0 || bud >= NO_BUDGET) ? NO_BUDGET : bud));
+}
+
+// Config-2 hot path: whole episodes in one persistent launch, record resident in LDS.  Budget: see rollout_budget.
 // __launch_bounds__(64, 3): at least three waves per SIMD.  The one-chunk shapes need 111 VGPRs anyway (four waves per SIMD); the
 // 50A/200T instantiation wants 176 -- two waves per SIMD although its LDS image (10.9 KB with the member arrival times left in
 // the HBM record) would let twelve workgroups share a CU -- and with 168 (five spilled) it runs three: 8.65 -> 6.90 ms per
@@ -1613,10 +1632,7 @@ __global__ __launch_bounds__(WAVE, 3) void k_rollout_random(int A, int T, int PA
     // (wave-uniform branches otherwise, at every decision)
     const bool all_obs = agents_out && tasks_out && mask_out;
     double* row = summary + (size_t)e * 8;
-    // decisions left in this launch: a 32-bit countdown is the only loop-carried counter (steps = budget - left afterwards)
-    constexpr int NO_BUDGET = 0x7FFFFFFF;
-    int64_t bud = budget_in ? budget_in[e] : budget_all;
-    const int left0 = uni((int)((bud < 0 || bud >= NO_BUDGET) ? NO_BUDGET : bud));
+    const int left0 = rollout_budget(e, budget_all, budget_in);
     int left = left0;
     PH_DECL;
     // key_1 = mix64(seed + GAMMA (d+1)): the argument is carried and advanced by GAMMA per decision (no 64-bit multiply,
@@ -1625,7 +1641,7 @@ __global__ __launch_bounds__(WAVE, 3) void k_rollout_random(int A, int T, int PA
     const uint64_t d0 = h.d;
     for (int ep = 0; ep < episodes; ep++) {
         if (h.flags & DCM_FLAG_DONE) {  // restart from the loaded instance; d keeps running
-            if (h.flags & (DCM_FLAG_BAD_ACTION | DCM_FLAG_OVERFLOW | DCM_FLAG_BAD_LEADER | DCM_FLAG_BAD_INSTANCE)) break;
+            if (h.flags & ROLLOUT_ERR) break;
             if (left == 0) break;       // budget spent at an episode boundary: the finished episode's results stay readable
             S.reset_state(h, lane);
             S.advance(h, P, lane, row PH_PASS);
@@ -1824,6 +1840,24 @@ __global__ void k_distance(const double* ax, const double* ay, const double* bx,
     } while (0)
 // kernel arguments every env kernel starts with: batch dims, layout dims
 #define DIMS(env) (env)->A, (env)->T, (env)->L.A, (env)->L.T
+// the one-chunk register-resident kernels (step_fast.hpp, rollout_fast.hpp): <20,50> exactly or with runtime sizes, every other
+// one-chunk layout in <64,64,runtime sizes>
+#define DISPATCH_ONE_CHUNK(env, CALL)                                                                  \
+    do {                                                                                               \
+        const dcm_env* e_ = (env);                                                                     \
+        const bool exact_ = !e_->sizes && e_->A == e_->L.A && e_->T == e_->L.T;                        \
+        if (e_->L.A == 20 && e_->L.T == 50) { if (exact_) { CALL(20, 50, false); } else { CALL(20, 50, true); } } \
+        else { CALL(64, 64, true); }                                                                   \
+    } while (0)
+
+// The register-resident kernels skip the task_update pass of a QUIET join on the ground that a member who has just joined
+// has not waited max_waiting_time yet (env/task_env.py:269), which needs max_waiting_time > 0 (the reference's 10 / 100):
+// a handle with max_waiting_time <= 0 (or NaN) takes the general kernels, which evaluate the rule literally.
+bool quiet_ok(const dcm_env* env) { return env->kp.mwt > 0.0; }
+// ... and the one-chunk ones need one lane per agent and per task, with lane 63 free for the depot
+bool one_chunk_ok(const dcm_env* env) {
+    return quiet_ok(env) && env->L.C == M && env->L.A <= 64 && env->L.T <= 64 && env->T <= 63;
+}
 
 // dcm_create / dcm_destroy run on the handle's device but leave the caller's current device as they found it
 struct DeviceGuard {
@@ -1834,14 +1868,17 @@ struct DeviceGuard {
 
 }  // namespace
 
+namespace {
+template <class K>
+void launch_rollout(K kernel, dim3 grid, dim3 block, unsigned lds_bytes, hipStream_t stream, const RolloutArgs& a) {
+    hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, a.A, a.T, a.PA, a.PT, a.kp, a.state, a.episodes, a.agents_out, a.tasks_out,
+                       a.mask_out, a.steps_out, a.summary, a.ablog, a.sizes, a.budget_all, a.budget_in, a.gscr, a.retlog, a.retcap);
+}
+}  // namespace
+
 #if defined(DCM_TU_G) || !defined(DCM_SPLIT_G)
-void dcm::launch_rollout_fast_g(int nac, int ntc, bool obs, unsigned grid, unsigned lds_bytes, hipStream_t stream, int A, int T, int PA, int PT,
-                                KP kp, unsigned char* state, int episodes, float* agents_out, float* tasks_out, uint8_t* mask_out,
-                                int64_t* steps_out, double* summary, uint16_t* ablog, const int32_t* sizes, int64_t budget_all,
-                                const int64_t* budget_in, unsigned char* gscr, double* retlog, int retcap) {
-#define CALLG(NAC, NTC, OBS)                                                                                           \
-    hipLaunchKernelGGL((k_rollout_fast_g<NAC, NTC, OBS>), dim3(grid), dim3(WAVE), lds_bytes, stream, A, T, PA, PT, kp, state, episodes, \
-                       agents_out, tasks_out, mask_out, steps_out, summary, ablog, sizes, budget_all, budget_in, gscr, retlog, retcap)
+void dcm::launch_rollout_fast_g(int nac, int ntc, bool obs, unsigned grid, unsigned lds_bytes, hipStream_t stream, const RolloutArgs& a) {
+#define CALLG(NAC, NTC, OBS) launch_rollout(k_rollout_fast_g<NAC, NTC, OBS>, dim3(grid), dim3(WAVE), lds_bytes, stream, a)
 #define CALLT(NAC, OBS) do { if (ntc > 3) { CALLG(NAC, 4, OBS); } else if (ntc > 2) { CALLG(NAC, 3, OBS); } else { CALLG(NAC, 2, OBS); } } while (0)
 #define CALLA(OBS) do { if (nac > 1) { CALLT(2, OBS); } else { CALLT(1, OBS); } } while (0)
     if (obs) { CALLA(true); } else { CALLA(false); }
@@ -2021,9 +2058,7 @@ int flush_pending(dcm_env* env, void* stream) {
                        (Sim<CA, CT, RS>::lds_image_bytes(env->L)) + 512u + (step_scratch_in_lds<CA, CT>() ? env->L.scratch_bytes() : 0u), \
                        (hipStream_t)stream, DIMS(env), env->kp, (const unsigned char*)env->side, env->side_pitch, env->pendq,       \
                        env->summary, (const int32_t*)env->sizes, env->gscratch)
-    const bool exact_ = !env->sizes && env->A == env->L.A && env->T == env->L.T;
-    if (env->L.A == 20 && env->L.T == 50) { if (exact_) { CALL(20, 50, false); } else { CALL(20, 50, true); } }
-    else { CALL(64, 64, true); }
+    DISPATCH_ONE_CHUNK(env, CALL);
 #undef CALL
     LAUNCH_OK();
     env->maybe_pending = false;
@@ -2114,13 +2149,9 @@ int dcm_step(dcm_env* env, const int32_t* actions, const int32_t* leader_in, con
     if (!actions) return fail(DCM_ERR_INVALID, "dcm_step: null actions");
     if ((nfol_in == nullptr) != (followers_in == nullptr))
         return fail(DCM_ERR_INVALID, "dcm_step: nfol_in and followers_in must be given together");
-    // The register-resident kernels skip the task_update pass of a QUIET join on the ground that a member who has just joined
-    // has not waited max_waiting_time yet (env/task_env.py:269), which needs max_waiting_time > 0 (the reference's 10 / 100):
-    // a handle with max_waiting_time <= 0 (or NaN) takes the general kernels, which evaluate the rule literally.
-    const bool quiet_ok = env->kp.mwt > 0.0;
 #ifndef DCM_NO_FAST_STEP
     // The plain call shape on a one-chunk layout: the register-resident step (step_fast.hpp); same contract, same results.
-    if (quiet_ok && env->L.C == M && env->L.A <= 64 && env->L.T <= 64 && env->T <= 63 && !leader_in && !nfol_in && !env->log.len && agents_out && tasks_out &&
+    if (one_chunk_ok(env) && !leader_in && !nfol_in && !env->log.len && agents_out && tasks_out &&
         mask_out && leader_out && active_out && !(env->p.flags & DCM_PARAM_NO_GROUPING)) {
         // Deferred terminal metrics (dcm_env::side) for auto-resetting handles: not under stream capture -- the periodic flush is a
         // host-side decision and the buffers are allocated on first use -- where episode ends keep computing their metrics inline.
@@ -2155,9 +2186,7 @@ int dcm_step(dcm_env* env, const int32_t* actions, const int32_t* leader_in, con
                        env->state, actions, agents_out, tasks_out, mask_out, leader_out, active_out, env->summary, env->ablog,  \
                        env->p.flags, (const int32_t*)env->sizes, env->gscratch, env->p.auto_reset_episodes, env->retlog, (int)env->retcap, \
                        env->side, env->side_pitch, pendq, (pendq && env->init_valid) ? (const unsigned char*)env->init : nullptr)
-        const bool exact_ = !env->sizes && env->A == env->L.A && env->T == env->L.T;
-        if (env->L.A == 20 && env->L.T == 50) { if (exact_) { CALL(20, 50, false); } else { CALL(20, 50, true); } }
-        else { CALL(64, 64, true); }
+        DISPATCH_ONE_CHUNK(env, CALL);
 #undef CALL
         LAUNCH_OK();
         if (pendq) {
@@ -2185,56 +2214,46 @@ int dcm_rollout_random(dcm_env* env, int32_t episodes, int64_t max_decisions, co
     if (!env->reset_done) return fail(DCM_ERR_STATE, "dcm_rollout_random: call dcm_reset first");
     if (episodes < 1) return fail(DCM_ERR_INVALID, "dcm_rollout_random: episodes must be >= 1");
     { const int rc_ = dcm::flush_pending(env, stream); if (rc_ != DCM_OK) return rc_; }
-    const bool quiet_ok = env->kp.mwt > 0.0;     // (see dcm_step)
+    const dcm::RolloutArgs ra{DIMS(env), env->kp, env->state, (int)episodes, agents_out, tasks_out, mask_out, steps_out, env->summary,
+                              env->ablog, (const int32_t*)env->sizes, max_decisions, max_decisions_in, env->gscratch, env->retlog,
+                              (int)env->retcap};
 #ifndef DCM_NO_FAST_ROLLOUT
-    // One-chunk layouts (one lane per agent and per task, lane 63 free for the depot) with all three observation buffers or
-    // none: the register-resident kernel.  Same contract, same results (tests/test_gpu_rollout.py runs both).
+    // One-chunk layouts with all three observation buffers or none: the register-resident kernel.  Same contract, same results
+    // (tests/test_gpu_rollout.py runs both).
     const bool all_obs = agents_out && tasks_out && mask_out, no_obs = !agents_out && !tasks_out && !mask_out;
-    if (quiet_ok && env->L.C == M && env->L.A <= 64 && env->L.T <= 64 && env->T <= 63 && (all_obs || no_obs)) {
+    if (one_chunk_ok(env) && (all_obs || no_obs)) {
 #define CALLF(CA, CT, RS, OBS, PRIO)                                                                                  \
-    hipLaunchKernelGGL((k_rollout_fast<CA, CT, RS, OBS, PRIO>), GRID(env),                                            \
-                       (Sim<CA, CT, RS>::SCR_IN_LDS ? env->L.lds_bytes() : Sim<CA, CT, RS>::lds_image_bytes(env->L)) + 512u, (hipStream_t)stream, DIMS(env), \
-                       env->kp, env->state, (int)episodes, agents_out, tasks_out, mask_out, steps_out, env->summary, env->ablog, \
-                       (const int32_t*)env->sizes, max_decisions, max_decisions_in, env->gscratch, env->retlog, (int)env->retcap)
+    launch_rollout(k_rollout_fast<CA, CT, RS, OBS, PRIO>, GRID(env),                                                  \
+                   (Sim<CA, CT, RS>::SCR_IN_LDS ? env->L.lds_bytes() : Sim<CA, CT, RS>::lds_image_bytes(env->L)) + 512u, (hipStream_t)stream, ra)
         // wave priorities (k_rollout_fast, PRIO) for a launch that fills the machine by itself: 16 workgroups x 256 CUs
         const bool prio = env->p.n_envs >= 4096;
 #define CALL(CA, CT, RS) do { if (prio) { if (all_obs) { CALLF(CA, CT, RS, true, true); } else { CALLF(CA, CT, RS, false, true); } }   \
                               else { if (all_obs) { CALLF(CA, CT, RS, true, false); } else { CALLF(CA, CT, RS, false, false); } } } while (0)
-        const bool exact_ = !env->sizes && env->A == env->L.A && env->T == env->L.T;
-        if (env->L.A == 20 && env->L.T == 50) { if (exact_) { CALL(20, 50, false); } else { CALL(20, 50, true); } }
-        else { CALL(64, 64, true); }
+        DISPATCH_ONE_CHUNK(env, CALL);
 #undef CALL
 #undef CALLF
         LAUNCH_OK();
         return DCM_OK;
     }
     // BASELINE configs[3], 50A/200T exactly: the multi-chunk register-resident kernel (rollout_fast_mc.hpp)
-    if (quiet_ok && env->L.C == M && !env->sizes && env->A == 50 && env->T == 200 && env->L.A == 50 && env->L.T == 200 && (all_obs || no_obs)) {
-#define CALLM(OBS)                                                                                                    \
-    hipLaunchKernelGGL((k_rollout_fast_mc<50, 200, OBS>), GRID(env), (FastM<50, 200, OBS>::LDS_BYTES), (hipStream_t)stream, \
-                       DIMS(env), env->kp, env->state, (int)episodes, agents_out, tasks_out, mask_out, steps_out, env->summary, env->ablog, \
-                       (const int32_t*)env->sizes, max_decisions, max_decisions_in, env->gscratch, env->retlog, (int)env->retcap)
-        if (all_obs) { CALLM(true); } else { CALLM(false); }
-#undef CALLM
+    if (quiet_ok(env) && env->L.C == M && !env->sizes && env->A == 50 && env->T == 200 && env->L.A == 50 && env->L.T == 200 && (all_obs || no_obs)) {
+        if (all_obs) launch_rollout(k_rollout_fast_mc<50, 200, true>, GRID(env), FastM<50, 200, true>::LDS_BYTES, (hipStream_t)stream, ra);
+        else launch_rollout(k_rollout_fast_mc<50, 200, false>, GRID(env), FastM<50, 200, false>::LDS_BYTES, (hipStream_t)stream, ra);
         LAUNCH_OK();
         return DCM_OK;
     }
     // Every other batch of the mid-size class (A <= 128, T <= 256; uniform or ragged): rollout_fast_g.hpp, chunk counts from the batch dims
-    if (quiet_ok && env->L.C == M && env->A <= 128 && env->T <= 256 && !(env->L.A == 20 && env->L.T == 50) && !(env->L.A == 64 && env->L.T == 64) &&
+    if (quiet_ok(env) && env->L.C == M && env->A <= 128 && env->T <= 256 && !(env->L.A == 20 && env->L.T == 50) && !(env->L.A == 64 && env->L.T == 64) &&
         (all_obs || no_obs)) {
         dcm::launch_rollout_fast_g(env->A > 64 ? 2 : 1, env->T > 192 ? 4 : (env->T > 128 ? 3 : 2), all_obs, (unsigned)env->p.n_envs,
-                                   (unsigned)(Sim<128, 256, true>::lds_image_bytes(env->L)) + 512u, (hipStream_t)stream, DIMS(env), env->kp,
-                                   env->state, (int)episodes, agents_out, tasks_out, mask_out, steps_out, env->summary, env->ablog,
-                                   (const int32_t*)env->sizes, max_decisions, max_decisions_in, env->gscratch, env->retlog, (int)env->retcap);
+                                   (unsigned)(Sim<128, 256, true>::lds_image_bytes(env->L)) + 512u, (hipStream_t)stream, ra);
         LAUNCH_OK();
         return DCM_OK;
     }
 #endif
 #define CALL(CA, CT, RS, ...)                                                                                         \
-    hipLaunchKernelGGL((k_rollout_random<CA, CT, RS, ##__VA_ARGS__>), GRID(env),                                                     \
-                       (Sim<CA, CT, RS>::SCR_IN_LDS ? env->L.lds_bytes() : Sim<CA, CT, RS, ((CT) > WAVE) && !(RS)>::lds_image_bytes(env->L)), (hipStream_t)stream, DIMS(env), \
-                       env->kp, env->state, (int)episodes, agents_out, tasks_out, mask_out, steps_out, env->summary, env->ablog, \
-                       (const int32_t*)env->sizes, max_decisions, max_decisions_in, env->gscratch, env->retlog, (int)env->retcap)
+    launch_rollout(k_rollout_random<CA, CT, RS, ##__VA_ARGS__>, GRID(env),                                            \
+                   (Sim<CA, CT, RS>::SCR_IN_LDS ? env->L.lds_bytes() : Sim<CA, CT, RS, ((CT) > WAVE) && !(RS)>::lds_image_bytes(env->L)), (hipStream_t)stream, ra)
     DISPATCH_ENV(env, CALL);
 #undef CALL
     LAUNCH_OK();

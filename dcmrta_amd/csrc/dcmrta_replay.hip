@@ -101,10 +101,6 @@ __device__ double py_floordiv(double vx, double wx) {
 #define RPH_COUNT(i)
 #endif
 
-__device__ __forceinline__ double rl(double v, int l) {
-    return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), l), __builtin_amdgcn_readlane(__double2loint(v), l));
-}
-
 struct Rep {
     int A, T, MR;
     unsigned char* b;

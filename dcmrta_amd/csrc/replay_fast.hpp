@@ -26,11 +26,6 @@
 // ordered member ids / len(abandoned_agent), the agents' travel_dist (ds_add_f64 by the agent's own lane) and max(arrival_time).  About 9 KB per env at 100A/500T; after the loop the head of the same bytes holds the terminal metrics'
 // serial-sum inputs (f64[T] + f64[A]).  time_start is written once per task to the handle's HBM scratch and read back at the end.
 
-__device__ __forceinline__ int rli(int v, int l) { return __builtin_amdgcn_readlane(v, l); }
-__device__ __forceinline__ uint64_t rl64(uint64_t v, int l) {
-    return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(v >> 32), l) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)v, l);
-}
-
 // LDS layout of k_replay_fast<NAC, NTL, ...>: [routes | txy | dur] are dead after the event loop and then hold tw f64[T], awl f64[A]
 struct FL {
     int A, T, cap, NA, NT;                                                   // NA = 64 NAC agent lanes, NT = 64 NTL live-task lanes

@@ -74,18 +74,6 @@ struct Fast {
         inA = lane < A_; inT = lane < T_; isD = lane == DL;
         la = inA ? lane : 0; lt = inT ? lane : 0;
     }
-    // position of the idx-th (0-based) set bit of m, idx < popcount(m): the lanes up to and including it are exactly those with
-    // fewer than idx + 1 set bits below them
-    __device__ __forceinline__ static int nth(uint64_t m, int idx) {
-        const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-        return __popcll(__ballot(rank <= idx)) - 1;
-    }
-    __device__ __forceinline__ static double rl(double v, int src) {
-        return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), src), __builtin_amdgcn_readlane(__double2loint(v), src));
-    }
-    __device__ __forceinline__ static uint64_t rl(uint64_t v, int src) {
-        return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(v >> 32), src) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, src);
-    }
 
     // ------------------------------------------------------------------------------ registers <-> LDS image
     __device__ __forceinline__ void load_consts(R& r) const {
@@ -527,9 +515,7 @@ __global__ __launch_bounds__(WAVE, 4) void k_rollout_fast(int A, int T, int PA, 
         mkp = mk + (f.inT ? lane + 1 : 0);
     }
     double* row = summary + (size_t)e * 8;
-    constexpr int NO_BUDGET = 0x7FFFFFFF;
-    int64_t bud = budget_in ? budget_in[e] : budget_all;
-    const int left0 = uni((int)((bud < 0 || bud >= NO_BUDGET) ? NO_BUDGET : bud));
+    const int left0 = rollout_budget(e, budget_all, budget_in);
     int left = left0;
     uint64_t gd = h.seed + GAMMA * (h.d + 1);
     // the choice-protocol keys of the next 64 decisions, one per lane (25 VALU instructions per 64 decisions instead of a dependent
@@ -541,7 +527,6 @@ __global__ __launch_bounds__(WAVE, 4) void k_rollout_fast(int A, int T, int PA, 
     typename F::R r;
     f.load_consts(r);
     FPH_START(f);
-    constexpr uint32_t ERR = DCM_FLAG_BAD_ACTION | DCM_FLAG_OVERFLOW | DCM_FLAG_BAD_LEADER | DCM_FLAG_BAD_INSTANCE;
     PH_DECL;
     int ep = 0;
     bool need_adv = false;       // the general event code has to run on the (flushed) LDS image before the next decision
@@ -571,7 +556,7 @@ __global__ __launch_bounds__(WAVE, 4) void k_rollout_fast(int A, int T, int PA, 
         if (!need_adv) {         // head of an episode slot (the `for ep` of k_rollout_random)
             if (ep >= episodes) break;
             if (h.flags & DCM_FLAG_DONE) {   // restart from the loaded instance; d keeps running
-                if (h.flags & ERR) break;
+                if (h.flags & ROLLOUT_ERR) break;
                 if (left == 0) break;        // budget spent at an episode boundary: the finished episode's results stay readable
                 S.reset_state(h, lane);
                 need_adv = true;
@@ -592,7 +577,7 @@ __global__ __launch_bounds__(WAVE, 4) void k_rollout_fast(int A, int T, int PA, 
             for (;;) {
                 FPHK(f, 12);
                 CNT(0);
-                const uint64_t k1 = F::rl(kv, ki), k2 = F::rl(kv2, ki);
+                const uint64_t k1 = rl(kv, ki), k2 = rl(kv2, ki);
                 const int rlen = f.decide(r, h, P, lane, k1, agrow, tkrow, mkp, &k2, use_prio ? &nv_last : nullptr);
                 if (h.flags & DCM_FLAG_DONE) break;
                 gd += GAMMA;

@@ -54,10 +54,6 @@ struct FastG {
     __device__ __forceinline__ uint64_t amask(int c) const { return cmask(S.rA, c); }
     __device__ __forceinline__ uint64_t tmask(int c) const { return cmask(S.rT, c); }
     __device__ __forceinline__ double* slots() const { return S.marr(); }
-    __device__ __forceinline__ static int nth(uint64_t m, int idx) {
-        const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-        return __popcll(__ballot(rank <= idx)) - 1;
-    }
     // agent id of the idx-th set bit of a per-chunk agent mask
     __device__ __forceinline__ static int nth_agent(const uint64_t (&m)[NAC], int idx) {
         if constexpr (NAC == 1) return nth(m[0], idx);
@@ -65,27 +61,6 @@ struct FastG {
             const int n0 = __popcll(m[0]);
             return idx < n0 ? nth(m[0], idx) : 64 + nth(m[1], idx - n0);
         }
-    }
-    __device__ __forceinline__ static double rl(double v, int src) {
-        return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), src), __builtin_amdgcn_readlane(__double2loint(v), src));
-    }
-    __device__ __forceinline__ static uint64_t rl(uint64_t v, int src) {
-        return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(v >> 32), src) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, src);
-    }
-    __device__ __forceinline__ static uint32_t rl(uint32_t v, int src) { return (uint32_t)__builtin_amdgcn_readlane((int)v, src); }
-    // value of a per-chunk register array at the wave-uniform position (chunk, lane): every chunk's lane is read, scalar selects pick
-    // (branches around two v_readlane cost more than the reads)
-    __device__ __forceinline__ static uint32_t sel(bool c, uint32_t a, uint32_t b) { return c ? a : b; }
-    __device__ __forceinline__ static uint64_t sel(bool c, uint64_t a, uint64_t b) { return c ? a : b; }
-    __device__ __forceinline__ static double sel(bool c, double a, double b) {
-        return __longlong_as_double((long long)sel(c, (uint64_t)__double_as_longlong(a), (uint64_t)__double_as_longlong(b)));
-    }
-    template <class V, int N>
-    __device__ __forceinline__ static V rlc(const V (&v)[N], int chunk, int src) {
-        V out = rl(v[0], src);
-#pragma unroll
-        for (int c = 1; c < N; c++) out = sel(c == chunk, rl(v[c], src), out);
-        return out;
     }
 
     // ------------------------------------------------------------------------------ registers <-> LDS image
@@ -599,15 +574,12 @@ __global__ __launch_bounds__(WAVE, DCM_G_WAVES) void k_rollout_fast_g(int A, int
         S.write_pad_obs(lane, A, T, ag, tk, mk);
     }
     double* row = summary + (size_t)e * 8;
-    constexpr int NO_BUDGET = 0x7FFFFFFF;
-    int64_t bud = budget_in ? budget_in[e] : budget_all;
-    const int left0 = uni((int)((bud < 0 || bud >= NO_BUDGET) ? NO_BUDGET : bud));
+    const int left0 = rollout_budget(e, budget_all, budget_in);
     int left = left0;
     uint64_t gd = h.seed + GAMMA * (h.d + 1);
     const uint64_t d0 = h.d;
     typename F::R r;
     f.load_consts(r, lane);
-    constexpr uint32_t ERR = DCM_FLAG_BAD_ACTION | DCM_FLAG_OVERFLOW | DCM_FLAG_BAD_LEADER | DCM_FLAG_BAD_INSTANCE;
     PH_DECL;
     int ep = 0;
     bool need_adv = false;
@@ -615,7 +587,7 @@ __global__ __launch_bounds__(WAVE, DCM_G_WAVES) void k_rollout_fast_g(int A, int
         if (!need_adv) {         // head of an episode slot (the `for ep` of k_rollout_random)
             if (ep >= episodes) break;
             if (h.flags & DCM_FLAG_DONE) {
-                if (h.flags & ERR) break;
+                if (h.flags & ROLLOUT_ERR) break;
                 if (left == 0) break;
                 S.reset_state(h, lane);
                 need_adv = true;

@@ -68,17 +68,6 @@ struct FastM {
         inA = lane < CA; isD = lane == DL;
         la = inA ? lane : 0;
     }
-    __device__ __forceinline__ static int nth(uint64_t m, int idx) {
-        const int rank = (int)__builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
-        return __popcll(__ballot(rank <= idx)) - 1;
-    }
-    __device__ __forceinline__ static double rl(double v, int src) {
-        return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(v), src), __builtin_amdgcn_readlane(__double2loint(v), src));
-    }
-    __device__ __forceinline__ static uint64_t rl(uint64_t v, int src) {
-        return ((uint64_t)(uint32_t)__builtin_amdgcn_readlane((int)(v >> 32), src) << 32) | (uint32_t)__builtin_amdgcn_readlane((int)(uint32_t)v, src);
-    }
-    __device__ __forceinline__ static uint32_t rl(uint32_t v, int src) { return (uint32_t)__builtin_amdgcn_readlane((int)v, src); }
 
     // ------------------------------------------------------------------------------ registers <-> LDS image / HBM record
     __device__ __forceinline__ void load_consts(R& r, const typename SimT::XY& xy, int lane) const {
@@ -519,15 +508,12 @@ __global__ __launch_bounds__(WAVE, DCM_MC_WAVES) void k_rollout_fast_mc(int A, i
         mk = mask_out + (size_t)e * (CT + 1);
     }
     double* row = summary + (size_t)e * 8;
-    constexpr int NO_BUDGET = 0x7FFFFFFF;
-    int64_t bud = budget_in ? budget_in[e] : budget_all;
-    const int left0 = uni((int)((bud < 0 || bud >= NO_BUDGET) ? NO_BUDGET : bud));
+    const int left0 = rollout_budget(e, budget_all, budget_in);
     int left = left0;
     uint64_t gd = h.seed + GAMMA * (h.d + 1);
     const uint64_t d0 = h.d;
     typename F::R r;
     f.load_consts(r, xy, lane);
-    constexpr uint32_t ERR = DCM_FLAG_BAD_ACTION | DCM_FLAG_OVERFLOW | DCM_FLAG_BAD_LEADER | DCM_FLAG_BAD_INSTANCE;
     PH_DECL;
     int ep = 0;
     bool need_adv = false;
@@ -535,7 +521,7 @@ __global__ __launch_bounds__(WAVE, DCM_MC_WAVES) void k_rollout_fast_mc(int A, i
         if (!need_adv) {         // head of an episode slot (the `for ep` of k_rollout_random)
             if (ep >= episodes) break;
             if (h.flags & DCM_FLAG_DONE) {
-                if (h.flags & ERR) break;
+                if (h.flags & ROLLOUT_ERR) break;
                 if (left == 0) break;
                 S.reset_state(h, lane);
                 need_adv = true;
