@@ -335,6 +335,31 @@ class BatchedTaskEnv:
         with torch.cuda.device(self.device):
             check(self._lib.dcm_load_routes(self._h, _ptr(d_arr), _ptr(d_ln), int(routes.shape[2]), int(member_cap), self._stream()))
             torch.cuda.current_stream(self.device).synchronize()
+        self._replay_member_cap = int(member_cap)
+        rlog = getattr(self, "_rlog", None)
+        if rlog is not None and rlog["members"].shape[2] != self._replay_member_cap:
+            self.enable_replay_log(rlog["route"].shape[2])                   # member_cols follows the routes' member_cap
+        return self
+
+    def enable_replay_log(self, cap=64):
+        """Record what execute_routes leaves for generate_traj (dcm_set_replay_log): every agent_step's (task id, -1 = depot;
+        arrival) in route[B,A,cap] / arrival[B,A,cap] / route_len[B,A] (agent['route'] / ['arrival_time']), and after the replay
+        members[B,T,member_cols] (task['members'], -1 padded) and feasible[B,T] (task['feasible_assignment']).  member_cols = the
+        member_cap of the last load_routes (re-allocated there when it changes).  cap = 0 disables."""
+        B, A, T, dev = self.B, self.A, self.T, self.device
+        if not cap:
+            check(self._lib.dcm_set_replay_log(self._h, None, None, None, 0, None, 0, None))
+            self._rlog = None
+            return self
+        mc = getattr(self, "_replay_member_cap", 8)
+        self._rlog = dict(route=torch.full((B, A, cap), -2, dtype=torch.int16, device=dev),
+                          arrival=torch.zeros((B, A, cap), dtype=torch.float64, device=dev),
+                          route_len=torch.zeros((B, A), dtype=torch.int32, device=dev),
+                          members=torch.full((B, T, mc), -1, dtype=torch.int16, device=dev),
+                          feasible=torch.zeros((B, T), dtype=torch.uint8, device=dev))
+        r = self._rlog
+        check(self._lib.dcm_set_replay_log(self._h, _ptr(r["route"]), _ptr(r["arrival"]), _ptr(r["route_len"]), int(cap),
+                                           _ptr(r["members"]), mc, _ptr(r["feasible"])))
         return self
 
     def set_visibility(self, initial=20, batch=20, period=10, cap=100):
@@ -353,7 +378,9 @@ class BatchedTaskEnv:
 
     def execute_routes(self, reactive=False, fields=None):
         """execute_by_route + get_episode_reward for every env; returns a dict of device tensors.
-        fields: which of the optional per-task / per-agent arrays to produce (default: all; () = steps, flags, summary only)."""
+        fields: which of the optional per-task / per-agent arrays to produce (default: all; () = steps, flags, summary only).
+        With the replay log on (enable_replay_log) the dict also holds its buffers -- route, arrival, route_len, members,
+        feasible -- which the next execute_routes overwrites."""
         B, A, T, dev = self.B, self.A, self.T, self.device
         spec = dict(finished=((B, T), torch.uint8), time_start=((B, T), torch.float64), time_finish=((B, T), torch.float64),
                     task_wait=((B, T), torch.float64), n_members=((B, T), torch.int32), agent_wait=((B, A), torch.float64),
@@ -365,6 +392,8 @@ class BatchedTaskEnv:
             check(self._lib.dcm_execute_routes(self._h, int(bool(reactive)), *[_ptr(v) for v in o.values()], self._stream()))
         o = {k: v for k, v in o.items() if v is not None}
         o["summary"] = self.summary()
+        if getattr(self, "_rlog", None) is not None:
+            o.update(self._rlog)
         return o
 
     # ------------------------------------------------------------------ snapshot (copy.deepcopy(env), worker.py:33)

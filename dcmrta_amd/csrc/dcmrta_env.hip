@@ -2112,11 +2112,7 @@ int dcm_reset(dcm_env* env, const uint64_t* seeds, void* stream) {
 
 int dcm_set_route_log(dcm_env* env, int16_t* route_task, double* route_arrival, int32_t* route_len, int32_t cap) {
     CHECK_HANDLE(env);
-    const bool off = !route_task && !route_arrival && !route_len;
-    if (!off && (!route_task || !route_arrival || !route_len || cap < 1))
-        return fail(DCM_ERR_INVALID, "dcm_set_route_log: give all three arrays and cap >= 1, or all NULL");
-    env->log = RouteLog{route_task, route_arrival, route_len, off ? 0 : cap};
-    return DCM_OK;
+    return make_route_log("dcm_set_route_log", route_task, route_arrival, route_len, cap, &env->log);
 }
 
 int dcm_set_return_log(dcm_env* env, double* returns, int32_t cap) {

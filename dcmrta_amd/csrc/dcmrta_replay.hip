@@ -80,6 +80,17 @@ struct RP {
     int vis_initial, vis_batch, vis_period, vis_cap;
 };
 
+// The replay log (dcm_set_replay_log), read only by the LOG = true instantiations of both kernels: every agent_step appends (task id,
+// -1 = depot; arrival time) to its agent's row of `route` (agent['route'] / ['arrival_time'], env/task_env.py:314,318; entries beyond
+// route.cap are counted, not stored), and after the event loop the final task['members'] (list order, -1 padded) and
+// task['feasible_assignment'] of every task are written -- what generate_traj reads (:375-418).
+struct ReplayLog {
+    RouteLog route;          // task / arrival [B][A][cap], len [B][A]
+    int16_t* members;        // [B][T][member_cols] or nullptr
+    int32_t member_cols;
+    uint8_t* feasible;       // [B][T] or nullptr
+};
+
 // Python float floor division (now // 10, env/task_env.py:567)
 __device__ double py_floordiv(double vx, double wx) {
     double mod = fmod(vx, wx), div = (vx - mod) / wx, fl;
@@ -387,14 +398,16 @@ struct Rep {
 };
 
 // <CA, CT, CMR> = the batch's agents / tasks / member slots as compile-time constants (every LDS offset and loop bound folds), or
-// <0, 0, 0> = read from the arguments.  SLDS: the replay scratch block in LDS instead of HBM (see replay_lds_bytes).
-template <int CA, int CT, int CMR, bool SLDS>
+// <0, 0, 0> = read from the arguments.  SLDS: the replay scratch block in LDS instead of HBM (see replay_lds_bytes).  LOG: write the
+// replay log LG (LOG = false never reads it).
+template <int CA, int CT, int CMR, bool SLDS, bool LOG>
 __global__ __launch_bounds__(WAVE) void k_replay(int A_, int T_, int PA, int PT, int MR_, RP P, const unsigned char* state,
                                                 const int32_t* routes, const int32_t* route_len, int route_cap,
                                                 double* summary, int64_t* steps_out, uint32_t* flags_out,
                                                 uint8_t* finished, double* time_start, double* time_finish,
                                                 double* task_wait, int32_t* n_members, double* agent_wait,
-                                                double* travel_dist, uint8_t* returned, unsigned char* gscr, double* member_arrivals) {
+                                                double* travel_dist, uint8_t* returned, unsigned char* gscr, double* member_arrivals,
+                                                ReplayLog LG) {
     const int e = blockIdx.x, lane = threadIdx.x;
     const int A = CA ? CA : A_, T = CT ? CT : T_, MR = CMR ? CMR : MR_;
     const Lay EL{PA, PT};                                      // layout dims of the handle's records (>= the batch dims)
@@ -448,6 +461,9 @@ __global__ __launch_bounds__(WAVE) void k_replay(int A_, int T_, int PA, int PT,
     WSYNC();
     uint32_t tu_what = 0;
     int ninf_vis = 0;
+    int rlen[AW_MAX];                   // LOG: len(agent['route']) of agent i * 64 + lane, kept by the agent's own lane
+#pragma unroll
+    for (int i = 0; i < AW_MAX; i++) rlen[i] = 0;
     RPH_DECL;
     // next_decision_time of the lane's agents (NaN beyond A) and their minimum: read once per event, by check_finished, and used
     // again by next_decision of the following event (nothing changes them in between)
@@ -580,6 +596,15 @@ __global__ __launch_bounds__(WAVE) void k_replay(int A_, int T_, int PA, int PT,
                         R.wake()[k] = -__builtin_inff();                     // its member list changed: the next task_update visits it
                     }
                 }
+                if constexpr (LOG) {                                         // agent['route'].append :314, ['arrival_time'] += :318
+                    const bool own = lane == (a & (WAVE - 1));
+                    if (own && rlen[i] < LG.route.cap) {
+                        const size_t o = ((size_t)e * A + a) * LG.route.cap + rlen[i];
+                        LG.route.task[o] = (int16_t)k;
+                        LG.route.arrival[o] = arrival;
+                    }
+                    rlen[i] += own ? 1 : 0;
+                }
                 if (++steps > step_cap) flags |= DCM_FLAG_TRUNCATED | DCM_FLAG_OVERFLOW;
                 WSYNC();
                 RPH(4); RPH_COUNT(7);
@@ -643,6 +668,23 @@ __global__ __launch_bounds__(WAVE) void k_replay(int A_, int T_, int PA, int PT,
         } else finished_flag = false;
     }
     WSYNC();
+    if constexpr (LOG) {                                                     // the log's lengths, final member lists and feasibility
+#pragma unroll
+        for (int i = 0; i < AW_MAX; i++) {
+            const int a = i * WAVE + lane;
+            if (a < A) LG.route.len[(size_t)e * A + a] = rlen[i];
+        }
+#pragma nounroll
+        for (int t = lane; t < T; t += WAVE) {
+            const uint32_t info = R.tinfo()[t];
+            const int n = (info >> 16) & 0xFF;                               // <= MR <= member_cols (checked by the host)
+            if (LG.members) {
+                int16_t* row = LG.members + ((size_t)e * T + t) * LG.member_cols;
+                for (int j = 0; j < LG.member_cols; j++) row[j] = j < n ? (int16_t)R.mid()[j * T + t] : (int16_t)-1;
+            }
+            if (LG.feasible) LG.feasible[(size_t)e * T + t] = (info & T_FEAS) ? 1 : 0;
+        }
+    }
     if (time_finish) for (int t = lane; t < T; t += WAVE) time_finish[(size_t)e * T + t] = R.tf()[t];
     WSYNC();
     // ---- get_episode_reward: calculate_waiting_time :344-364 (np.sum = pairwise block for n >= 8)
@@ -799,10 +841,30 @@ int dcm_set_replay_placement(dcm_env* env, int32_t placement) {
     return DCM_OK;
 }
 
+int dcm_set_replay_log(dcm_env* env, int16_t* route_task, double* route_arrival, int32_t* route_len, int32_t cap,
+                       int16_t* member_ids, int32_t member_cols, uint8_t* feasible) {
+    CHECK_HANDLE(env);
+    RouteLog r;
+    const int rc = make_route_log("dcm_set_replay_log", route_task, route_arrival, route_len, cap, &r);
+    if (rc != DCM_OK) return rc;
+    if (r.cap == 0 && (member_ids || feasible))
+        return fail(DCM_ERR_INVALID, "dcm_set_replay_log: member_ids / feasible need the route arrays (all NULL disables the log)");
+    if (member_ids && member_cols < 1) return fail(DCM_ERR_INVALID, "dcm_set_replay_log: member_ids needs member_cols >= 1");
+    env->rlog = r;
+    env->rlog_members = member_ids;
+    env->rlog_member_cols = member_ids ? member_cols : 0;
+    env->rlog_feasible = feasible;
+    return DCM_OK;
+}
+
 int dcm_execute_routes(dcm_env* env, int32_t reactive, int64_t* steps_out, uint32_t* flags_out, uint8_t* finished,
                        double* time_start, double* time_finish, double* task_wait, int32_t* n_members,
                        double* agent_wait, double* travel_dist, uint8_t* returned, void* stream) {
     CHECK_ENV(env);
+    const ReplayLog LG{env->rlog, env->rlog_members, env->rlog_member_cols, env->rlog_feasible};
+    const bool log = LG.route.cap > 0;
+    if (log && LG.members && LG.member_cols < env->member_cap)
+        return fail(DCM_ERR_INVALID, "dcm_execute_routes: the replay log's member_cols is smaller than the member_cap of dcm_load_routes");
     { const int rc_ = dcm::flush_pending(env, stream); if (rc_ != DCM_OK) return rc_; }
     if (!env->loaded) return fail(DCM_ERR_STATE, "dcm_execute_routes: call dcm_load_instances first");
     if (!env->routes) return fail(DCM_ERR_STATE, "dcm_execute_routes: call dcm_load_routes first");
@@ -827,34 +889,38 @@ int dcm_execute_routes(dcm_env* env, int32_t reactive, int64_t* steps_out, uint3
         const int TL = reactive ? (env->T < env->vis[3] ? env->T : env->vis[3]) : env->T;
         const uint32_t flds = replay_fast_lds_bytes(env->A, env->T, env->route_cap);   // (route_cap < 32768: the cursor and the length share a word)
         if (env->replay_placement == 0 && env->A <= 2 * WAVE && TL <= 2 * WAVE && env->member_cap <= 8 && flds <= 64u * 1024u && env->route_cap < 32768) {
-#define REPLAYF(CMR, RE)                                                                                                     \
+#define REPLAYF(CMR, RE, LOG)                                                                                                \
     do {                                                                                                                    \
-        (void)hipFuncSetAttribute((const void*)k_replay_fast<2, 2, CMR, RE>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)flds); \
-        hipLaunchKernelGGL((k_replay_fast<2, 2, CMR, RE>), GRID(env), flds, (hipStream_t)stream, env->A, env->T, TL, env->L.A, env->L.T, \
+        (void)hipFuncSetAttribute((const void*)k_replay_fast<2, 2, CMR, RE, LOG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)flds); \
+        hipLaunchKernelGGL((k_replay_fast<2, 2, CMR, RE, LOG>), GRID(env), flds, (hipStream_t)stream, env->A, env->T, TL, env->L.A, env->L.T, \
                            env->member_cap, P, env->state, env->routes, env->route_len, env->route_cap, env->summary,      \
                            steps_out, flags_out, finished, time_start, time_finish, task_wait, n_members, agent_wait,       \
-                           travel_dist, returned, env->gscratch);                                                          \
+                           travel_dist, returned, env->gscratch, LG);                                                      \
     } while (0)
-            if (env->member_cap <= 5) { if (reactive) REPLAYF(5, true); else REPLAYF(5, false); }
-            else { if (reactive) REPLAYF(8, true); else REPLAYF(8, false); }
+#define REPLAYF_L(CMR, RE) do { if (log) REPLAYF(CMR, RE, true); else REPLAYF(CMR, RE, false); } while (0)
+            if (env->member_cap <= 5) { if (reactive) REPLAYF_L(5, true); else REPLAYF_L(5, false); }
+            else { if (reactive) REPLAYF_L(8, true); else REPLAYF_L(8, false); }
+#undef REPLAYF_L
 #undef REPLAYF
             LAUNCH_OK();
             return DCM_OK;
         }
     }
-#define REPLAY(CA, CT, CMR, SL)                                                                                              \
+#define REPLAY(CA, CT, CMR, SL, LOG)                                                                                         \
     do {                                                                                                                    \
-        (void)hipFuncSetAttribute((const void*)k_replay<CA, CT, CMR, SL>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
-        hipLaunchKernelGGL((k_replay<CA, CT, CMR, SL>), GRID(env), lds, (hipStream_t)stream, env->A, env->T, env->L.A, env->L.T,  \
+        (void)hipFuncSetAttribute((const void*)k_replay<CA, CT, CMR, SL, LOG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
+        hipLaunchKernelGGL((k_replay<CA, CT, CMR, SL, LOG>), GRID(env), lds, (hipStream_t)stream, env->A, env->T, env->L.A, env->L.T, \
                            env->member_cap, P, env->state, env->routes, env->route_len, env->route_cap, env->summary,      \
                            steps_out, flags_out, finished, time_start, time_finish, task_wait, n_members, agent_wait,       \
-                           travel_dist, returned, env->gscratch, env->rmarr);                                              \
+                           travel_dist, returned, env->gscratch, env->rmarr, LG);                                          \
     } while (0)
+#define REPLAY_L(CA, CT, CMR, SL) do { if (log) REPLAY(CA, CT, CMR, SL, true); else REPLAY(CA, CT, CMR, SL, false); } while (0)
     const bool base5 = env->A == 100 && env->T == 500 && env->member_cap == 5;   // BASELINE config 5
-    if (base5 && slds) REPLAY(100, 500, 5, true);
-    else if (base5) REPLAY(100, 500, 5, false);
-    else if (slds) REPLAY(0, 0, 0, true);
-    else REPLAY(0, 0, 0, false);
+    if (base5 && slds) REPLAY_L(100, 500, 5, true);
+    else if (base5) REPLAY_L(100, 500, 5, false);
+    else if (slds) REPLAY_L(0, 0, 0, true);
+    else REPLAY_L(0, 0, 0, false);
+#undef REPLAY_L
 #undef REPLAY
     LAUNCH_OK();
     return DCM_OK;

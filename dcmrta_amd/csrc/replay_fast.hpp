@@ -49,13 +49,14 @@ __host__ __device__ inline uint32_t replay_fast_lds_bytes(int A, int T, int rout
                                 // exit in its middle -- round 6; four fit without spills, 128 VGPRs, and measure the same: 2.01e9 both ways)
 #endif
 
-template <int NAC, int NTL, int CMR, bool REACTIVE>
+// LOG: write the replay log LG (ReplayLog in dcmrta_replay.hip; LOG = false never reads it).
+template <int NAC, int NTL, int CMR, bool REACTIVE, bool LOG>
 __global__ __launch_bounds__(WAVE, DCM_REPLAY_WAVES) void k_replay_fast(int A, int T, int TL, int PA, int PT, int MR, RP P, const unsigned char* state,
                                                      const int32_t* routes, const int32_t* route_len, int route_cap,
                                                      double* summary, int64_t* steps_out, uint32_t* flags_out,
                                                      uint8_t* finished, double* time_start, double* time_finish,
                                                      double* task_wait, int32_t* n_members, double* agent_wait,
-                                                     double* travel_dist, uint8_t* returned, unsigned char* gscr) {
+                                                     double* travel_dist, uint8_t* returned, unsigned char* gscr, ReplayLog LG) {
     static_assert(CMR <= 8, "member ids: one byte each of one 64-bit word");
     const int e = blockIdx.x, lane = threadIdx.x;
     const Lay EL{PA, PT};                                      // layout dims of the handle's records (>= the batch dims)
@@ -101,8 +102,10 @@ __global__ __launch_bounds__(WAVE, DCM_REPLAY_WAVES) void k_replay_fast(int A, i
     double ax[NAC], ay[NAC], arr[NAC], nd[NAC], ctf[NAC], rq[NAC];           // rq: (next preset action - 1) // batch * period (:221)
     int nxt[NAC], cur[NAC], hl[NAC];                                         // hl = route cursor | len(pre_set_route) << 16 (-1 = None)
     uint32_t ai[NAC];
+    int rlen[NAC];                                                           // LOG: len(agent['route']) of the lane's agents
 #pragma unroll
     for (int i = 0; i < NAC; i++) {
+        rlen[i] = 0;
         const int a = i * WAVE + lane, aa = a < A ? a : 0;
         const int len = a < A ? route_len[(size_t)e * A + aa] : -1;          // pre_set_route :595-599
         hl[i] = len << 16;
@@ -363,6 +366,14 @@ __global__ __launch_bounds__(WAVE, DCM_REPLAY_WAVES) void k_replay_fast(int A, i
                 ax[i] = me ? tx_ : ax[i]; ay[i] = me ? ty_ : ay[i];          // :320
                 cur[i] = me ? k : cur[i];                                    // :314
                 ai[i] = me ? ((ai[i] & ~A_MEMBER) | (action == 0 ? A_INDEPOT : 0u) | (joined ? A_MEMBER : 0u)) : ai[i];
+                if constexpr (LOG) {                                         // agent['route'].append :314, ['arrival_time'] += :318
+                    if (me && rlen[i] < LG.route.cap) {
+                        const size_t o = ((size_t)e * A + a) * LG.route.cap + rlen[i];
+                        LG.route.task[o] = (int16_t)k;
+                        LG.route.arrival[o] = arrival_l;
+                    }
+                    rlen[i] += me ? 1 : 0;
+                }
                 if (popped) {                                                // :585 pop(0): the cursor moves on, the next entry is staged
                     const int up = h1_l < len_l ? up_l : 0;
                     hl[i] = me ? hl[i] + 1 : hl[i];
@@ -404,6 +415,35 @@ __global__ __launch_bounds__(WAVE, DCM_REPLAY_WAVES) void k_replay_fast(int A, i
         } else finished_flag = false;
     }
     WSYNC();
+    if constexpr (LOG) {                                                     // the log's lengths, final member lists and feasibility
+#pragma unroll
+        for (int i = 0; i < NAC; i++) {
+            const int a = i * WAVE + lane;
+            if (a < A) LG.route.len[(size_t)e * A + a] = rlen[i];
+        }
+        // A task that is not live (t >= TL) is never joined -- no agent is sent beyond `visible` <= TL -- and its lane, if it has one,
+        // holds an inert requirement-1 task without members that never becomes feasible: no members, not feasible.
+#pragma unroll
+        for (int c = 0; c < NTL; c++) {
+            const int t = c * WAVE + lane;
+            const bool live = t < TL;
+            const int n = live ? (int)((ti[c] >> 16) & 0xFF) : 0;          // <= MR <= CMR <= 8 ids in the word, MR <= member_cols
+            const uint64_t idw = lids[t];
+            if (t < T) {
+                if (LG.members) {
+                    int16_t* row = LG.members + ((size_t)e * T + t) * LG.member_cols;
+                    for (int j = 0; j < LG.member_cols; j++) row[j] = j < n ? (int16_t)((idw >> (8 * (j & 7))) & 0xFFu) : (int16_t)-1;
+                }
+                if (LG.feasible) LG.feasible[(size_t)e * T + t] = (live && (ti[c] & T_FEAS)) ? 1 : 0;
+            }
+        }
+#pragma nounroll
+        for (int t = NTL * WAVE + lane; t < T; t += WAVE) {                  // tasks that never had a lane
+            if (LG.members)
+                for (int j = 0; j < LG.member_cols; j++) LG.members[((size_t)e * T + t) * LG.member_cols + j] = -1;
+            if (LG.feasible) LG.feasible[(size_t)e * T + t] = 0;
+        }
+    }
     // ---- outputs per task and get_episode_reward: calculate_waiting_time :344-364 (np.sum = pairwise block for n >= 8)
     double* const tw = (double*)smem;                                        // f64[T]
     double* const awl = tw + T;                                              // f64[A]

@@ -113,10 +113,7 @@ class TaskEnv:
         self._ag, self._tk = ag, tk
         obs = self._env.observe()
         self._leader_dev = int(obs.leader[0])
-        rt, ra, rl = (x[0].cpu().numpy() for x in self._env.routes())
-        if (rl > self._ROUTE_CAP).any():
-            raise RuntimeError(f"an agent's route has more than {self._ROUTE_CAP} entries (TaskEnv._ROUTE_CAP)")
-        self._routes = [(rt[a, :rl[a]].astype(np.int64).tolist(), ra[a, :rl[a]].tolist()) for a in range(self.agents_num)]
+        self._routes = self._route_lists(*(x[0].cpu().numpy() for x in self._env.routes()))
         mem = self._env.task_members()[0].cpu().numpy()
         self._members = [[int(m) for m in mem[t] if m >= 0] for t in range(self.tasks_num)]
         ab = self._env.abandoned_counts()[0].cpu().numpy()
@@ -127,6 +124,13 @@ class TaskEnv:
             raise RuntimeError("every agent is at the depot while a task can never become feasible: the reference "
                                "loops forever here (SURVEY.md §5); the device env truncated the episode")
         self._dirty = False
+
+    def _route_lists(self, rt, ra, rl):
+        """(route, arrival_time) per agent from one env's log rows (dcm_set_route_log / dcm_set_replay_log layout)."""
+        if (rl > self._ROUTE_CAP).any():
+            raise RuntimeError(f"an agent's route has more than {self._ROUTE_CAP} entries (TaskEnv._ROUTE_CAP)")
+        from .trajectory import route_lists
+        return route_lists(rt, ra, rl)
 
     @property
     def _done(self):
@@ -288,6 +292,7 @@ class TaskEnv:
         (finished, time_start, time_finish, sum_waiting_time, travel_dist, returned) describe the replayed episode, as
         baselines/CTAS-D.py:83-94 reads them.  Raises TypeError where the reference does (:220, pre_set_route None)."""
         self._env.load_routes([self._preset], member_cap=min(32, max(8, self.agents_num)))
+        self._env.enable_replay_log(cap=self._ROUTE_CAP)                     # member_cols = that member_cap
         out = self._env.execute_routes(reactive=bool(self.reactive_planning))
         flags = int(out["flags"][0])
         if flags & _lib.FLAG_TYPE_ERROR:
@@ -302,13 +307,12 @@ class TaskEnv:
         nanA, zerA = np.full(A, np.nan), np.zeros(A)
         self._ag = dict(x=nanA, y=nanA, returned=g("returned"), assigned=zerA, next_decision=nanA, arrival=nanA,
                         travel_dist=g("travel_dist"), sum_waiting_time=g("agent_wait"), current=np.full(A, -1), pending_group=zerA)
-        fin = g("finished")
-        self._tk = dict(feasible=fin.copy(), finished=fin, time_start=g("time_start"), time_finish=g("time_finish"),
+        self._tk = dict(feasible=g("feasible"), finished=g("finished"), time_start=g("time_start"), time_finish=g("time_finish"),
                         status=np.zeros(T, np.int32), sum_waiting_time=g("task_wait"), n_members=g("n_members"),
                         n_abandoned=np.zeros(T, np.int32))
-        # (the replay kernel keeps no visiting history / member lists: these views are empty after execute_by_route)
-        self._routes = [([], []) for _ in range(A)]
-        self._members = [[] for _ in range(T)]
+        # route / arrival_time / members from the replay log (dcm_set_replay_log); abandoned_agent lists are not kept: empty
+        self._routes = self._route_lists(g("route"), g("arrival"), g("route_len"))
+        self._members = [[int(m) for m in row if m >= 0] for row in g("members")]
         self._abandoned = [[] for _ in range(T)]
         self._now = float(sm[3])
         self._flags = flags | _lib.FLAG_DONE

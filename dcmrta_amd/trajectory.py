@@ -6,6 +6,8 @@ route_history       -- per-agent (route, arrival_time) lists of one env, as env/
 write_results_csv   -- RL_test.py:31,45-51 / baselines/CTAS-D.py:56,96: one row of the six perf metrics per instance
 trajectories / generate_traj -- env/task_env.py:375-418: positions (x, y, heading) of every agent sampled every dt, the
                        input of the reference's plot_animation
+replay_trajectories -- the same after a route replay (execute_by_route -> plot_animation, env/task_env.py:589-590), from the
+                       replay log (BatchedTaskEnv.enable_replay_log)
 """
 import csv
 
@@ -15,15 +17,19 @@ import yaml
 METRIC_COLUMNS = ("success_rate", "makespan", "time_cost", "waiting_time", "travel_dist", "efficiency")
 
 
-def route_history(env, b=0):
-    task, arrival, length = (x[b].cpu().numpy() for x in env.routes())
+def route_lists(task, arrival, length, what="enable_route_log(cap)"):
+    """Per agent (route, arrival_time) lists from one env's log rows task[A,cap], arrival[A,cap], length[A] (numpy)."""
     out = []
-    for a in range(env.A):
+    for a in range(len(length)):
         n = int(length[a])
         if n > task.shape[1]:
-            raise ValueError(f"route of agent {a} has {n} entries but the log holds {task.shape[1]}; raise enable_route_log(cap)")
+            raise ValueError(f"route of agent {a} has {n} entries but the log holds {task.shape[1]}; raise {what}")
         out.append(([int(t) for t in task[a, :n]], [float(x) for x in arrival[a, :n]]))
     return out
+
+
+def route_history(env, b=0):
+    return route_lists(*(x[b].cpu().numpy() for x in env.routes()))
 
 
 def routes_to_yaml(env, path, b=0):
@@ -124,3 +130,15 @@ def generate_traj(env, b=0, dt=0.1):
     st = env.status()
     return trajectories(route_history(env, b), d[b].cpu().numpy(), xy[b].cpu().numpy(), members, ts["feasible"].astype(bool),
                         ts["time_start"], ts["time_finish"], float(st["now"][b]), env.max_waiting_time, dt)
+
+
+def replay_trajectories(env, out, b=0, dt=0.1):
+    """generate_traj after execute_by_route (env/task_env.py:589-590 -> :431-439 -> :375-418) for env b of a BatchedTaskEnv:
+    `out` = its execute_routes() result with the replay log on (enable_replay_log).  max_waiting_time is the 100 execute_by_route
+    sets (:564), the horizon the makespan (current_time after the replay)."""
+    g = lambda k: out[k][b].cpu().numpy()
+    routes = route_lists(g("route"), g("arrival"), g("route_len"), "enable_replay_log(cap)")
+    members = [[int(x) for x in row if x >= 0] for row in g("members")]
+    d, xy, _, _ = env._instances
+    return trajectories(routes, d[b].cpu().numpy(), xy[b].cpu().numpy(), members, g("feasible").astype(bool), g("time_start"),
+                        g("time_finish"), float(out["summary"][b, 3]), 100.0, dt)

@@ -182,6 +182,20 @@ int dcm_step(dcm_env *env, const int32_t *actions, const int32_t *leader_in, con
  * (dcm_rollout_random does not log: use the lockstep API when trajectories are wanted.) */
 int dcm_set_route_log(dcm_env *env, int16_t *route_task, double *route_arrival, int32_t *route_len, int32_t cap);
 
+/* Optional history of route replay: what execute_by_route leaves for generate_traj / plot_animation (env/task_env.py:375-418,
+ * 589-590) -- agent['route'] / ['arrival_time'], task['members'] and task['feasible_assignment'].  When set, dcm_execute_routes
+ * restarts the log of every env and each agent_step it runs (forced depot visits of :573-584 included) appends (task id, -1 =
+ * depot; arrival time) to the agent's log: route_task[B,A,cap] i16, route_arrival[B,A,cap] f64, route_len[B,A] i32 (the layout of
+ * dcm_set_route_log; entries beyond cap are counted but not stored; per env the lengths sum to steps_out).  After the episode
+ * member_ids[B,T,member_cols] i16 holds every task's final member list in list order, -1 padded, and feasible[B,T] u8 its
+ * feasible_assignment (at the cut-off t = 200 or on a TRUNCATED env a task can be feasible and not finished).  dcm_execute_routes
+ * fails with DCM_ERR_INVALID, before it launches anything, when member_cols is smaller than the member_cap of dcm_load_routes.
+ * Caller-owned device memory that must outlive its use; all NULL disables; member_ids and feasible may be NULL on their own.
+ * The contents are defined for envs that end FINISHED, at the cut-off or TRUNCATED; for envs flagged TYPE_ERROR, BAD_ACTION or
+ * OVERFLOW they are unspecified.  Independent of dcm_set_route_log, which dcm_step alone writes.  Host-side setter. */
+int dcm_set_replay_log(dcm_env *env, int16_t *route_task, double *route_arrival, int32_t *route_len, int32_t cap,
+                       int16_t *member_ids, int32_t member_cols, uint8_t *feasible);
+
 /* Optional log of EVERY episode's return (reward = -makespan, env/task_env.py:424; what worker.py:87 reads per episode):
  * returns[B,cap] f64, caller-owned device memory that must outlive its use; NULL / 0 disables.  The k-th episode an env
  * finishes since dcm_reset (dcm_rollout_random, dcm_step) writes returns[b, k mod cap] -- a ring, so a caller that plays
