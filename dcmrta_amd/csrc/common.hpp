@@ -10,6 +10,7 @@
 #include <vector>
 
 #include "../../include/dcmrta_env.h"
+#include "plan.hpp"
 
 namespace dcm {
 
@@ -107,6 +108,9 @@ struct Lay {
 static_assert(Lay{20, 50}.rec_bytes() == 5824, "S(20,50) = 64 + 48A + 96T");
 static_assert(Lay{20, 50}.mids() == Lay{20, 50}.tb() + 56 * 50 && Lay{20, 50}.mut_bytes() == align16(Lay{20, 50}.tb() + 72 * 50), "5 member slots: the canonical record");
 constexpr int MW = DCM_MAX_MEMBERS_WIDE;
+// The removal path's dummy slots: LDS that a launch of a register-resident kernel (rollout_fast*.hpp, step_fast.hpp) asks for behind
+// everything the general code uses
+constexpr uint32_t DUMMY_SLOT_BYTES = 512u;
 static_assert(MW <= 16, "member ids: one byte each of up to two 64-bit words");
 
 // Ordered member ids of one task: byte j of the word array = members[j] (the order matters: quirk Q1).  One word for the 5 slots
@@ -427,6 +431,12 @@ inline int make_route_log(const char* fn, int16_t* task, double* arrival, int32_
     do {                                                                                       \
         hipError_t _e = (expr);                                                                \
         if (_e != hipSuccess) return dcm::fail(DCM_ERR_HIP, "%s failed: %s", #expr, hipGetErrorString(_e)); \
+    } while (0)
+// the same for a call that returns a DCM_* code and has recorded its own message
+#define DCM_TRY(call)                     \
+    do {                                  \
+        const int rc_ = (call);           \
+        if (rc_ != DCM_OK) return rc_;    \
     } while (0)
 #define CHECK_HANDLE(env) \
     if (!(env)) return dcm::fail(DCM_ERR_INVALID, "null env handle")

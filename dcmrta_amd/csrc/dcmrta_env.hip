@@ -19,6 +19,7 @@
 //
 // Reference restated: env/task_env.py (TaskEnv) and worker.py:41-112 (the rollout loop).
 // Every device function cites the lines it follows.
+#include <array>
 #include <cstdlib>
 #include <mutex>
 
@@ -55,7 +56,7 @@ struct RolloutArgs {
     unsigned char* gscr; double* retlog; int retcap;
 };
 // k_rollout_fast_g<NAC, NTC, OBS> (rollout_fast_g.hpp, its own translation unit)
-void launch_rollout_fast_g(int nac, int ntc, bool obs, unsigned grid, unsigned lds_bytes, hipStream_t stream, const RolloutArgs& a);
+void launch_rollout_fast_g(int nac, int ntc, bool obs, unsigned grid, Lay L, hipStream_t stream, const RolloutArgs& a);
 }  // namespace dcm
 
 namespace {
@@ -1364,6 +1365,10 @@ __global__ __launch_bounds__(WAVE) void k_load_instances(int A, int T, int PA, i
     }
 }
 
+// dynamic LDS of a k_reset / k_observe / k_step launch: the record image (MC moves no section of it)
+template <int CA, int CT, bool RS>
+constexpr uint32_t env_kernel_lds_bytes(Lay L) { return Sim<CA, CT, RS>::lds_image_bytes(L); }
+
 template <int CA, int CT, bool RS, int MC = M>
 __global__ __launch_bounds__(WAVE) void k_reset(int A, int T, int PA, int PT, KP P, unsigned char* state, const uint64_t* seeds,
                                                double* summary, uint16_t* ablog, uint32_t mode, const int32_t* sizes,
@@ -1595,6 +1600,13 @@ __device__ __forceinline__ int rollout_budget(int e, int64_t budget_all, const i
     return uni((int)((bud < 0 || bud >= NO_BUDGET) ? NO_BUDGET : bud));
 }
 
+// dynamic LDS of a k_rollout_random launch: the record image, or record + scratch for the layouts that keep the scratch in LDS
+template <int CA, int CT, bool RS>
+constexpr uint32_t rollout_random_lds_bytes(Lay L) {
+    using SimT = Sim<CA, CT, RS, (CT > WAVE) && !RS>;
+    return SimT::SCR_IN_LDS ? L.lds_bytes() : SimT::lds_image_bytes(L);
+}
+
 // Config-2 hot path: whole episodes in one persistent launch, record resident in LDS.  Budget: see rollout_budget.
 // __launch_bounds__(64, 3): at least three waves per SIMD.  The one-chunk shapes need 111 VGPRs anyway (four waves per SIMD); the
 // 50A/200T instantiation wants 176 -- two waves per SIMD although its LDS image (10.9 KB with the member arrival times left in
@@ -1819,45 +1831,23 @@ __global__ void k_distance(const double* ax, const double* ay, const double* bx,
 }
 
 // ---------------------------------------------------------------------------------- host side
-// Instantiations: the three BASELINE shapes exactly; <20,50,runtime sizes> for every other shape (uniform or ragged) inside
-// the reference's training range A <= 20, T <= 50 (parameters.py:15-16); <64,64,runtime sizes> for the remaining one-chunk
-// shapes (A <= 64, T <= 64: one lane per agent / task); <128,256,runtime sizes and layout> for the mid sizes (generate_env
-// takes any size, env/task_env.py:57-65); <0,0> for the rest.
-#define FOR_EACH_INSTANCE(X) X(20, 50, false); X(20, 50, true); X(64, 64, true); X(50, 200, false); X(100, 500, false); X(128, 256, true); X(0, 0, false)
-// one-chunk layouts: the register-resident persistent kernel (rollout_fast.hpp)
-#define FOR_EACH_FAST(X) X(20, 50, false); X(20, 50, true); X(64, 64, true)
-#define DISPATCH_ENV(env, CALL)                                                                        \
-    do {                                                                                               \
-        const dcm_env* e_ = (env);                                                                     \
-        const bool exact_ = !e_->sizes && e_->A == e_->L.A && e_->T == e_->L.T;                        \
-        if (e_->L.C > M) { CALL(0, 0, false, MW); }   /* DCM_PARAM_WIDE_MEMBERS: sixteen member slots (two id words), runtime-size code */ \
-        else if (e_->L.A == 20 && e_->L.T == 50) { if (exact_) { CALL(20, 50, false); } else { CALL(20, 50, true); } } \
-        else if (e_->L.A == 64 && e_->L.T == 64) { CALL(64, 64, true); }                               \
-        else if (exact_ && e_->A == 50 && e_->T == 200) { CALL(50, 200, false); }                      \
-        else if (exact_ && e_->A == 100 && e_->T == 500) { CALL(100, 500, false); }                    \
-        else if (e_->A <= 128 && e_->T <= 256) { CALL(128, 256, true); }   /* mid sizes: bounded trip counts, own layout */ \
-        else { CALL(0, 0, false); }                                                                    \
-    } while (0)
+// Which Sim<> instantiation and which kernels serve a handle is decided in plan.hpp; here its answers become template arguments.
+// The instantiations by their plan::SimKind: first the one-chunk layouts, which also have the register-resident kernels of
+// rollout_fast.hpp / step_fast.hpp, then the rest
+#define FOR_EACH_FAST(X) X(S20x50, 20, 50, false) X(S20x50_RS, 20, 50, true) X(S64x64_RS, 64, 64, true)
+#define FOR_EACH_INSTANCE(X) FOR_EACH_FAST(X) X(S50x200, 50, 200, false) X(S100x500, 100, 500, false) X(S128x256_RS, 128, 256, true) \
+    X(Runtime, 0, 0, false) X(RuntimeWide, 0, 0, false, MW)
+// DISPATCH_ENV(env): the caller's macro CALL(CA, CT, RS[, MC]) for the handle's instantiation; DISPATCH_ONE_CHUNK(env): the same for
+// the kernels that exist for the one-chunk layouts only (their callers have asked plan::one_chunk_ok)
+#define SIM_CASE(KIND, ...) case plan::SimKind::KIND: CALL(__VA_ARGS__); break;
+#define DISPATCH_ENV(env) switch (plan::sim_kind(shape_of(env))) { FOR_EACH_INSTANCE(SIM_CASE) }
+#define DISPATCH_ONE_CHUNK(env) \
+    switch (plan::sim_kind(shape_of(env))) { FOR_EACH_FAST(SIM_CASE) default: return fail(DCM_ERR_STATE, "internal error: a one-chunk kernel on another layout"); }
 // kernel arguments every env kernel starts with: batch dims, layout dims
 #define DIMS(env) (env)->A, (env)->T, (env)->L.A, (env)->L.T
-// the one-chunk register-resident kernels (step_fast.hpp, rollout_fast.hpp): <20,50> exactly or with runtime sizes, every other
-// one-chunk layout in <64,64,runtime sizes>
-#define DISPATCH_ONE_CHUNK(env, CALL)                                                                  \
-    do {                                                                                               \
-        const dcm_env* e_ = (env);                                                                     \
-        const bool exact_ = !e_->sizes && e_->A == e_->L.A && e_->T == e_->L.T;                        \
-        if (e_->L.A == 20 && e_->L.T == 50) { if (exact_) { CALL(20, 50, false); } else { CALL(20, 50, true); } } \
-        else { CALL(64, 64, true); }                                                                   \
-    } while (0)
 
-// The register-resident kernels skip the task_update pass of a QUIET join on the ground that a member who has just joined
-// has not waited max_waiting_time yet (env/task_env.py:269), which needs max_waiting_time > 0 (the reference's 10 / 100):
-// a handle with max_waiting_time <= 0 (or NaN) takes the general kernels, which evaluate the rule literally.
-bool quiet_ok(const dcm_env* env) { return env->kp.mwt > 0.0; }
-// ... and the one-chunk ones need one lane per agent and per task, with lane 63 free for the depot
-bool one_chunk_ok(const dcm_env* env) {
-    return quiet_ok(env) && env->L.C == M && env->L.A <= 64 && env->L.T <= 64 && env->T <= 63;
-}
+// what plan.hpp reads of a handle
+plan::Shape shape_of(const dcm_env* env) { return {env->A, env->T, env->sizes != nullptr, env->L.C > M, env->kp.mwt > 0.0}; }
 
 // dcm_create / dcm_destroy run on the handle's device but leave the caller's current device as they found it
 struct DeviceGuard {
@@ -1866,9 +1856,6 @@ struct DeviceGuard {
     ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
 };
 
-}  // namespace
-
-namespace {
 template <class K>
 void launch_rollout(K kernel, dim3 grid, dim3 block, unsigned lds_bytes, hipStream_t stream, const RolloutArgs& a) {
     hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, a.A, a.T, a.PA, a.PT, a.kp, a.state, a.episodes, a.agents_out, a.tasks_out,
@@ -1877,8 +1864,8 @@ void launch_rollout(K kernel, dim3 grid, dim3 block, unsigned lds_bytes, hipStre
 }  // namespace
 
 #if defined(DCM_TU_G) || !defined(DCM_SPLIT_G)
-void dcm::launch_rollout_fast_g(int nac, int ntc, bool obs, unsigned grid, unsigned lds_bytes, hipStream_t stream, const RolloutArgs& a) {
-#define CALLG(NAC, NTC, OBS) launch_rollout(k_rollout_fast_g<NAC, NTC, OBS>, dim3(grid), dim3(WAVE), lds_bytes, stream, a)
+void dcm::launch_rollout_fast_g(int nac, int ntc, bool obs, unsigned grid, Lay L, hipStream_t stream, const RolloutArgs& a) {
+#define CALLG(NAC, NTC, OBS) launch_rollout(k_rollout_fast_g<NAC, NTC, OBS>, dim3(grid), dim3(WAVE), rollout_fast_g_lds_bytes(L), stream, a)
 #define CALLT(NAC, OBS) do { if (ntc > 3) { CALLG(NAC, 4, OBS); } else if (ntc > 2) { CALLG(NAC, 3, OBS); } else { CALLG(NAC, 2, OBS); } } while (0)
 #define CALLA(OBS) do { if (nac > 1) { CALLT(2, OBS); } else { CALLT(1, OBS); } } while (0)
     if (obs) { CALLA(true); } else { CALLA(false); }
@@ -1889,6 +1876,54 @@ void dcm::launch_rollout_fast_g(int nac, int ntc, bool obs, unsigned grid, unsig
 #endif
 
 #ifndef DCM_DEVICE_ONLY_TU   // (tools/loop_insts.py compiles single kernel instantiations of this file without the host API)
+namespace {
+constexpr uint32_t CU_LDS_BYTES = 160u * 1024u;
+
+// The most dynamic LDS any kernel of this file asks for on a layout: the general image with the wake-up times of the multi-chunk
+// layouts, or record + scratch where the persistent kernels keep the scratch in LDS (Sim::SCR_IN_LDS); then the dummy slots
+int largest_lds_request(Lay L) {
+    uint32_t lds = Sim<0, 0, false>::lds_image_bytes(L);
+    if (L.lds_bytes() <= 10240) lds = L.lds_bytes();
+    if (lds + DUMMY_SLOT_BYTES <= CU_LDS_BYTES) lds += DUMMY_SLOT_BYTES;
+    return (int)lds;
+}
+template <class K>
+void allow_lds(K kernel, int bytes) { (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes); }
+
+// ADVICE.md item 2 is to be fixed here: an error from hipStreamIsCapturing counts as "capturing"
+bool stream_capturing(void* stream) {
+    hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
+    return hipStreamIsCapturing((hipStream_t)stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
+}
+
+// the common tail of dcm_load_instances / dcm_load_instances_ragged (env->sizes: the per-env sizes of a ragged batch, or nullptr)
+int launch_load(dcm_env* env, const double* depot, const double* task_xy, const int32_t* req, const double* dur, void* stream) {
+    hipLaunchKernelGGL(k_load_instances, GRID(env), 0, (hipStream_t)stream, DIMS(env), env->L.C, env->state, depot, task_xy,
+                       req, dur, (const int32_t*)env->sizes);
+    LAUNCH_OK();
+    env->loaded = true;
+    env->reset_done = false;
+    return DCM_OK;
+}
+
+// dcm_env_status / dcm_env_episodes: header fields of every env (layout dims: only the record pitch matters)
+int launch_env_status(dcm_env* env, uint32_t* flags_out, int64_t* decisions_out, double* now_out, int32_t* episodes_out, void* stream) {
+    const int B = env->p.n_envs;
+    hipLaunchKernelGGL(k_env_status, dim3((B + WAVE - 1) / WAVE), dim3(WAVE), 0, (hipStream_t)stream, env->L.A, env->L.T, env->L.C,
+                       env->state, B, flags_out, decisions_out, now_out, episodes_out);
+    LAUNCH_OK();
+    return DCM_OK;
+}
+
+// the blob of dcm_state_bytes / dcm_clone_state / dcm_restore_state: these sections of the handle, in this order
+struct Section { void* ptr; size_t bytes; };
+std::array<Section, 3> state_sections(const dcm_env* env) {
+    const size_t B = (size_t)env->p.n_envs;
+    return {{{env->state, B * env->L.rec_bytes()}, {env->summary, B * 8 * sizeof(double)},
+             {env->ablog, side_bytes(env->p.n_envs, env->A, env->T)}}};
+}
+}  // namespace
+
 extern "C" {
 
 const char* dcm_last_error(void) { return dcm::g_err; }
@@ -1923,29 +1958,22 @@ int dcm_create(const dcm_params* params, dcm_env** out) {
     if (!h) return fail(DCM_ERR_INVALID, "dcm_create: out of host memory");
     h->p = *params;
     h->A = params->n_agents; h->T = params->n_tasks;
-    h->L = (params->flags & DCM_PARAM_WIDE_MEMBERS) ? Lay{h->A, h->T, MW}
-           : (h->A <= 20 && h->T <= 50) ? Lay{20, 50} : (h->A <= 64 && h->T <= 64) ? Lay{64, 64} : Lay{h->A, h->T};
+    const plan::LayDims ld = plan::layout_dims(h->A, h->T, (params->flags & DCM_PARAM_WIDE_MEMBERS) != 0);
+    h->L = Lay{ld.A, ld.T, ld.C};
     h->kp.mwt = params->max_waiting_time;
     h->kp.max_time = params->max_time;
-    if (h->L.lds_rec() + align16(4u * (uint32_t)h->L.T) > 160 * 1024) { delete h; return fail(DCM_ERR_INVALID, "dcm_create: env record does not fit the 160 KiB LDS"); }
-    const size_t bytes = (size_t)params->n_envs * h->L.rec_bytes();
-    hipError_t e1 = hipMalloc((void**)&h->state, bytes);
-    hipError_t e2 = hipMalloc((void**)&h->summary, (size_t)params->n_envs * 8 * sizeof(double));
-    if (e1 == hipSuccess && e2 == hipSuccess)
-        e2 = hipMalloc((void**)&h->ablog, side_bytes(params->n_envs, params->n_agents, params->n_tasks));
-    if (e1 == hipSuccess && e2 == hipSuccess)
-        e2 = hipMalloc((void**)&h->gscratch, (size_t)params->n_envs * h->L.scratch_bytes());
-    if (e1 != hipSuccess || e2 != hipSuccess) {
-        if (h->state) (void)hipFree(h->state);
-        if (h->summary) (void)hipFree(h->summary);
-        if (h->ablog) (void)hipFree(h->ablog);
-        if (h->gscratch) (void)hipFree(h->gscratch);
-        delete h;
-        return fail(DCM_ERR_HIP, "dcm_create: hipMalloc failed: %s", hipGetErrorString(e1 != hipSuccess ? e1 : e2));
-    }
-    hipError_t e3 = hipMemset(h->state, 0, bytes);
-    if (e3 == hipSuccess) e3 = hipMemset(h->ablog, 0, side_bytes(params->n_envs, params->n_agents, params->n_tasks));
-    if (e3 != hipSuccess) { (void)hipFree(h->state); (void)hipFree(h->summary); (void)hipFree(h->ablog); (void)hipFree(h->gscratch); delete h; return fail(DCM_ERR_HIP, "hipMemset: %s", hipGetErrorString(e3)); }
+    // (from here on dcm_destroy frees whatever the partly built handle holds)
+    if (Sim<0, 0, false>::lds_image_bytes(h->L) > CU_LDS_BYTES) { dcm_destroy(h); return fail(DCM_ERR_INVALID, "dcm_create: env record does not fit the 160 KiB LDS"); }
+    const size_t B = (size_t)params->n_envs, bytes = B * h->L.rec_bytes(), side = side_bytes(params->n_envs, h->A, h->T);
+    hipError_t e = hipMalloc((void**)&h->state, bytes);
+    if (e == hipSuccess) e = hipMalloc((void**)&h->summary, B * 8 * sizeof(double));
+    if (e == hipSuccess) e = hipMalloc((void**)&h->ablog, side);
+    if (e == hipSuccess) e = hipMalloc((void**)&h->gscratch, B * h->L.scratch_bytes());
+    if (e != hipSuccess) { dcm_destroy(h); return fail(DCM_ERR_HIP, "dcm_create: hipMalloc failed: %s", hipGetErrorString(e)); }
+    e = hipMemset(h->state, 0, bytes);
+    if (e == hipSuccess) e = hipMemset(h->ablog, 0, side);
+    if (e != hipSuccess) { dcm_destroy(h); return fail(DCM_ERR_HIP, "hipMemset: %s", hipGetErrorString(e)); }
+    *out = h;
     // kernels that keep the record in LDS may need more than the default 64 KiB of dynamic LDS.  The limit is a
     // per-function, per-device attribute shared by every handle of the process, so it only ever grows: a later, smaller
     // env must not lower it under an earlier handle's launches.
@@ -1953,80 +1981,59 @@ int dcm_create(const dcm_params* params, dcm_env** out) {
     static std::mutex lds_mutex;                 // handles are created from several host threads (one actor thread per GPU)
     std::lock_guard<std::mutex> lds_guard(lds_mutex);
     const int dev_slot = params->device & 63;
-    int lds = (int)(h->L.lds_rec() + align16(4u * (uint32_t)h->L.T));   // (+ the wake-up times of the multi-chunk layouts)
-    if (h->L.lds_bytes() <= 10240) lds = (int)h->L.lds_bytes();           // persistent kernel of the small layouts: scratch in LDS
-    if (lds + 512 <= 160 * 1024) lds += 512;                               // the register-resident kernels' dummy slots (small layouts)
+    const int lds = largest_lds_request(h->L);
     // (only when the limit really grows: the attribute calls of one host thread must not keep landing in another thread's
     //  stream capture -- actors create handles for new batch shapes while others capture)
-    const bool grow = lds > lds_limit[dev_slot];
-    if (!grow) { *out = h; return DCM_OK; }
+    if (lds <= lds_limit[dev_slot]) return DCM_OK;
     lds_limit[dev_slot] = lds;
-#define SET_ATTR(CA, CT, RS)                                                                                             \
-    (void)hipFuncSetAttribute((const void*)k_reset<CA, CT, RS>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);        \
-    (void)hipFuncSetAttribute((const void*)k_observe<CA, CT, RS>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);      \
-    (void)hipFuncSetAttribute((const void*)k_step<CA, CT, RS>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);         \
-    (void)hipFuncSetAttribute((const void*)k_rollout_random<CA, CT, RS>, hipFuncAttributeMaxDynamicSharedMemorySize, lds)
-    FOR_EACH_INSTANCE(SET_ATTR);
+#define SET_ATTR(KIND, CA, CT, RS, ...)                        \
+    allow_lds(k_reset<CA, CT, RS, ##__VA_ARGS__>, lds);        \
+    allow_lds(k_observe<CA, CT, RS, ##__VA_ARGS__>, lds);      \
+    allow_lds(k_step<CA, CT, RS, ##__VA_ARGS__>, lds);         \
+    allow_lds(k_rollout_random<CA, CT, RS, ##__VA_ARGS__>, lds);
+    FOR_EACH_INSTANCE(SET_ATTR)
 #undef SET_ATTR
-    (void)hipFuncSetAttribute((const void*)k_reset<0, 0, false, MW>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute((const void*)k_observe<0, 0, false, MW>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute((const void*)k_step<0, 0, false, MW>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute((const void*)k_rollout_random<0, 0, false, MW>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-#define SET_FAST(CA, CT, RS)                                                                                              \
-    (void)hipFuncSetAttribute((const void*)k_rollout_fast<CA, CT, RS, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);  \
-    (void)hipFuncSetAttribute((const void*)k_rollout_fast<CA, CT, RS, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); \
-    (void)hipFuncSetAttribute((const void*)k_rollout_fast<CA, CT, RS, true, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);  \
-    (void)hipFuncSetAttribute((const void*)k_rollout_fast<CA, CT, RS, false, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds); \
-    (void)hipFuncSetAttribute((const void*)k_step_fast<CA, CT, RS>, hipFuncAttributeMaxDynamicSharedMemorySize, lds)
-    FOR_EACH_FAST(SET_FAST);
+#define SET_FAST(KIND, CA, CT, RS)                             \
+    allow_lds(k_rollout_fast<CA, CT, RS, true>, lds);          \
+    allow_lds(k_rollout_fast<CA, CT, RS, false>, lds);         \
+    allow_lds(k_rollout_fast<CA, CT, RS, true, true>, lds);    \
+    allow_lds(k_rollout_fast<CA, CT, RS, false, true>, lds);   \
+    allow_lds(k_step_fast<CA, CT, RS>, lds);
+    FOR_EACH_FAST(SET_FAST)
 #undef SET_FAST
-    (void)hipFuncSetAttribute((const void*)k_rollout_fast_mc<50, 200, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute((const void*)k_rollout_fast_mc<50, 200, false>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute((const void*)k_get_tasks<M>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute((const void*)k_get_agents<M>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute((const void*)k_get_tasks<MW>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    (void)hipFuncSetAttribute((const void*)k_get_agents<MW>, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
-    *out = h;
+    allow_lds(k_rollout_fast_mc<50, 200, true>, lds);
+    allow_lds(k_rollout_fast_mc<50, 200, false>, lds);
+    allow_lds(k_get_tasks<M>, lds);
+    allow_lds(k_get_agents<M>, lds);
+    allow_lds(k_get_tasks<MW>, lds);
+    allow_lds(k_get_agents<MW>, lds);
     return DCM_OK;
 }
 
 int dcm_destroy(dcm_env* env) {
     if (!env) return DCM_OK;
     DeviceGuard guard(env->p.device);
-    if (env->state) (void)hipFree(env->state);
-    if (env->summary) (void)hipFree(env->summary);
-    if (env->ablog) (void)hipFree(env->ablog);
-    if (env->gscratch) (void)hipFree(env->gscratch);
-    if (env->routes) (void)hipFree(env->routes);
-    if (env->route_len) (void)hipFree(env->route_len);
-    if (env->rmarr) (void)hipFree(env->rmarr);
-    if (env->sizes) (void)hipFree(env->sizes);
-    if (env->side) (void)hipFree(env->side);
-    if (env->pendq) (void)hipFree(env->pendq);
-    if (env->init) (void)hipFree(env->init);
+    void* const owned[] = {env->state, env->summary, env->ablog, env->gscratch, env->routes, env->route_len,
+                           env->rmarr, env->sizes, env->side, env->pendq, env->init};
+    for (void* p : owned)
+        if (p) (void)hipFree(p);
     delete env;
     return DCM_OK;
 }
-
 
 int dcm_load_instances(dcm_env* env, const double* depot, const double* task_xy, const int32_t* req, const double* dur,
                        void* stream) {
     CHECK_ENV(env);
     if (!depot || !task_xy || !req || !dur) return fail(DCM_ERR_INVALID, "dcm_load_instances: null array");
-    { const int rc_ = dcm::drop_pending(env, stream); if (rc_ != DCM_OK) return rc_; }
+    DCM_TRY(dcm::drop_pending(env, stream));
     if (env->sizes) { HIP_TRY(hipFree(env->sizes)); env->sizes = nullptr; }   // back to a uniform batch (hipFree synchronises)
-    hipLaunchKernelGGL(k_load_instances, GRID(env), 0, (hipStream_t)stream, DIMS(env), env->L.C, env->state, depot, task_xy,
-                       req, dur, (const int32_t*)nullptr);
-    LAUNCH_OK();
-    env->loaded = true;
-    env->reset_done = false;
-    return DCM_OK;
+    return launch_load(env, depot, task_xy, req, dur, stream);
 }
 
 int dcm_load_instances_ragged(dcm_env* env, const double* depot, const double* task_xy, const int32_t* req,
                               const double* dur, const int32_t* n_agents_host, const int32_t* n_tasks_host, void* stream) {
     CHECK_ENV(env);
-    { const int rc_ = dcm::drop_pending(env, stream); if (rc_ != DCM_OK) return rc_; }
+    DCM_TRY(dcm::drop_pending(env, stream));
     if (!depot || !task_xy || !req || !dur || !n_agents_host || !n_tasks_host)
         return fail(DCM_ERR_INVALID, "dcm_load_instances_ragged: null array");
     const int B = env->p.n_envs;
@@ -2040,12 +2047,7 @@ int dcm_load_instances_ragged(dcm_env* env, const double* depot, const double* t
     if (!env->sizes) HIP_TRY(hipMalloc((void**)&env->sizes, (size_t)2 * B * sizeof(int32_t)));
     HIP_TRY(hipMemcpyAsync(env->sizes, env->sizes_host.data(), (size_t)2 * B * sizeof(int32_t), hipMemcpyHostToDevice,
                            (hipStream_t)stream));
-    hipLaunchKernelGGL(k_load_instances, GRID(env), 0, (hipStream_t)stream, DIMS(env), env->L.C, env->state, depot, task_xy,
-                       req, dur, (const int32_t*)env->sizes);
-    LAUNCH_OK();
-    env->loaded = true;
-    env->reset_done = false;
-    return DCM_OK;
+    return launch_load(env, depot, task_xy, req, dur, stream);
 }
 
 }  // extern "C"
@@ -2054,11 +2056,10 @@ namespace dcm {
 int flush_pending(dcm_env* env, void* stream) {
     if (!env->maybe_pending) return DCM_OK;
 #define CALL(CA, CT, RS)                                                                                             \
-    hipLaunchKernelGGL((k_terminal_flush<CA, CT, RS>), GRID(env),                                    \
-                       (Sim<CA, CT, RS>::lds_image_bytes(env->L)) + 512u + (step_scratch_in_lds<CA, CT>() ? env->L.scratch_bytes() : 0u), \
+    hipLaunchKernelGGL((k_terminal_flush<CA, CT, RS>), GRID(env), (step_fast_lds_bytes<CA, CT, RS>(env->L)),          \
                        (hipStream_t)stream, DIMS(env), env->kp, (const unsigned char*)env->side, env->side_pitch, env->pendq,       \
                        env->summary, (const int32_t*)env->sizes, env->gscratch)
-    DISPATCH_ONE_CHUNK(env, CALL);
+    DISPATCH_ONE_CHUNK(env);
 #undef CALL
     LAUNCH_OK();
     env->maybe_pending = false;
@@ -2078,31 +2079,30 @@ extern "C" {
 
 int dcm_reset(dcm_env* env, const uint64_t* seeds, void* stream) {
     CHECK_ENV(env);
-    { const int rc_ = dcm::drop_pending(env, stream); if (rc_ != DCM_OK) return rc_; }
+    DCM_TRY(dcm::drop_pending(env, stream));
     if (!env->loaded) return fail(DCM_ERR_STATE, "dcm_reset: call dcm_load_instances first");
     if (!seeds) return fail(DCM_ERR_INVALID, "dcm_reset: null seeds");
 #define CALL(CA, CT, RS, ...)                                                                                         \
-    hipLaunchKernelGGL((k_reset<CA, CT, RS, ##__VA_ARGS__>), GRID(env), (Sim<CA, CT, RS>::lds_image_bytes(env->L)), (hipStream_t)stream, DIMS(env), env->kp, \
+    hipLaunchKernelGGL((k_reset<CA, CT, RS, ##__VA_ARGS__>), GRID(env), (env_kernel_lds_bytes<CA, CT, RS>(env->L)), (hipStream_t)stream, DIMS(env), env->kp, \
                        env->state, seeds, env->summary, env->ablog, env->p.flags, (const int32_t*)env->sizes, env->gscratch)
-    DISPATCH_ENV(env, CALL);
+    DISPATCH_ENV(env);
 #undef CALL
     LAUNCH_OK();
     if (env->log.len)
         HIP_TRY(hipMemsetAsync(env->log.len, 0, (size_t)env->p.n_envs * env->A * sizeof(int32_t), (hipStream_t)stream));
     env->reset_done = true;
-    // the restart image of the register-resident lockstep kernel (dcm_env::init): what this reset produced
+    // the restart image of the register-resident lockstep kernel (dcm_env::init, read by k_step_fast only): what this reset produced
     env->init_valid = false;
     // (max_time <= 0: the first event already ends the episode -- summary row, episode count, return log -- which a copied image cannot redo)
-    if ((env->p.flags & DCM_PARAM_AUTO_RESET) && env->L.C == M && env->L.A <= 64 && env->L.T <= 64 && !env->init_failed && env->kp.max_time > 0.0) {
-        hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-        const bool capturing = hipStreamIsCapturing((hipStream_t)stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
+    if ((env->p.flags & DCM_PARAM_AUTO_RESET) && plan::one_chunk_ok(shape_of(env)) && !env->init_failed && env->kp.max_time > 0.0 &&
+        !stream_capturing(stream)) {
         const size_t sb = (size_t)env->p.n_envs * env->L.rec_bytes();
-        if (!env->init && !capturing && hipMalloc((void**)&env->init, sb) != hipSuccess) {
+        if (!env->init && hipMalloc((void**)&env->init, sb) != hipSuccess) {
             (void)hipGetLastError();                                         // out of memory: the kernel restarts the long way
             env->init = nullptr;
             env->init_failed = true;
         }
-        if (env->init && !capturing) {
+        if (env->init) {
             HIP_TRY(hipMemcpyAsync(env->init, env->state, sb, hipMemcpyDeviceToDevice, (hipStream_t)stream));
             env->init_valid = true;
         }
@@ -2128,10 +2128,10 @@ int dcm_observe(dcm_env* env, float* agents_out, float* tasks_out, uint8_t* mask
     CHECK_ENV(env);
     if (!env->reset_done) return fail(DCM_ERR_STATE, "dcm_observe: call dcm_reset first");
 #define CALL(CA, CT, RS, ...)                                                                                           \
-    hipLaunchKernelGGL((k_observe<CA, CT, RS, ##__VA_ARGS__>), GRID(env), (Sim<CA, CT, RS>::lds_image_bytes(env->L)), (hipStream_t)stream, DIMS(env),            \
+    hipLaunchKernelGGL((k_observe<CA, CT, RS, ##__VA_ARGS__>), GRID(env), (env_kernel_lds_bytes<CA, CT, RS>(env->L)), (hipStream_t)stream, DIMS(env),            \
                        env->state, agents_out, tasks_out, mask_out, leader_out, active_out, leader_in,                  \
                        (const int32_t*)env->sizes, env->p.flags)
-    DISPATCH_ENV(env, CALL);
+    DISPATCH_ENV(env);
 #undef CALL
     LAUNCH_OK();
     return DCM_OK;
@@ -2145,17 +2145,14 @@ int dcm_step(dcm_env* env, const int32_t* actions, const int32_t* leader_in, con
     if (!actions) return fail(DCM_ERR_INVALID, "dcm_step: null actions");
     if ((nfol_in == nullptr) != (followers_in == nullptr))
         return fail(DCM_ERR_INVALID, "dcm_step: nfol_in and followers_in must be given together");
-#ifndef DCM_NO_FAST_STEP
     // The plain call shape on a one-chunk layout: the register-resident step (step_fast.hpp); same contract, same results.
-    if (one_chunk_ok(env) && !leader_in && !nfol_in && !env->log.len && agents_out && tasks_out &&
+    if (plan::one_chunk_ok(shape_of(env)) && !leader_in && !nfol_in && !env->log.len && agents_out && tasks_out &&
         mask_out && leader_out && active_out && !(env->p.flags & DCM_PARAM_NO_GROUPING)) {
         // Deferred terminal metrics (dcm_env::side) for auto-resetting handles: not under stream capture -- the periodic flush is a
         // host-side decision and the buffers are allocated on first use -- where episode ends keep computing their metrics inline.
         uint32_t* pendq = nullptr;
         if (env->p.flags & DCM_PARAM_AUTO_RESET) {
-            hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
-            const bool capturing = hipStreamIsCapturing((hipStream_t)stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
-            if (capturing) {
+            if (stream_capturing(stream)) {
                 if (env->maybe_pending)
                     return fail(DCM_ERR_STATE, "dcm_step under stream capture: deferred episode summaries are waiting; call dcm_summary (or dcm_reset) before the capture");
                 env->captured = true;      // a replay of this graph writes summary rows unseen by the host: no snapshots on this handle any more
@@ -2176,13 +2173,12 @@ int dcm_step(dcm_env* env, const int32_t* actions, const int32_t* leader_in, con
             }
         }
 #define CALL(CA, CT, RS)                                                                                             \
-    hipLaunchKernelGGL((k_step_fast<CA, CT, RS>), GRID(env),                                                           \
-                       (Sim<CA, CT, RS>::lds_image_bytes(env->L)) + 512u + (step_scratch_in_lds<CA, CT>() ? env->L.scratch_bytes() : 0u), \
+    hipLaunchKernelGGL((k_step_fast<CA, CT, RS>), GRID(env), (step_fast_lds_bytes<CA, CT, RS>(env->L)),                \
                        (hipStream_t)stream, DIMS(env), env->kp,                                                            \
                        env->state, actions, agents_out, tasks_out, mask_out, leader_out, active_out, env->summary, env->ablog,  \
                        env->p.flags, (const int32_t*)env->sizes, env->gscratch, env->p.auto_reset_episodes, env->retlog, (int)env->retcap, \
                        env->side, env->side_pitch, pendq, (pendq && env->init_valid) ? (const unsigned char*)env->init : nullptr)
-        DISPATCH_ONE_CHUNK(env, CALL);
+        DISPATCH_ONE_CHUNK(env);
 #undef CALL
         LAUNCH_OK();
         if (pendq) {
@@ -2191,14 +2187,13 @@ int dcm_step(dcm_env* env, const int32_t* actions, const int32_t* leader_in, con
         }
         return DCM_OK;
     }
-#endif
-    { const int rc_ = dcm::flush_pending(env, stream); if (rc_ != DCM_OK) return rc_; }    // (the general kernel writes summary rows itself)
+    DCM_TRY(dcm::flush_pending(env, stream));    // (the general kernel writes summary rows itself)
 #define CALL(CA, CT, RS, ...)                                                                                        \
-    hipLaunchKernelGGL((k_step<CA, CT, RS, ##__VA_ARGS__>), GRID(env), (Sim<CA, CT, RS>::lds_image_bytes(env->L)), (hipStream_t)stream, DIMS(env), env->kp,   \
+    hipLaunchKernelGGL((k_step<CA, CT, RS, ##__VA_ARGS__>), GRID(env), (env_kernel_lds_bytes<CA, CT, RS>(env->L)), (hipStream_t)stream, DIMS(env), env->kp,   \
                        env->state, actions, leader_in, nfol_in, followers_in, agents_out, tasks_out, mask_out, leader_out, \
                        active_out, env->summary, env->log, env->ablog, env->p.flags, (const int32_t*)env->sizes, env->gscratch, \
                        env->p.auto_reset_episodes, env->retlog, (int)env->retcap)
-    DISPATCH_ENV(env, CALL);
+    DISPATCH_ENV(env);
 #undef CALL
     LAUNCH_OK();
     return DCM_OK;
@@ -2209,49 +2204,40 @@ int dcm_rollout_random(dcm_env* env, int32_t episodes, int64_t max_decisions, co
     CHECK_ENV(env);
     if (!env->reset_done) return fail(DCM_ERR_STATE, "dcm_rollout_random: call dcm_reset first");
     if (episodes < 1) return fail(DCM_ERR_INVALID, "dcm_rollout_random: episodes must be >= 1");
-    { const int rc_ = dcm::flush_pending(env, stream); if (rc_ != DCM_OK) return rc_; }
+    DCM_TRY(dcm::flush_pending(env, stream));
     const dcm::RolloutArgs ra{DIMS(env), env->kp, env->state, (int)episodes, agents_out, tasks_out, mask_out, steps_out, env->summary,
                               env->ablog, (const int32_t*)env->sizes, max_decisions, max_decisions_in, env->gscratch, env->retlog,
                               (int)env->retcap};
-#ifndef DCM_NO_FAST_ROLLOUT
-    // One-chunk layouts with all three observation buffers or none: the register-resident kernel.  Same contract, same results
-    // (tests/test_gpu_rollout.py runs both).
+    // The register-resident kernels have the same contract and the same results as the general one (tests/test_gpu_rollout.py runs both)
     const bool all_obs = agents_out && tasks_out && mask_out, no_obs = !agents_out && !tasks_out && !mask_out;
-    if (one_chunk_ok(env) && (all_obs || no_obs)) {
-#define CALLF(CA, CT, RS, OBS, PRIO)                                                                                  \
-    launch_rollout(k_rollout_fast<CA, CT, RS, OBS, PRIO>, GRID(env),                                                  \
-                   (Sim<CA, CT, RS>::SCR_IN_LDS ? env->L.lds_bytes() : Sim<CA, CT, RS>::lds_image_bytes(env->L)) + 512u, (hipStream_t)stream, ra)
+    switch (plan::rollout_kind(shape_of(env), all_obs || no_obs)) {
+    case plan::Rollout::Fast: {
+#define CALLF(CA, CT, RS, OBS, PRIO) \
+    launch_rollout(k_rollout_fast<CA, CT, RS, OBS, PRIO>, GRID(env), rollout_fast_lds_bytes<CA, CT, RS>(env->L), (hipStream_t)stream, ra)
         // wave priorities (k_rollout_fast, PRIO) for a launch that fills the machine by itself: 16 workgroups x 256 CUs
         const bool prio = env->p.n_envs >= 4096;
 #define CALL(CA, CT, RS) do { if (prio) { if (all_obs) { CALLF(CA, CT, RS, true, true); } else { CALLF(CA, CT, RS, false, true); } }   \
                               else { if (all_obs) { CALLF(CA, CT, RS, true, false); } else { CALLF(CA, CT, RS, false, false); } } } while (0)
-        DISPATCH_ONE_CHUNK(env, CALL);
+        DISPATCH_ONE_CHUNK(env);
 #undef CALL
 #undef CALLF
-        LAUNCH_OK();
-        return DCM_OK;
+        break;
     }
-    // BASELINE configs[3], 50A/200T exactly: the multi-chunk register-resident kernel (rollout_fast_mc.hpp)
-    if (quiet_ok(env) && env->L.C == M && !env->sizes && env->A == 50 && env->T == 200 && env->L.A == 50 && env->L.T == 200 && (all_obs || no_obs)) {
+    case plan::Rollout::FastMc:
         if (all_obs) launch_rollout(k_rollout_fast_mc<50, 200, true>, GRID(env), FastM<50, 200, true>::LDS_BYTES, (hipStream_t)stream, ra);
         else launch_rollout(k_rollout_fast_mc<50, 200, false>, GRID(env), FastM<50, 200, false>::LDS_BYTES, (hipStream_t)stream, ra);
-        LAUNCH_OK();
-        return DCM_OK;
-    }
-    // Every other batch of the mid-size class (A <= 128, T <= 256; uniform or ragged): rollout_fast_g.hpp, chunk counts from the batch dims
-    if (quiet_ok(env) && env->L.C == M && env->A <= 128 && env->T <= 256 && !(env->L.A == 20 && env->L.T == 50) && !(env->L.A == 64 && env->L.T == 64) &&
-        (all_obs || no_obs)) {
-        dcm::launch_rollout_fast_g(env->A > 64 ? 2 : 1, env->T > 192 ? 4 : (env->T > 128 ? 3 : 2), all_obs, (unsigned)env->p.n_envs,
-                                   (unsigned)(Sim<128, 256, true>::lds_image_bytes(env->L)) + 512u, (hipStream_t)stream, ra);
-        LAUNCH_OK();
-        return DCM_OK;
-    }
-#endif
-#define CALL(CA, CT, RS, ...)                                                                                         \
-    launch_rollout(k_rollout_random<CA, CT, RS, ##__VA_ARGS__>, GRID(env),                                            \
-                   (Sim<CA, CT, RS>::SCR_IN_LDS ? env->L.lds_bytes() : Sim<CA, CT, RS, ((CT) > WAVE) && !(RS)>::lds_image_bytes(env->L)), (hipStream_t)stream, ra)
-    DISPATCH_ENV(env, CALL);
+        break;
+    case plan::Rollout::FastG:
+        dcm::launch_rollout_fast_g(plan::fast_g_agent_chunks(env->A), plan::fast_g_task_chunks(env->T), all_obs, (unsigned)env->p.n_envs,
+                                   env->L, (hipStream_t)stream, ra);
+        break;
+    case plan::Rollout::General:
+#define CALL(CA, CT, RS, ...) \
+    launch_rollout(k_rollout_random<CA, CT, RS, ##__VA_ARGS__>, GRID(env), rollout_random_lds_bytes<CA, CT, RS>(env->L), (hipStream_t)stream, ra)
+        DISPATCH_ENV(env);
 #undef CALL
+        break;
+    }
     LAUNCH_OK();
     return DCM_OK;
 }
@@ -2259,7 +2245,7 @@ int dcm_rollout_random(dcm_env* env, int32_t episodes, int64_t max_decisions, co
 int dcm_summary(dcm_env* env, double* out, void* stream) {
     CHECK_ENV(env);
     if (!out) return fail(DCM_ERR_INVALID, "dcm_summary: null out");
-    { const int rc_ = dcm::flush_pending(env, stream); if (rc_ != DCM_OK) return rc_; }
+    DCM_TRY(dcm::flush_pending(env, stream));
     HIP_TRY(hipMemcpyAsync(out, env->summary, (size_t)env->p.n_envs * 8 * sizeof(double), hipMemcpyDeviceToDevice,
                            (hipStream_t)stream));
     return DCM_OK;
@@ -2267,21 +2253,13 @@ int dcm_summary(dcm_env* env, double* out, void* stream) {
 
 int dcm_env_status(dcm_env* env, uint32_t* flags_out, int64_t* decisions_out, double* now_out, void* stream) {
     CHECK_ENV(env);
-    const int B = env->p.n_envs;
-    hipLaunchKernelGGL(k_env_status, dim3((B + WAVE - 1) / WAVE), dim3(WAVE), 0, (hipStream_t)stream, env->L.A, env->L.T, env->L.C,
-                       env->state, B, flags_out, decisions_out, now_out, (int32_t*)nullptr);   // (layout dims: only the record pitch matters)
-    LAUNCH_OK();
-    return DCM_OK;
+    return launch_env_status(env, flags_out, decisions_out, now_out, nullptr, stream);
 }
 
 int dcm_env_episodes(dcm_env* env, int32_t* episodes_out, void* stream) {
     CHECK_ENV(env);
     if (!episodes_out) return fail(DCM_ERR_INVALID, "dcm_env_episodes: null episodes_out");
-    const int B = env->p.n_envs;
-    hipLaunchKernelGGL(k_env_status, dim3((B + WAVE - 1) / WAVE), dim3(WAVE), 0, (hipStream_t)stream, env->L.A, env->L.T, env->L.C,
-                       env->state, B, (uint32_t*)nullptr, (int64_t*)nullptr, (double*)nullptr, episodes_out);
-    LAUNCH_OK();
-    return DCM_OK;
+    return launch_env_status(env, nullptr, nullptr, nullptr, episodes_out, stream);
 }
 
 int dcm_get_tasks(dcm_env* env, uint8_t* finished, uint8_t* feasible, double* time_start, double* time_finish,
@@ -2331,34 +2309,32 @@ int dcm_get_abandoned(dcm_env* env, uint16_t* counts_out, void* stream) {
 int dcm_state_bytes(dcm_env* env, size_t* bytes_out) {
     CHECK_HANDLE(env);
     if (!bytes_out) return fail(DCM_ERR_INVALID, "null bytes_out");
-    *bytes_out = (size_t)env->p.n_envs * env->L.rec_bytes() + (size_t)env->p.n_envs * 8 * sizeof(double) +
-                 side_bytes(env->p.n_envs, env->A, env->T);
+    *bytes_out = 0;
+    for (const Section& s : state_sections(env)) *bytes_out += s.bytes;
     return DCM_OK;
 }
 
 int dcm_clone_state(dcm_env* env, void* dst, void* stream) {
     CHECK_ENV(env);
     if (!dst) return fail(DCM_ERR_INVALID, "dcm_clone_state: null dst");
-    { const int rc_ = dcm::flush_pending(env, stream); if (rc_ != DCM_OK) return rc_; }
-    const size_t sb = (size_t)env->p.n_envs * env->L.rec_bytes();
-    HIP_TRY(hipMemcpyAsync(dst, env->state, sb, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    const size_t mb = (size_t)env->p.n_envs * 8 * sizeof(double);
-    HIP_TRY(hipMemcpyAsync((unsigned char*)dst + sb, env->summary, mb, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    HIP_TRY(hipMemcpyAsync((unsigned char*)dst + sb + mb, env->ablog, side_bytes(env->p.n_envs, env->A, env->T),
-                           hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    DCM_TRY(dcm::flush_pending(env, stream));
+    unsigned char* out = (unsigned char*)dst;
+    for (const Section& s : state_sections(env)) {
+        HIP_TRY(hipMemcpyAsync(out, s.ptr, s.bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        out += s.bytes;
+    }
     return DCM_OK;
 }
 
 int dcm_restore_state(dcm_env* env, const void* src, void* stream) {
     CHECK_ENV(env);
     if (!src) return fail(DCM_ERR_INVALID, "dcm_restore_state: null src");
-    { const int rc_ = dcm::drop_pending(env, stream); if (rc_ != DCM_OK) return rc_; }
-    const size_t sb = (size_t)env->p.n_envs * env->L.rec_bytes();
-    HIP_TRY(hipMemcpyAsync(env->state, src, sb, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    const size_t mb = (size_t)env->p.n_envs * 8 * sizeof(double);
-    HIP_TRY(hipMemcpyAsync(env->summary, (const unsigned char*)src + sb, mb, hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    HIP_TRY(hipMemcpyAsync(env->ablog, (const unsigned char*)src + sb + mb,
-                           side_bytes(env->p.n_envs, env->A, env->T), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    DCM_TRY(dcm::drop_pending(env, stream));
+    const unsigned char* in = (const unsigned char*)src;
+    for (const Section& s : state_sections(env)) {
+        HIP_TRY(hipMemcpyAsync(s.ptr, in, s.bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
+        in += s.bytes;
+    }
     env->loaded = true;
     env->reset_done = true;
     env->init_valid = false;          // (the restored records may belong to other instances)

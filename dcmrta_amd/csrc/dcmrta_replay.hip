@@ -865,30 +865,16 @@ int dcm_execute_routes(dcm_env* env, int32_t reactive, int64_t* steps_out, uint3
     const bool log = LG.route.cap > 0;
     if (log && LG.members && LG.member_cols < env->member_cap)
         return fail(DCM_ERR_INVALID, "dcm_execute_routes: the replay log's member_cols is smaller than the member_cap of dcm_load_routes");
-    { const int rc_ = dcm::flush_pending(env, stream); if (rc_ != DCM_OK) return rc_; }
+    DCM_TRY(dcm::flush_pending(env, stream));
     if (!env->loaded) return fail(DCM_ERR_STATE, "dcm_execute_routes: call dcm_load_instances first");
     if (!env->routes) return fail(DCM_ERR_STATE, "dcm_execute_routes: call dcm_load_routes first");
     if (env->sizes) return fail(DCM_ERR_STATE, "dcm_execute_routes: route replay needs a uniform batch (dcm_load_instances)");
-    // Where the replay scratch block lives: in LDS when the whole batch is resident with at most one wave per SIMD anyway (<= 4
-    // envs per CU) and it fits a quarter of the CU's LDS, else in HBM (14 instead of 4 resident waves per CU at 100A/500T).
-    int cus = 0;
-    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, env->p.device));
-    const uint32_t lds_in = replay_lds_bytes(env->A, env->T, env->member_cap, true);
-    bool slds = lds_in <= 40u * 1024u && env->p.n_envs <= 4 * cus;
-    if (env->replay_placement == 1) slds = lds_in <= 160u * 1024u;
-    if (env->replay_placement == 2) slds = false;
-    const uint32_t lds = slds ? lds_in : replay_lds_bytes(env->A, env->T, env->member_cap, false);
-
     RP P{100.0, 200.0, reactive ? 1 : 0, env->vis[0], env->vis[1], env->vis[2], env->vis[3]};  // env/task_env.py:564-565,567
-    // The register-resident kernel (replay_fast.hpp) for every replay whose agents fit two lane chunks, whose LIVE tasks -- all
-    // of them without dynamic arrivals, tasks 1..cap with them (an agent is never sent to a task that is not visible yet, and
-    // visible <= cap: env/task_env.py:567,578-584) -- fit two lane chunks and whose member slots fit one id word: BASELINE
-    // config 5 (100A/500T at the reference's cap of 100) and every small shape.  An explicit replay placement (1 / 2) asks for
-    // the general kernel, whose scratch block it places.
-    {
-        const int TL = reactive ? (env->T < env->vis[3] ? env->T : env->vis[3]) : env->T;
-        const uint32_t flds = replay_fast_lds_bytes(env->A, env->T, env->route_cap);   // (route_cap < 32768: the cursor and the length share a word)
-        if (env->replay_placement == 0 && env->A <= 2 * WAVE && TL <= 2 * WAVE && env->member_cap <= 8 && flds <= 64u * 1024u && env->route_cap < 32768) {
+    // which kernel, and where the general one keeps its scratch block: plan.hpp
+    const uint32_t flds = replay_fast_lds_bytes(env->A, env->T, env->route_cap);
+    if (plan::replay_kind(env->A, env->T, env->member_cap, reactive != 0, env->vis[3], env->replay_placement, env->route_cap, flds) ==
+        plan::Replay::Fast) {
+        const int TL = plan::replay_live_tasks(env->T, reactive != 0, env->vis[3]);
 #define REPLAYF(CMR, RE, LOG)                                                                                                \
     do {                                                                                                                    \
         (void)hipFuncSetAttribute((const void*)k_replay_fast<2, 2, CMR, RE, LOG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)flds); \
@@ -898,14 +884,18 @@ int dcm_execute_routes(dcm_env* env, int32_t reactive, int64_t* steps_out, uint3
                            travel_dist, returned, env->gscratch, LG);                                                      \
     } while (0)
 #define REPLAYF_L(CMR, RE) do { if (log) REPLAYF(CMR, RE, true); else REPLAYF(CMR, RE, false); } while (0)
-            if (env->member_cap <= 5) { if (reactive) REPLAYF_L(5, true); else REPLAYF_L(5, false); }
-            else { if (reactive) REPLAYF_L(8, true); else REPLAYF_L(8, false); }
+        if (env->member_cap <= 5) { if (reactive) REPLAYF_L(5, true); else REPLAYF_L(5, false); }
+        else { if (reactive) REPLAYF_L(8, true); else REPLAYF_L(8, false); }
 #undef REPLAYF_L
 #undef REPLAYF
-            LAUNCH_OK();
-            return DCM_OK;
-        }
+        LAUNCH_OK();
+        return DCM_OK;
     }
+    int cus = 0;
+    HIP_TRY(hipDeviceGetAttribute(&cus, hipDeviceAttributeMultiprocessorCount, env->p.device));
+    const uint32_t lds_in = replay_lds_bytes(env->A, env->T, env->member_cap, true);
+    const bool slds = plan::replay_scratch_in_lds(env->replay_placement, lds_in, env->p.n_envs, cus);
+    const uint32_t lds = slds ? lds_in : replay_lds_bytes(env->A, env->T, env->member_cap, false);
 #define REPLAY(CA, CT, CMR, SL, LOG)                                                                                         \
     do {                                                                                                                    \
         (void)hipFuncSetAttribute((const void*)k_replay<CA, CT, CMR, SL, LOG>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
@@ -915,7 +905,7 @@ int dcm_execute_routes(dcm_env* env, int32_t reactive, int64_t* steps_out, uint3
                            travel_dist, returned, env->gscratch, env->rmarr, LG);                                          \
     } while (0)
 #define REPLAY_L(CA, CT, CMR, SL) do { if (log) REPLAY(CA, CT, CMR, SL, true); else REPLAY(CA, CT, CMR, SL, false); } while (0)
-    const bool base5 = env->A == 100 && env->T == 500 && env->member_cap == 5;   // BASELINE config 5
+    const bool base5 = plan::replay_exact_100x500(env->A, env->T, env->member_cap);   // BASELINE config 5
     if (base5 && slds) REPLAY_L(100, 500, 5, true);
     else if (base5) REPLAY_L(100, 500, 5, false);
     else if (slds) REPLAY_L(0, 0, 0, true);

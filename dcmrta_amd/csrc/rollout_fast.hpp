@@ -477,6 +477,14 @@ struct Fast {
     }
 };
 
+// dynamic LDS of a k_rollout_fast launch: what the general code uses (the record image, + the scratch when it sits in LDS), then
+// the dummy slots
+template <int CA, int CT, bool RS>
+constexpr uint32_t rollout_fast_lds_bytes(Lay L) {
+    using SimT = Sim<CA, CT, RS, false>;
+    return (SimT::SCR_IN_LDS ? L.lds_bytes() : SimT::lds_image_bytes(L)) + DUMMY_SLOT_BYTES;
+}
+
 // Same contract as k_rollout_random (see there); OBS: all three observation buffers given / none of them.
 // PRIO: wave priorities, longest remaining work first (see the main loop) -- the host picks it for launches that fill the machine alone
 template <int CA, int CT, bool RS, bool OBS, bool PRIO = false>

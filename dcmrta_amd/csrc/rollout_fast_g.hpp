@@ -540,6 +540,9 @@ struct FastG {
     }
 };
 
+// dynamic LDS of a k_rollout_fast_g launch: the record image of the batch's own layout, then the dummy slots
+constexpr uint32_t rollout_fast_g_lds_bytes(Lay L) { return Sim<128, 256, true>::lds_image_bytes(L) + DUMMY_SLOT_BYTES; }
+
 // Same contract as k_rollout_random (see there); OBS: all three observation buffers given / none of them.
 template <int NAC, int NTC, bool OBS>
 __global__ __launch_bounds__(WAVE, DCM_G_WAVES) void k_rollout_fast_g(int A, int T, int PA, int PT, KP P, unsigned char* state, int episodes,

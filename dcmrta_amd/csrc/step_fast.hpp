@@ -19,7 +19,12 @@
 // per CU -- all that the kernel's VGPRs allow -- still fit: the env whose episode ends in a launch is that launch's slowest wave,
 // and with the scratch in HBM every write -> WSYNC -> read phase of the metrics is a global-memory round trip.
 template <int CA, int CT>
-constexpr bool step_scratch_in_lds() { return Lay{CA, CT}.lds_bytes() + 512u <= 10240u; }
+constexpr bool step_scratch_in_lds() { return Lay{CA, CT}.lds_bytes() + DUMMY_SLOT_BYTES <= 10240u; }
+// dynamic LDS of a k_step_fast / k_terminal_flush launch: the record image, the dummy slots, the scratch when it sits in LDS
+template <int CA, int CT, bool RS>
+constexpr uint32_t step_fast_lds_bytes(Lay L) {
+    return Sim<CA, CT, RS, false>::lds_image_bytes(L) + DUMMY_SLOT_BYTES + (step_scratch_in_lds<CA, CT>() ? L.scratch_bytes() : 0u);
+}
 
 template <int CA, int CT, bool RS>
 __global__ __launch_bounds__(WAVE, DCM_STEP_WAVES) void k_step_fast(int A, int T, int PA, int PT, KP P, unsigned char* state, const int32_t* actions,

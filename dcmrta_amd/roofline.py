@@ -134,7 +134,7 @@ def issue_roofline(c, units_per_step, step_s, unit="decision", e32_share=None):
 def rollout_kernel_name(A, T):
     """Which persistent rollout kernel dcm_rollout_random launches for a uniform batch of this shape (all three observation
     buffers given): the register-resident kernels for the one-chunk layouts, for 50A/200T and for the mid-size class (A <= 128,
-    T <= 256), the general one otherwise."""
+    T <= 256), the general one otherwise.  Mirrors plan::rollout_kind of csrc/plan.hpp (tests/test_host.py compares the two)."""
     if A <= 64 and T <= 63:
         return "k_rollout_fast"
     if (A, T) == (50, 200):
@@ -146,13 +146,15 @@ def rollout_kernel_name(A, T):
 
 def replay_kernel_name(A, T, member_cap, reactive, vis_cap):
     """Which kernel dcm_execute_routes launches (default placement): the register-resident one when the agents, the LIVE tasks (all
-    of them without dynamic arrivals, tasks 1..cap with them) and the member slots fit it, the general one otherwise."""
+    of them without dynamic arrivals, tasks 1..cap with them) and the member slots fit it, the general one otherwise.  Mirrors
+    plan::replay_kind of csrc/plan.hpp."""
     live = min(T, vis_cap) if reactive else T
     return "k_replay_fast" if (A <= 128 and live <= 128 and member_cap <= 8) else "k_replay"
 
 
 def step_kernel_name(A, T):
-    """The lockstep kernel dcm_step launches for the plain call shape (no injected choices, no route log, all outputs)."""
+    """The lockstep kernel dcm_step launches for the plain call shape (no injected choices, no route log, all outputs).  Mirrors
+    plan::one_chunk_ok of csrc/plan.hpp."""
     return "k_step_fast" if (A <= 64 and T <= 63) else "k_step"
 
 

@@ -300,9 +300,13 @@ def test_issue_roofline_pricing():
     assert abs(r3["frac"] - r3["achieved"] / r3["peak"]) < 1e-12 and r3["valu_issue_frac"] <= r3["valu_issue_frac_hi"] < r3["frac"]
 
 
-def test_kernel_name_helpers_follow_the_dispatch():
-    """roofline.rollout_kernel_name / step_kernel_name (which rocprofv3 kernel a bench line is priced with) restate the shape
-    dispatch of dcm_rollout_random / dcm_step (csrc/dcmrta_env.hip): one-chunk layouts, 50A/200T, the mid-size class, the rest."""
+def test_kernel_name_helpers_follow_the_dispatch(tmp_path):
+    """roofline.rollout_kernel_name / step_kernel_name / replay_kernel_name (which rocprofv3 kernel a bench line is priced with) follow
+    the dispatch policy of the library, csrc/plan.hpp: one-chunk layouts, 50A/200T, the mid-size class, the rest.  The header needs no
+    HIP, so it is compiled here with the host compiler and asked through ctypes: the Python helpers over the whole shape grid, the
+    inputs they do not model (ragged, wide, max_waiting_time <= 0, placement, route_cap, LDS need) directly."""
+    import shutil
+    import subprocess
     from dcmrta_amd.roofline import replay_kernel_name, rollout_kernel_name, step_kernel_name
     # dcm_execute_routes (csrc/dcmrta_replay.hip): the register-resident kernel up to 128 agents / 128 LIVE tasks / 8 member slots
     assert replay_kernel_name(100, 500, 5, True, 100) == replay_kernel_name(20, 50, 8, False, 100) == "k_replay_fast"
@@ -315,3 +319,71 @@ def test_kernel_name_helpers_follow_the_dispatch():
     for shape in ((64, 64), (100, 500), (50, 257), (128, 300)):     # T = 64 of the <64,64> layout has no free depot lane; larger shapes
         assert rollout_kernel_name(*shape) == "k_rollout_random", shape
     assert step_kernel_name(20, 50) == "k_step_fast" and step_kernel_name(70, 130) == "k_step" and step_kernel_name(64, 64) == "k_step"
+
+    cxx = shutil.which("c++") or shutil.which("g++") or "/opt/rocm/llvm/bin/clang++"
+    if not os.path.exists(cxx):
+        pytest.skip("no host C++ compiler")
+    shim = tmp_path / "plan_shim.cpp"
+    shim.write_text('#include "%s"\n' % os.path.join(ROOT, "dcmrta_amd", "csrc", "plan.hpp") + """
+using namespace dcm::plan;
+static Shape shape(int A, int T, int ragged, int wide, int quiet) { return Shape{A, T, ragged != 0, wide != 0, quiet != 0}; }
+extern "C" {
+void p_layout(int A, int T, int wide, int* out) { const LayDims d = layout_dims(A, T, wide != 0); out[0] = d.A; out[1] = d.T; out[2] = d.C; }
+int p_sim(int A, int T, int ragged, int wide, int quiet) { return (int)sim_kind(shape(A, T, ragged, wide, quiet)); }
+int p_step(int A, int T, int ragged, int wide, int quiet) { return one_chunk_ok(shape(A, T, ragged, wide, quiet)) ? 1 : 0; }
+int p_rollout(int A, int T, int ragged, int wide, int quiet, int obs) { return (int)rollout_kind(shape(A, T, ragged, wide, quiet), obs != 0); }
+int p_nac(int A) { return fast_g_agent_chunks(A); }
+int p_ntc(int T) { return fast_g_task_chunks(T); }
+int p_replay(int A, int T, int member_cap, int reactive, int vis_cap, int placement, int route_cap, unsigned fast_lds) {
+    return (int)replay_kind(A, T, member_cap, reactive != 0, vis_cap, placement, route_cap, fast_lds);
+}
+}
+""")
+    so = tmp_path / "plan_shim.so"
+    out = subprocess.run([cxx, "-std=c++17", "-O1", "-shared", "-fPIC", str(shim), "-o", str(so)], capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr[-2000:]
+    P = C.CDLL(str(so))
+    ROLLOUT = ("k_rollout_fast", "k_rollout_fast_mc", "k_rollout_fast_g", "k_rollout_random")      # enum plan::Rollout
+    REPLAY = ("k_replay_fast", "k_replay")                                                            # enum plan::Replay
+    SIM = ("<20,50,false>", "<20,50,true>", "<64,64,true>", "<50,200,false>", "<100,500,false>", "<128,256,true>", "<0,0,false>",
+           "<0,0,false,MW>")                                                                          # enum plan::SimKind
+
+    def layout(A, T, wide):
+        buf = (C.c_int * 3)()
+        P.p_layout(A, T, wide, buf)
+        return tuple(buf)
+
+    # the case the Python helpers describe: a uniform, ordinary handle, max_waiting_time > 0, all observation buffers -- every shape
+    for A in range(1, 129):
+        for T in range(1, 1024):
+            assert ROLLOUT[P.p_rollout(A, T, 0, 0, 1, 1)] == rollout_kernel_name(A, T), (A, T)
+            assert ("k_step_fast" if P.p_step(A, T, 0, 0, 1) else "k_step") == step_kernel_name(A, T), (A, T)
+    # ... and every replay of the default placement whose fast-kernel LDS need is within its limit
+    for A in (1, 20, 64, 100, 128):
+        for T in (1, 50, 128, 129, 500, 1023):
+            for member_cap in range(1, 33):
+                for reactive in (0, 1):
+                    for vis_cap in (20, 100, 128, 129, 500):
+                        got = REPLAY[P.p_replay(A, T, member_cap, reactive, vis_cap, 0, 64, 64 * 1024)]
+                        assert got == replay_kernel_name(A, T, member_cap, bool(reactive), vis_cap), (A, T, member_cap, reactive, vis_cap)
+
+    # what the Python helpers do not model.  A ragged batch of the 20A/50T layout: still the fast kernel, RS = true instantiation
+    assert ROLLOUT[P.p_rollout(20, 50, 1, 0, 1, 1)] == "k_rollout_fast" and SIM[P.p_sim(20, 50, 1, 0, 1)] == "<20,50,true>"
+    assert SIM[P.p_sim(20, 50, 0, 0, 1)] == "<20,50,false>" and layout(20, 50, 0) == layout(3, 7, 0) == (20, 50, 5)
+    assert layout(21, 50, 0) == layout(64, 64, 0) == (64, 64, 5) and layout(65, 64, 0) == (65, 64, 5)
+    # a wide handle: <0,0,false,MW>, its own layout dims with 16 member slots, the general kernels
+    for A, T in ((20, 50), (50, 200), (70, 130)):
+        assert SIM[P.p_sim(A, T, 0, 1, 1)] == "<0,0,false,MW>" and layout(A, T, 1) == (A, T, 16), (A, T)
+        assert ROLLOUT[P.p_rollout(A, T, 0, 1, 1, 1)] == "k_rollout_random" and P.p_step(A, T, 0, 1, 1) == 0, (A, T)
+    # max_waiting_time <= 0: the general kernels, which evaluate the waiting rule literally
+    for A, T in ((20, 50), (50, 200), (70, 130)):
+        assert ROLLOUT[P.p_rollout(A, T, 0, 0, 0, 1)] == "k_rollout_random" and P.p_step(A, T, 0, 0, 0) == 0, (A, T)
+    # some but not all observation buffers: the general kernel
+    assert ROLLOUT[P.p_rollout(20, 50, 0, 0, 1, 0)] == ROLLOUT[P.p_rollout(70, 130, 0, 0, 1, 0)] == "k_rollout_random"
+    # an explicit placement, a route_cap whose cursor does not fit half a word, an LDS need above 64 KiB: k_replay
+    assert REPLAY[P.p_replay(20, 50, 5, 1, 100, 0, 64, 64 * 1024)] == REPLAY[P.p_replay(20, 50, 5, 1, 100, 0, 32767, 0)] == "k_replay_fast"
+    for placement, route_cap, fast_lds in ((1, 64, 1024), (2, 64, 1024), (0, 32768, 1024), (0, 100000, 1024), (0, 64, 64 * 1024 + 1)):
+        assert REPLAY[P.p_replay(20, 50, 5, 1, 100, placement, route_cap, fast_lds)] == "k_replay", (placement, route_cap, fast_lds)
+    # lane chunks of the mid-size kernel
+    for (A, T), want in (((65, 65), (2, 2)), ((64, 129), (1, 3)), ((128, 193), (2, 4)), ((128, 256), (2, 4))):
+        assert ROLLOUT[P.p_rollout(A, T, 0, 0, 1, 1)] == "k_rollout_fast_g" and (P.p_nac(A), P.p_ntc(T)) == want, (A, T)
