@@ -156,6 +156,64 @@ class BatchedTaskEnv:
         self._instances = (d, xy, rq, du)  # keep alive until the kernel ran
         return self
 
+    @staticmethod
+    def _range(r, dim):
+        return (dim, dim) if r is None else (int(r[0]), int(r[1])) if isinstance(r, (tuple, list)) else (int(r), int(r))
+
+    def generate_instances(self, seeds, agents_range=None, tasks_range=None, max_coalition_size=5, max_duration=5.0):
+        """Make the batch on the device: env b = TaskEnv(agents_range, tasks_range, max_coalition_size=.., max_duration=..,
+        seed=seeds[b]) of the reference (env/task_env.py:9-24,57-71), bit-equal to instances.generate_batch /
+        generate_batch_ranges followed by load_instances, with nothing but the seeds crossing to the device.
+
+        seeds: an int `first` (seeds first .. first + B - 1), a numpy array or a torch uint64 / int64 tensor of B seeds.
+        A range is an int or (lo, hi); None = the env's own dim.  When both ranges are the env's dims the batch is uniform, otherwise
+        ragged with the drawn sizes in self.n_agents / self.n_tasks (one read-back of 2 B ints).  A zero-width tuple at the dim, such as
+        (20, 20) on a 20-agent env, counts as the dim: the batch is uniform and the shape-specialised kernels run, where
+        load_instances(**generate_batch_ranges(...)) of the same ranges makes a ragged batch of equal sizes -- same results, other kernels."""
+        B = self.B
+        if isinstance(seeds, (int, np.integer)):
+            seeds = np.uint64(int(seeds)) + np.arange(B, dtype=np.uint64)
+        if isinstance(seeds, torch.Tensor):
+            if seeds.dtype not in (torch.int64, torch.uint64):
+                raise DcmError("seeds must be a uint64 / int64 tensor")
+            s = seeds.to(self.device).contiguous()
+        else:
+            s = torch.from_numpy(np.ascontiguousarray(seeds, dtype=np.uint64).view(np.int64)).to(self.device)
+        if s.numel() != B:
+            raise DcmError("seeds must have one entry per env")
+        (a_lo, a_hi), (t_lo, t_hi) = self._range(agents_range, self.A), self._range(tasks_range, self.T)
+        # the library's own rule (dcm_generate_instances), from lo alone: it rejects lo > hi and hi > dim before anything changes, so
+        # lo == dim leaves hi == dim, and where it rejects, check() raises before `ragged` is used
+        ragged = not (a_lo == self.A and t_lo == self.T)
+        with torch.cuda.device(self.device):
+            check(self._lib.dcm_generate_instances(self._h, _ptr(s), a_lo, a_hi, t_lo, t_hi, int(max_coalition_size),
+                                                   float(max_duration), self._stream()))
+            if ragged != (self.n_tasks is not None):
+                self.graph_epoch += 1
+            if ragged:
+                sizes = torch.empty((2, B), dtype=torch.int32, device=self.device)
+                check(self._lib.dcm_get_instances(self._h, None, None, None, None, _ptr(sizes[0]), _ptr(sizes[1]), self._stream()))
+                sizes = sizes.cpu().numpy()
+                self.n_agents, self.n_tasks = sizes[0].copy(), sizes[1].copy()
+            else:
+                self.n_agents = self.n_tasks = None
+        self._instances = (s,)  # keep alive until the kernel ran
+        return self
+
+    def instances(self):
+        """The instances the env holds, however they got there, as device tensors in the keyword format of load_instances:
+        depot[B,2], task_xy[B,T,2], req[B,T], dur[B,T], n_agents[B], n_tasks[B] (rows beyond an env's own sizes: xy 0, req 1, dur 0, the
+        padding of instances.generate_batch_ranges; n_agents / n_tasks are None on a uniform batch)."""
+        B, T, dev = self.B, self.T, self.device
+        o = dict(depot=torch.empty((B, 2), dtype=torch.float64, device=dev), task_xy=torch.empty((B, T, 2), dtype=torch.float64, device=dev),
+                 req=torch.empty((B, T), dtype=torch.int32, device=dev), dur=torch.empty((B, T), dtype=torch.float64, device=dev),
+                 n_agents=torch.empty((B,), dtype=torch.int32, device=dev), n_tasks=torch.empty((B,), dtype=torch.int32, device=dev))
+        with torch.cuda.device(dev):
+            check(self._lib.dcm_get_instances(self._h, *[_ptr(v) for v in o.values()], self._stream()))
+        if self.n_tasks is None:
+            o["n_agents"] = o["n_tasks"] = None
+        return o
+
     def reset(self, seeds, observe=True):
         """seeds: uint64[B] per-env choice-protocol seeds (numpy/torch) or an int base seed."""
         if isinstance(seeds, (int, np.integer)):
@@ -428,3 +486,17 @@ def device_distance(a_xy, b_xy, device="cuda:0"):
         check(lib.dcm_distance(_ptr(ax), _ptr(ay), _ptr(bx), _ptr(by), _ptr(d), _ptr(t), ax.numel(),
                                C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
     return d.cpu().numpy(), t.cpu().numpy()
+
+
+def device_generator_draws(seeds, n_doubles, bound, n_ints, device="cuda:0"):
+    """Per seed the first n_doubles of np.random.default_rng(seed).random(), then n_ints of .integers(0, bound), from the device
+    routines generate_instances uses (known-answer test helper): (f64[n, n_doubles], u32[n, n_ints]) as numpy arrays."""
+    lib = _lib.load()
+    dev = torch.device(device)
+    s = torch.from_numpy(np.ascontiguousarray(seeds, dtype=np.uint64).view(np.int64)).to(dev)
+    d = torch.empty((s.numel(), int(n_doubles)), dtype=torch.float64, device=dev)
+    i = torch.empty((s.numel(), int(n_ints)), dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        check(lib.dcm_generator_draws(_ptr(s), s.numel(), int(n_doubles), int(bound), int(n_ints), _ptr(d), _ptr(i),
+                                      C.c_void_p(torch.cuda.current_stream(dev).cuda_stream)))
+    return d.cpu().numpy(), i.cpu().numpy().view(np.uint32)

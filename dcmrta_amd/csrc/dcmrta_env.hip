@@ -24,6 +24,7 @@
 #include <mutex>
 
 #include "common.hpp"
+#include "np_stream.hpp"
 
 using namespace dcm;
 
@@ -1830,6 +1831,10 @@ __global__ void k_distance(const double* ax, const double* ay, const double* bx,
     if (time_out) time_out[i] = over_velocity(d);
 }
 
+#ifndef DCM_TU_G
+#include "instgen.hpp"
+#endif
+
 // ---------------------------------------------------------------------------------- host side
 // Which Sim<> instantiation and which kernels serve a handle is decided in plan.hpp; here its answers become template arguments.
 // The instantiations by their plan::SimKind: first the one-chunk layouts, which also have the register-resident kernels of
@@ -2048,6 +2053,51 @@ int dcm_load_instances_ragged(dcm_env* env, const double* depot, const double* t
     HIP_TRY(hipMemcpyAsync(env->sizes, env->sizes_host.data(), (size_t)2 * B * sizeof(int32_t), hipMemcpyHostToDevice,
                            (hipStream_t)stream));
     return launch_load(env, depot, task_xy, req, dur, stream);
+}
+
+// TaskEnv(agents_range, tasks_range, max_coalition_size, max_duration, seed=inst_seeds[e]) for every env, made on the device
+int dcm_generate_instances(dcm_env* env, const uint64_t* inst_seeds, int32_t agents_lo, int32_t agents_hi, int32_t tasks_lo,
+                           int32_t tasks_hi, int32_t max_coalition_size, double max_duration, void* stream) {
+    CHECK_ENV(env);
+    if (!inst_seeds) return fail(DCM_ERR_INVALID, "dcm_generate_instances: null seeds");
+    if (agents_lo < 1 || agents_lo > agents_hi || agents_hi > env->A || tasks_lo < 1 || tasks_lo > tasks_hi || tasks_hi > env->T)
+        return fail(DCM_ERR_INVALID, "dcm_generate_instances: need 1 <= agents_lo <= agents_hi <= A and 1 <= tasks_lo <= tasks_hi <= T");
+    if (max_coalition_size < 1 || max_coalition_size > env->L.C)
+        return fail(DCM_ERR_INVALID, "dcm_generate_instances: need 1 <= max_coalition_size <= the member slots of the handle");
+    if (!(max_duration >= 0.0)) return fail(DCM_ERR_INVALID, "dcm_generate_instances: need max_duration >= 0");
+    DCM_TRY(dcm::drop_pending(env, stream));
+    const bool uniform = agents_lo == env->A && tasks_lo == env->T;    // (lo <= hi <= the dim: both ranges zero-width at the dims)
+    if (uniform && env->sizes) { HIP_TRY(hipFree(env->sizes)); env->sizes = nullptr; }
+    if (!uniform && !env->sizes) HIP_TRY(hipMalloc((void**)&env->sizes, (size_t)2 * env->p.n_envs * sizeof(int32_t)));
+    const GenArgs g{agents_lo, agents_hi, tasks_lo, tasks_hi, max_coalition_size, max_duration};
+    hipLaunchKernelGGL(k_generate_instances, GRID(env), 0, (hipStream_t)stream, env->L.A, env->L.T, env->L.C, env->state, inst_seeds, g,
+                       env->sizes);
+    LAUNCH_OK();
+    env->loaded = true;
+    env->reset_done = false;
+    return DCM_OK;
+}
+
+int dcm_get_instances(dcm_env* env, double* depot, double* task_xy, int32_t* req, double* dur, int32_t* n_agents, int32_t* n_tasks,
+                      void* stream) {
+    CHECK_ENV(env);
+    if (!env->loaded) return fail(DCM_ERR_STATE, "dcm_get_instances: no instances loaded");
+    hipLaunchKernelGGL(k_get_instances, GRID(env), 0, (hipStream_t)stream, DIMS(env), env->L.C, (const unsigned char*)env->state,
+                       (const int32_t*)env->sizes, depot, task_xy, req, dur, n_agents, n_tasks);
+    LAUNCH_OK();
+    return DCM_OK;
+}
+
+int dcm_generator_draws(const uint64_t* seeds, int64_t n, int32_t n_doubles, uint32_t bound, int32_t n_ints, double* doubles_out,
+                        uint32_t* ints_out, void* stream) {
+    if (!seeds || n < 0 || n > INT32_MAX || n_doubles < 0 || n_ints < 0 || bound < 1 || (n_doubles > 0 && !doubles_out) ||
+        (n_ints > 0 && !ints_out))
+        return fail(DCM_ERR_INVALID, "dcm_generator_draws: bad argument");
+    if (n == 0) return DCM_OK;
+    hipLaunchKernelGGL(k_generator_draws, dim3((unsigned)n), dim3(WAVE), 0, (hipStream_t)stream, seeds, n_doubles, bound - 1u, n_ints,
+                       doubles_out, ints_out);
+    LAUNCH_OK();
+    return DCM_OK;
 }
 
 }  // extern "C"

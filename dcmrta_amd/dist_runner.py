@@ -35,6 +35,7 @@ class ShardedRunner:
         self.lo, self.hi = shard_range(self.total, self.ctx.rank, self.ctx.world)
         if self.hi <= self.lo:
             raise ValueError("fewer envs than ranks")
+        # runner_kwargs go to BatchedRunner (device_instances=True: every rank makes its shard's instances on its own device)
         # episode_stride = the whole budget, env_offset = this rank's shard: round e plays instances [e * total, (e + 1) * total)
         self.runner = BatchedRunner(metaAgentID=self.ctx.rank, n_envs=self.hi - self.lo, device=str(self.ctx.device),
                                     episode_stride=self.total, env_offset=self.lo, **runner_kwargs)

@@ -37,7 +37,8 @@ def init(n_envs=None, devices=None, net_factory=None, base_seed=0, concurrent=Fa
     n_envs: episodes per `job` of every actor -- or total_envs: env budget per round split over `num_actors` actors by
     dist.shard_range (actor i gets the i-th contiguous share).  devices: list of torch devices (default: all visible
     GPUs); net_factory: () -> policy module (default: the stand-in AttentionNet; pass the reference's own class to keep
-    using attention.py).  runner_kwargs go to BatchedRunner (rollout_precision, check_every, ...)."""
+    using attention.py).  runner_kwargs go to BatchedRunner (rollout_precision, check_every,
+    device_instances=True to make every job's instances on the device, ...)."""
     _CFG.update(n_envs=n_envs if n_envs is not None else 256, devices=devices, net_factory=net_factory, base_seed=base_seed,
                 concurrent=bool(concurrent), runner_kwargs=dict(runner_kwargs), total_envs=total_envs, num_actors=int(num_actors))
 

@@ -39,7 +39,8 @@ class EnvError(RuntimeError):
 class BatchedRunner:
     def __init__(self, metaAgentID=0, n_envs=256, device="cuda:0", net_factory=None, base_seed=0, max_steps=None, gamma=1.0,
                  rollout_precision="fp32", check_every=8, use_graph=True, cache_shapes=8, buckets="auto", episode_stride=None,
-                 env_offset=0, strict_mask=None, twin_rollout="auto", tune_gemms=False, gemm_tuning_file=None):
+                 env_offset=0, strict_mask=None, twin_rollout="auto", tune_gemms=False, gemm_tuning_file=None,
+                 device_instances=False):
         """rollout_precision "bf16" / "fp16": the rollouts (sampled, greedy twin, evaluation) run a low-precision shadow
         of localNetwork (net.rollout_copy(dtype), refreshed after every weight update); needs a net that offers
         rollout_copy / sync_rollout_copy (the stand-in does).  max_steps: capacity of the experience record in batched
@@ -52,7 +53,11 @@ class BatchedRunner:
         graphs will use with PyTorch's TunableOp tuning switched on (stock torch.cuda.tunable: picks the fastest rocBLAS /
         hipBLASLt solution per GEMM shape; 8.0 -> 6.8 ms per fp32 forward at 4096 x 20A/50T) and the selection is kept for the
         graphs.  Tuning a shape takes about a minute and a half the first time; the results accumulate in `gemm_tuning_file`
-        (default: PyTorch's own tunableop_results file) across rounds and runs, so it pays for long trainings, not for one job."""
+        (default: PyTorch's own tunableop_results file) across rounds and runs, so it pays for long trainings, not for one job.
+        device_instances: job() and testing() make their instances on the device (BatchedTaskEnv.generate_instances: the same
+        seeds, bit-equal instances) instead of one numpy Generator per env on the host plus four copies.  A zero-width tuple range
+        at the env's dims then gives a uniform batch (the shape-specialised kernels) where the host path gives a ragged one of equal
+        sizes: the same results through other kernels."""
         self.metaAgentID = metaAgentID
         self.device = torch.device(device)
         self.B = int(n_envs)
@@ -73,6 +78,7 @@ class BatchedRunner:
         # ("auto": below 1024 envs -- 8.5e4 -> 1.4e5 recorded decisions/s at 256 envs; from there on the forward is throughput-bound
         #  and two batches of B cost the same as one of 2 B)
         self.twin_rollout = (self.B < 1024) if twin_rollout == "auto" else bool(twin_rollout)
+        self.device_instances = bool(device_instances)
         self.tune_gemms = bool(tune_gemms)
         if self.tune_gemms:
             import torch.cuda.tunable as tunable
@@ -310,10 +316,13 @@ class BatchedRunner:
         env = slot["env"]
         first = self.first_env(episodeNumber)
         ragged = self._is_range(agents_num) or self._is_range(tasks_num)
-        if ragged:
-            inst = generate_batch_ranges(range(self.base_seed + first, self.base_seed + first + self.B),
-                                         tuple(agents_num) if isinstance(agents_num, (tuple, list)) else int(agents_num),
-                                         tuple(tasks_num) if isinstance(tasks_num, (tuple, list)) else int(tasks_num))
+        ar = tuple(agents_num) if isinstance(agents_num, (tuple, list)) else int(agents_num)
+        tr = tuple(tasks_num) if isinstance(tasks_num, (tuple, list)) else int(tasks_num)
+        if self.device_instances:
+            inst = None
+            inst_seeds = np.uint64(self.base_seed + first) + np.arange(self.B, dtype=np.uint64)
+        elif ragged:
+            inst = generate_batch_ranges(range(self.base_seed + first, self.base_seed + first + self.B), ar, tr)
         else:
             inst = generate_batch(self.B, A, T, base_seed=self.base_seed, first=first)   # worker.py:32
         net = self._rollout_net()
@@ -321,7 +330,10 @@ class BatchedRunner:
         seeds = env_seeds(self.base_seed, first, self.B)
         if self.twin_rollout:
             B = self.B
-            env.load_instances(**{k: (np.concatenate([v, v]) if isinstance(v, np.ndarray) else v) for k, v in inst.items()})
+            if inst is None:
+                env.generate_instances(np.concatenate([inst_seeds, inst_seeds]), ar, tr)
+            else:
+                env.load_instances(**{k: (np.concatenate([v, v]) if isinstance(v, np.ndarray) else v) for k, v in inst.items()})
             summary2, rec2, n_steps = self.rollout(net, slot, np.concatenate([seeds, seeds]), "twin", record=True)
             truncated = self._check_flags(env, "sampled + greedy twin rollout")
             summary, greedy_summary = summary2[:B], summary2[B:]
@@ -329,7 +341,10 @@ class BatchedRunner:
             grec = {k: v[:, B:] for k, v in rec2.items()} if self.keep_greedy_record else None
             g_steps = n_steps
         else:
-            env.load_instances(**inst)
+            if inst is None:
+                env.generate_instances(inst_seeds, ar, tr)
+            else:
+                env.load_instances(**inst)
             summary, rec, n_steps = self.rollout(net, slot, seeds, "sample", record=True)             # run_episode
             truncated = self._check_flags(env, "sampled rollout")
             greedy_summary, grec, g_steps = self.rollout(net, slot, seeds, "greedy", record=self.keep_greedy_record)  # baseline_test :89
@@ -409,10 +424,13 @@ class BatchedRunner:
             # driver.py:245-250 asks for ONE seed per call, and padding that to n_envs copies cost a full-batch rollout each
             slot = self._slot(A, T, n_envs=len(chunk))
             env = slot["env"]
-            inst = generate_batch_ranges(chunk, ar, tr)    # same draw order as TaskEnv(ar, tr, seed=s), sizes first
-            if not ragged:
-                inst.pop("n_agents"); inst.pop("n_tasks")  # uniform batch: shape-specialised kernels
-            env.load_instances(**inst)
+            if self.device_instances:
+                env.generate_instances(np.array([int(s) for s in chunk], dtype=np.uint64), ar, tr)
+            else:
+                inst = generate_batch_ranges(chunk, ar, tr)    # same draw order as TaskEnv(ar, tr, seed=s), sizes first
+                if not ragged:
+                    inst.pop("n_agents"); inst.pop("n_tasks")  # uniform batch: shape-specialised kernels
+                env.load_instances(**inst)
             cs = np.array([env_seeds(self.base_seed, int(s), 1)[0] for s in chunk], dtype=np.uint64)
             summary, _, _ = self.rollout(net, slot, cs, "greedy", record=False)
             self._check_flags(env, "testing")

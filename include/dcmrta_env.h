@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define DCM_ABI_VERSION 5 /* v3: dcm_build_id, dcm_set_visibility, dcm_load_instances validates req on the device; v4: dcm_set_replay_placement; v5: DCM_PARAM_WIDE_MEMBERS */
+#define DCM_ABI_VERSION 5 /* v3: dcm_build_id, dcm_set_visibility, dcm_load_instances validates req on the device; v4: dcm_set_replay_placement; v5: DCM_PARAM_WIDE_MEMBERS; still v5, additions only: dcm_generate_instances, dcm_get_instances, dcm_generator_draws */
 
 typedef struct dcm_env dcm_env; /* opaque */
 
@@ -143,6 +143,32 @@ int dcm_load_instances(dcm_env *env, const double *depot, const double *task_xy,
  * Route replay (dcm_execute_routes) needs a uniform batch. */
 int dcm_load_instances_ragged(dcm_env *env, const double *depot, const double *task_xy, const int32_t *req,
                               const double *dur, const int32_t *n_agents, const int32_t *n_tasks, void *stream);
+
+/* TaskEnv(agents_range, tasks_range, max_coalition_size=.., max_duration=.., seed=inst_seeds[e]) for every env, made on the device
+ * (env/task_env.py:21-22,57-71): replaces the host generator plus dcm_load_instances / dcm_load_instances_ragged, and nothing but
+ * inst_seeds[B] u64 comes from the caller.  The instances are bit-equal to the reference's: np.random.default_rng(seed) is restated
+ * in csrc/np_stream.hpp, the draw order of generate_env in csrc/instgen.hpp.  A range with lo == hi is an int (or a tuple that
+ * draws nothing); lo < hi draws the env's own size from the stream first, tasks before agents (:58-65).
+ * Needs 1 <= agents_lo <= agents_hi <= A, 1 <= tasks_lo <= tasks_hi <= T and 1 <= max_coalition_size <= the member slots of the
+ * handle (DCM_MAX_MEMBERS, or DCM_MAX_MEMBERS_WIDE with DCM_PARAM_WIDE_MEMBERS), max_duration >= 0: otherwise DCM_ERR_INVALID, and
+ * nothing is launched or changed.  When both ranges are the handle's dims the batch is uniform, exactly as after
+ * dcm_load_instances; otherwise it is ragged as after dcm_load_instances_ragged, with the per-env sizes written on the device
+ * (dcm_get_instances returns them).  dcm_reset must follow, as after dcm_load_instances. */
+int dcm_generate_instances(dcm_env *env, const uint64_t *inst_seeds, int32_t agents_lo, int32_t agents_hi, int32_t tasks_lo,
+                           int32_t tasks_hi, int32_t max_coalition_size, double max_duration, void *stream);
+
+/* The instances the handle holds, however they got there, in the batch shapes of dcm_load_instances (any pointer may be NULL):
+ * depot[B,2] f64, task_xy[B,T,2] f64, req[B,T] i32, dur[B,T] f64, n_agents[B] / n_tasks[B] i32 (the batch dims on a uniform
+ * batch).  Rows beyond an env's own sizes read xy 0, req 1, dur 0. */
+int dcm_get_instances(dcm_env *env, double *depot, double *task_xy, int32_t *req, double *dur, int32_t *n_agents,
+                      int32_t *n_tasks, void *stream);
+
+/* Known-answer entry point of the instance generator's random stream (no handle, like dcm_distance): for each of the n seeds
+ * (u64[n]) the first n_doubles values of np.random.default_rng(seed).random(), then n_ints values of .integers(0, bound),
+ * 1 <= bound <= 2^32 - 1, through the device routines dcm_generate_instances uses: doubles_out f64[n, n_doubles],
+ * ints_out u32[n, n_ints]. */
+int dcm_generator_draws(const uint64_t *seeds, int64_t n, int32_t n_doubles, uint32_t bound, int32_t n_ints,
+                        double *doubles_out, uint32_t *ints_out, void *stream);
 
 /* reset + clear_decisions (env/task_env.py:116-140) for every env, then advance each env to its
  * first decision point (event t=0, one group of all agents; worker.py:45-51).
