@@ -46,6 +46,8 @@ SIGNATURES = {
     "dcm_load_instances_ragged": (C.c_int, [_vp] * 8),   # env, depot, task_xy, req, dur, n_agents (host), n_tasks (host), stream
     "dcm_generate_instances": (C.c_int, [_vp, _vp, _i32, _i32, _i32, _i32, _i32, C.c_double, _vp]),   # env, inst_seeds, agents lo/hi, tasks lo/hi, max_coalition_size, max_duration, stream
     "dcm_get_instances": (C.c_int, [_vp] * 8),
+    "dcm_set_instance_renewal": (C.c_int, [_vp, C.c_uint64]),   # env, stride (0 = off)
+    "dcm_instance_index": (C.c_int, [_vp] * 3),
     "dcm_generator_draws": (C.c_int, [_vp, _i64, _i32, C.c_uint32, _i32, _vp, _vp, _vp]),   # seeds, n, n_doubles, bound, n_ints, doubles_out, ints_out, stream
     "dcm_reset": (C.c_int, [_vp] * 3),
     "dcm_observe": (C.c_int, [_vp] * 8),

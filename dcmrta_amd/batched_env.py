@@ -200,6 +200,24 @@ class BatchedTaskEnv:
         self._instances = (s,)  # keep alive until the kernel ran
         return self
 
+    def set_instance_renewal(self, stride):
+        """A fresh instance at every episode restart (dcm_set_instance_renewal): with stride != 0 an env that restarts an episode
+        inside step() (auto_reset) or rollout_random() first replaces its instance by the one of seed seeds[b] + (n + 1) * stride
+        (mod 2**64; seeds = what generate_instances was given, n = instance_index()[b]) -- instances.renewal_seeds -- the way every
+        reference Worker builds a new TaskEnv (worker.py:32).  With stride = B and seeds base + arange(B), episode k of env b plays
+        instance base + k * B + b.  0 turns it off.  Needs a uniform batch made by generate_instances (DcmError otherwise);
+        load_instances and a new generate_instances turn it off; reset() does not renew."""
+        check(self._lib.dcm_set_instance_renewal(self._h, int(stride) % (1 << 64)))
+        self.graph_epoch += 1          # a captured dcm_step has the kernel form and its arguments baked in
+        return self
+
+    def instance_index(self):
+        """uint32-valued int64[B] device tensor: how many times each env's instance has been renewed since generate_instances."""
+        out = torch.empty((self.B,), dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            check(self._lib.dcm_instance_index(self._h, _ptr(out), self._stream()))
+        return out.to(torch.int64) & 0xFFFFFFFF
+
     def instances(self):
         """The instances the env holds, however they got there, as device tensors in the keyword format of load_instances:
         depot[B,2], task_xy[B,T,2], req[B,T], dur[B,T], n_agents[B], n_tasks[B] (rows beyond an env's own sizes: xy 0, req 1, dur 0, the

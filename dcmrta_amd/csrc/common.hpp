@@ -27,7 +27,7 @@ struct Hdr {  // 64 B header of an env record
     uint32_t flags;        // DCM_FLAG_*
     uint32_t groups;       // packed in memory: bits 0-7 cur_group, 8-15 n_groups, 16-23 empty_passes (see HdrRegs)
     uint32_t episodes;     // finished episodes since dcm_reset
-    uint32_t reserved;
+    uint32_t reserved;     // instance index n: renewals of this env's instance since dcm_generate_instances (instgen.hpp); else 0
     double max_arrival;    // largest arrival time any agent_step of this episode has appended to an arrival_time list: the
                            // "max(arrival_time)" over all agents that next_decision / check_finished return as the time when
                            // nobody can decide any more (env/task_env.py:286,369).  With valid actions every list is
@@ -146,6 +146,20 @@ struct IdW {
 struct KP {
     double mwt;       // max_waiting_time
     double max_time;  // MAX_TIME
+};
+
+// The scalar arguments of generate_env (instgen.hpp)
+struct GenArgs {
+    int32_t a_lo, a_hi, t_lo, t_hi;   // agents_range, tasks_range (lo == hi: an int, or a tuple that draws nothing)
+    int32_t max_coalition_size;
+    double max_duration;
+};
+// Instance renewal (dcm_set_instance_renewal): what a kernel that restarts episodes needs to draw the env's next instance, the last
+// argument of the renewing kernel forms (k_rn_*).  The batch is uniform: both ranges of g are zero-width at the handle's dims.
+struct Renew {
+    const uint64_t* seeds;            // [B] inst_seeds of dcm_generate_instances (the handle's device copy)
+    uint64_t stride;                  // instance n of env e has the seed seeds[e] + n * stride (mod 2^64); never 0 here
+    GenArgs g;
 };
 
 // optional route history of the lockstep API (agent['route'] / agent['arrival_time'], env/task_env.py:95-96,314,318)
@@ -466,6 +480,12 @@ struct dcm_env {
     double* summary = nullptr;       // [B][8]
     uint16_t* ablog = nullptr;       // [B][A][AB_CAP] abandonment log (side table of the state)
     bool loaded = false, reset_done = false;
+    // instance renewal (dcm_set_instance_renewal): what dcm_generate_instances was last called with.  `generated` while the records'
+    // instances came from it; renew_stride != 0 while renewal is on (only ever with generated && !sizes)
+    uint64_t* inst_seeds = nullptr;  // [B] device copy of its inst_seeds
+    dcm::GenArgs gen{};
+    bool generated = false;
+    uint64_t renew_stride = 0;
     int32_t* sizes = nullptr;        // [B][2] (A_e, T_e) of a ragged batch (dcm_load_instances_ragged), else nullptr
     std::vector<int32_t> sizes_host;
     // route replay (dcmrta_replay.hip)

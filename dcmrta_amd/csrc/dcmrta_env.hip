@@ -55,8 +55,9 @@ struct RolloutArgs {
     int64_t* steps_out; double* summary; uint16_t* ablog;
     const int32_t* sizes; int64_t budget_all; const int64_t* budget_in;
     unsigned char* gscr; double* retlog; int retcap;
+    Renew rn;            // last argument of the renewing forms (k_rn_*), which are launched while rn.stride != 0
 };
-// k_rollout_fast_g<NAC, NTC, OBS> (rollout_fast_g.hpp, its own translation unit)
+// k_rollout_fast_g<NAC, NTC, OBS> / k_rn_rollout_fast_g<NAC, NTC, OBS> (rollout_fast_g.hpp, its own translation unit)
 void launch_rollout_fast_g(int nac, int ntc, bool obs, unsigned grid, Lay L, hipStream_t stream, const RolloutArgs& a);
 }  // namespace dcm
 
@@ -1336,6 +1337,8 @@ __device__ __forceinline__ int env_of_workgroup() {
     return x * q + (x < r ? x : r) + i;
 }
 
+#include "instgen.hpp"
+
 __global__ __launch_bounds__(WAVE) void k_load_instances(int A, int T, int PA, int PT, int PC, unsigned char* state, const double* depot,
                                                         const double* task_xy, const int32_t* req, const double* dur,
                                                         const int32_t* sizes) {
@@ -1436,154 +1439,13 @@ __global__ __launch_bounds__(WAVE) void k_observe(int A, int T, int PA, int PT, 
     }
 }
 
-template <int CA, int CT, bool RS, int MC = M>
-__global__ __launch_bounds__(WAVE) void k_step(int A, int T, int PA, int PT, KP P, unsigned char* state, const int32_t* actions,
-                                              const int32_t* leader_in, const int32_t* nfol_in, const int16_t* fol_in,
-                                              float* agents_out, float* tasks_out, uint8_t* mask_out,
-                                              int32_t* leader_out, uint8_t* active_out, double* summary, RouteLog log,
-                                              uint16_t* ablog, uint32_t mode, const int32_t* sizes, unsigned char* gscr,
-                                              uint32_t max_episodes, double* retlog, int retcap) {
-    const int e = env_of_workgroup(), lane = threadIdx.x;
-    int eA, eT;
-    env_dims<CA, CT, RS>(sizes, e, A, T, eA, eT);
-    using SimT = Sim<CA, CT, RS, false, MC>;
-    SimT S{eA, eT, PA, PT, smem, nullptr};
-    using AMask = typename SimT::AMask;
-    const Lay L = S.L();
-    S.scr = gscr + (size_t)e * L.scratch_bytes();
-    const int BA = S.BA(A), BT = S.BT(T);
-    unsigned char* rec = state + (size_t)e * L.rec_bytes();
-    PHK_DECL;
-    // the host's per-env inputs are requested first, so that their memory latency hides behind the record copy instead of
-    // being paid at their first use in the middle of the step (phase profile: ~1 us of every wave's critical path)
-    const int act_in = actions[e];
-    const int lead_in = leader_in ? leader_in[e] : -1;
-    const int nf = nfol_in ? nfol_in[e] : -1;
-        // (plain loads, not the non-temporal ones of the persistent kernel: with the record read AND rewritten every launch the
-    //  default L2 policy measured 5.5 % faster at 65 536 envs, same at 4096)
-    typename SimT::XY xy;
-    S.template load_record<false>(rec, lane, xy);
-    S.set_ablog(ablog, e, BA, BT, lane);
-    S.set_retlog(retlog, retcap, e, lane);
-    if (lane == 0) { *S.dirty() = 0; *S.dirty2() = 0; }
-    WSYNC();
-    HdrRegs h = load_hdr(smem);
-    PHK_MARK(0);                                   // record HBM -> LDS (issue + wait)
-    const bool was_active = !(h.flags & DCM_FLAG_DONE);
-    if (was_active) {
-        AMask gm;
-        const uint64_t k1 = key1(h.seed, h.d);
-        const int leader = S.pick_leader(h, lane, lead_in, k1, gm, (mode & DCM_PARAM_NO_GROUPING) != 0);
-        PHK_MARK(1);                               // key + leader
-        if (leader >= 0) {
-            PH_DECL;
-            S.apply_and_advance(h, P, lane, leader, gm, act_in, k1, nf,
-                                fol_in ? fol_in + (size_t)e * DCM_FOLLOWER_COLS : nullptr, summary + (size_t)e * 8 PH_PASS,
-                                log, e * BA, (mode & DCM_PARAM_NO_GROUPING) != 0, (mode & DCM_PARAM_STRICT_MASK) ? 2 : 1, false, true, &xy);
-            PHK_MARK(2);                           // apply + updates + advance (+ terminal)
-            PHK_INNER();
-            // DCM_PARAM_AUTO_RESET: the episode has just ended (its results are in the summary row) -> start the next one from
-            // the loaded instance, as k_rollout_random does between its episodes (the decision counter keeps running)
-            if ((mode & DCM_PARAM_AUTO_RESET) && (h.flags & DCM_FLAG_DONE) &&
-                !(h.flags & (DCM_FLAG_BAD_ACTION | DCM_FLAG_OVERFLOW | DCM_FLAG_BAD_LEADER | DCM_FLAG_BAD_INSTANCE)) &&
-                (max_episodes == 0 || uni(((const Hdr*)smem)->episodes) < max_episodes)) {
-                if (log.len) for (int a = lane; a < eA; a += WAVE) log.len[(size_t)e * BA + a] = 0;
-                S.reset_state(h, lane);
-                if (lane == 0) *S.dirty() = SimT::DIRTY_ALL;
-                S.advance(h, P, lane, summary + (size_t)e * 8 PH_PASS, (mode & DCM_PARAM_NO_GROUPING) != 0);
-                PHK_MARK(3);                       // auto-reset: reset_state + first event
-            }
-        }
-    }
-    if (was_active) {
-        WSYNC();
-        store_hdr(h, lane);
-        WSYNC();
-        // Write back what this step can have changed: the header and the agent arrays always, status words always, and of
-        // the other task sections only those marked dirty (one decision typically touches one member-arrival row, the id
-        // word of one task and -- when a task became feasible -- the two time arrays: ~2.4 of the 4.6 KB at 20A/50T).
-        // Ranges are widened to 16-byte boundaries; the bytes around them are unchanged copies of what HBM already holds.
-        const uint32_t dm = uni(*S.dirty());
-        const bool big = gridDim.x >= 8192u;           // far more state than the L2s hold: stream the stores (copy16_nt)
-        auto put = [&](uint32_t lo, uint32_t hi) {     // [lo, hi) of the record
-            lo &= ~15u; hi = (hi + 15u) & ~15u;
-            if (big) copy16_nt(rec + lo, smem + lo, hi - lo, lane); else copy16(rec + lo, smem + lo, hi - lo, lane);
-        };
-        const uint32_t Tn = (uint32_t)S.PT();
-        put(0, L.tb());                                                               // header + agent arrays
-        const uint32_t d2 = uni(*S.dirty2());
-        if ((dm & SimT::DIRTY_TIMES) && !(dm & SimT::DIRTY_NAB) && (d2 >> 24) == 1u) {   // one task became feasible: its pieces of the two arrays
-            const uint32_t bt = d2 & 0xFFFFFFu;
-            for (uint32_t sec : {L.ts(), L.tf()}) {
-                const uint32_t lo = (sec + 8u * bt) & ~63u, end = sec + 8u * Tn;
-                put(lo < sec ? sec : lo, lo + 64u < end ? lo + 64u : end);
-            }
-        } else if (dm & SimT::DIRTY_TIMES) put(L.ts(), L.marr());         // time_start, time_finish
-        // a join (the only thing that dirties arrival rows / member ids without also dirtying the abandonment counts) names its
-        // task: the aligned 64-byte pieces of those sections that hold it go back instead of the 8 T-byte sections
-        const bool one_task = (dm & SimT::DIRTY_IDS) && !(dm & SimT::DIRTY_NAB) && (dm & SimT::DIRTY_ROWS) != SimT::DIRTY_ROWS;
-        if (one_task) {
-            const uint32_t jt = dm >> SimT::DIRTY_TASK_SHIFT;
-            auto piece = [&](uint32_t sec) {
-                const uint32_t lo = (sec + 8u * jt) & ~63u, end = sec + 8u * Tn;
-                put(lo < sec ? sec : lo, lo + 64u < end ? lo + 64u : end);
-            };
-#pragma unroll
-            for (int j = 0; j < MC; j++) if (dm & (2u << j)) piece(L.marr() + 8u * Tn * j);
-            for (uint32_t w = 0; w < L.idw(); w++) piece(L.mids() + 8u * Tn * w);
-        } else {
-            if ((dm & SimT::DIRTY_ROWS) == SimT::DIRTY_ROWS) put(L.marr(), L.mids());
-            else {
-#pragma unroll
-                for (int j = 0; j < MC; j++) if (dm & (2u << j)) put(L.marr() + 8u * Tn * j, L.marr() + 8u * Tn * (j + 1));
-            }
-            if (dm & SimT::DIRTY_IDS) put(L.mids(), L.tinfo());
-        }
-        put(L.tinfo(), (dm & SimT::DIRTY_NAB) ? L.mut_bytes() : L.tnab());  // status words (+ abandonment counts)
-        PHK_MARK(5);                               // write-back (issue)
-    }
-    const bool want_obs = agents_out || tasks_out || mask_out || leader_out || active_out;
-    if (want_obs) {
-        WSYNC();
-        float* ag = agents_out ? agents_out + (size_t)e * 6 * BA : nullptr;
-        float* tk = tasks_out ? tasks_out + (size_t)e * 5 * (BT + 1) : nullptr;
-        uint8_t* mk = mask_out ? mask_out + (size_t)e * (BT + 1) : nullptr;
-        int leader = -1;
-        if (!(h.flags & DCM_FLAG_DONE)) { AMask gm; leader = S.pick_leader(h, lane, -1, key1(h.seed, h.d), gm, (mode & DCM_PARAM_NO_GROUPING) != 0); }
-        if (leader >= 0) {
-            // The observation rows are built in LDS and leave as contiguous runs.  One lane per row writing its 5 or 6 floats
-            // straight to HBM is a 20/24-byte-strided store (24 partial cache lines per wave instruction, 12 instructions);
-            // staged, the same bytes are 6 fully coalesced instructions.  The staging area is the member-slot section of the
-            // record image (arrival rows + id words): the write-back above has already read it, observe() never does, and
-            // LDS operations of a wave execute in order -- so it costs no LDS (a separate 1.5 KB buffer would cost six
-            // resident workgroups per CU, which is why round 2 measured staging slower).
-            // Only for grids that fill the machine several times over (the HBM-bound regime: 165 -> 158 us at 65 536 envs);
-            // a single round of workgroups is latency-bound and the extra LDS round trip costs it 0.8 us of 24 (4096 envs).
-            const uint32_t need = 24u * (uint32_t)S.A() + 21u * ((uint32_t)S.T() + 1u) + 16u;
-            if (gridDim.x >= 8192u && L.tinfo() - L.marr() >= need) {
-                float* sag = (float*)(smem + L.marr());
-                float* stk = sag + 6 * S.A();
-                uint8_t* smk = (uint8_t*)(stk + 5 * (S.T() + 1));
-                S.observe(h, lane, leader, ag ? sag : nullptr, tk ? stk : nullptr, mk ? smk : nullptr, xy);
-                WSYNC();
-                if (ag) for (int i = lane; i < 6 * S.A(); i += WAVE) __builtin_nontemporal_store(sag[i], ag + i);
-                if (tk) for (int i = lane; i < 5 * (S.T() + 1); i += WAVE) __builtin_nontemporal_store(stk[i], tk + i);
-                if (mk) for (int i = lane; i <= S.T(); i += WAVE) __builtin_nontemporal_store(smk[i], mk + i);
-            } else {
-                S.observe(h, lane, leader, ag, tk, mk, xy);
-            }
-        } else {
-            S.write_inactive_obs(lane, ag, tk, mk);
-        }
-        if constexpr (RS || CA == 0) S.write_pad_obs(lane, BA, BT, ag, tk, mk);
-        if (lane == 0) {
-            if (leader_out) leader_out[e] = leader;
-            if (active_out) active_out[e] = leader >= 0 ? 1 : 0;
-        }
-        PHK_MARK(4);                               // next leader + observation stores (issue)
-    }
-    PHK_TOTAL(6);
-}
+// k_step and its renewing form k_rn_step: see k_step.inc
+#define DCM_RENEW 0
+#include "k_step.inc"
+#undef DCM_RENEW
+#define DCM_RENEW 1
+#include "k_step.inc"
+#undef DCM_RENEW
 
 // ================================================================================== the persistent rollout kernels' budget and error stop
 // Shared by k_rollout_random below and the register-resident k_rollout_fast, k_rollout_fast_mc and k_rollout_fast_g.
@@ -1613,90 +1475,13 @@ constexpr uint32_t rollout_random_lds_bytes(Lay L) {
 // 50A/200T instantiation wants 176 -- two waves per SIMD although its LDS image (10.9 KB with the member arrival times left in
 // the HBM record) would let twelve workgroups share a CU -- and with 168 (five spilled) it runs three: 8.65 -> 6.90 ms per
 // 8192-env launch.  Four (128 VGPRs, 47 spilled) measured slower again (7.15 ms).
-template <int CA, int CT, bool RS, int MC = M>
-__global__ __launch_bounds__(WAVE, 3) void k_rollout_random(int A, int T, int PA, int PT, KP P, unsigned char* state, int episodes,
-                                                        float* agents_out, float* tasks_out, uint8_t* mask_out,
-                                                        int64_t* steps_out, double* summary, uint16_t* ablog,
-                                                        const int32_t* sizes, int64_t budget_all, const int64_t* budget_in,
-                                                        unsigned char* gscr, double* retlog, int retcap) {
-    const int e = env_of_workgroup(), lane = threadIdx.x;
-    int eA, eT;
-    env_dims<CA, CT, RS>(sizes, e, A, T, eA, eT);
-    using SimT = Sim<CA, CT, RS, (CT > WAVE) && !RS, MC>;   // member arrival times in the HBM record (MG) for the exact multi-chunk shapes
-    SimT S{eA, eT, PA, PT, smem, nullptr};
-    using AMask = typename SimT::AMask;
-    const Lay L = S.L();
-    S.scr = SimT::SCR_IN_LDS ? smem + L.lds_rec() : gscr + (size_t)e * L.scratch_bytes();
-    const int BA = S.BA(A), BT = S.BT(T);
-    unsigned char* rec = state + (size_t)e * L.rec_bytes();
-    S.gm = (double*)(rec + L.marr());
-    typename SimT::XY xy;
-    S.template load_record<true, false>(rec, lane, xy);
-    S.set_ablog(ablog, e, BA, BT, lane);
-    S.set_retlog(retlog, retcap, e, lane);
-    if (lane == 0) S.inc_state()[1] = -1;  // incremental task_update: nothing is known about the last call of the previous launch
-    WSYNC();
-    HdrRegs h = load_hdr(smem);
-    float* ag = agents_out ? agents_out + (size_t)e * 6 * BA : nullptr;
-    float* tk = tasks_out ? tasks_out + (size_t)e * 5 * (BT + 1) : nullptr;
-    uint8_t* mk = mask_out ? mask_out + (size_t)e * (BT + 1) : nullptr;
-    if constexpr (RS || CA == 0) S.write_pad_obs(lane, BA, BT, ag, tk, mk);
-    // the usual call gives all three observation buffers: say so once, so that the per-decision null checks of observe() fold
-    // (wave-uniform branches otherwise, at every decision)
-    const bool all_obs = agents_out && tasks_out && mask_out;
-    double* row = summary + (size_t)e * 8;
-    const int left0 = rollout_budget(e, budget_all, budget_in);
-    int left = left0;
-    PH_DECL;
-    // key_1 = mix64(seed + GAMMA (d+1)): the argument is carried and advanced by GAMMA per decision (no 64-bit multiply,
-    // and neither seed nor d stay live in the loop: d = d0 + steps afterwards)
-    uint64_t gd = h.seed + GAMMA * (h.d + 1);
-    const uint64_t d0 = h.d;
-    for (int ep = 0; ep < episodes; ep++) {
-        if (h.flags & DCM_FLAG_DONE) {  // restart from the loaded instance; d keeps running
-            if (h.flags & ROLLOUT_ERR) break;
-            if (left == 0) break;       // budget spent at an episode boundary: the finished episode's results stay readable
-            S.reset_state(h, lane);
-            S.advance(h, P, lane, row PH_PASS);
-            PH_MARK(10);
-        }
-        // (the budget test rides on the loop's own scalar branch; testing it between observe and the action pick instead
-        //  splits the hot block and was measured 2.3 % slower)
-        while (!(h.flags & DCM_FLAG_DONE) && left != 0) {
-            AMask gm;
-            const uint64_t k1 = mix64(gd);   // (computing the next decision's key early, under the LDS latency of apply, measured
-                                             //  0.9 % SLOWER: two more live registers across the whole decision)
-            const int leader = S.pick_leader(h, lane, -1, k1, gm);
-            if (leader < 0) break;
-            PH_MARK(0);
-            if (all_obs) { __builtin_assume(ag != nullptr); __builtin_assume(tk != nullptr); __builtin_assume(mk != nullptr); S.observe(h, lane, leader, ag, tk, mk, xy); }
-            else S.observe(h, lane, leader, ag, tk, mk, xy);
-            PH_MARK(1);
-            const int action = S.pick_random_action(lane, k1);
-            PH_MARK(2);
-            S.template apply_and_advance<true>(h, P, lane, leader, gm, action, k1, -1, nullptr, row PH_PASS, RouteLog{nullptr, nullptr, nullptr, 0}, 0, false, 0, true, false, &xy);
-            gd += GAMMA;
-            left--;
-        }
-        if (left == 0) break;
-    }
-    PH_FLUSH(lane);
-    const int64_t steps = (int64_t)(left0 - left);
-    if (lane == 0 && steps_out) steps_out[e] = steps;
-    h.d = d0 + (uint64_t)steps;   // every decision of this kernel is valid, so apply_and_advance counted exactly `steps`
-    {   // Hdr::max_arrival: this kernel only takes valid actions, under which every arrival list is monotone, so the maximum of
-        // the agents' last arrivals IS the running maximum of the episode so far -- folded in once per launch for a later
-        // dcm_step on the same episode
-        double m = 0.0;
-        S.for_agents(lane, [&](int a) { const double av = (S.cur()[a] != -2) ? S.arr()[a] : 0.0; m = av > m ? av : m; });
-        const double wm = wave_nanmax(m);
-        if (lane == 0) { Hdr* q = (Hdr*)smem; if (wm > q->max_arrival) q->max_arrival = wm; }
-    }
-    WSYNC();
-    store_hdr(h, lane);
-    WSYNC();
-    S.store_record(rec, lane);
-}
+// k_rollout_random and its renewing form k_rn_rollout_random: see k_rollout_random.inc
+#define DCM_RENEW 0
+#include "k_rollout_random.inc"
+#undef DCM_RENEW
+#define DCM_RENEW 1
+#include "k_rollout_random.inc"
+#undef DCM_RENEW
 
 #include "rollout_fast.hpp"
 #include "step_fast.hpp"
@@ -1831,10 +1616,6 @@ __global__ void k_distance(const double* ax, const double* ay, const double* bx,
     if (time_out) time_out[i] = over_velocity(d);
 }
 
-#ifndef DCM_TU_G
-#include "instgen.hpp"
-#endif
-
 // ---------------------------------------------------------------------------------- host side
 // Which Sim<> instantiation and which kernels serve a handle is decided in plan.hpp; here its answers become template arguments.
 // The instantiations by their plan::SimKind: first the one-chunk layouts, which also have the register-resident kernels of
@@ -1866,11 +1647,21 @@ void launch_rollout(K kernel, dim3 grid, dim3 block, unsigned lds_bytes, hipStre
     hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, a.A, a.T, a.PA, a.PT, a.kp, a.state, a.episodes, a.agents_out, a.tasks_out,
                        a.mask_out, a.steps_out, a.summary, a.ablog, a.sizes, a.budget_all, a.budget_in, a.gscr, a.retlog, a.retcap);
 }
+// the same for the renewing form of a rollout kernel (k_rn_*)
+template <class K>
+void launch_rollout_rn(K kernel, dim3 grid, dim3 block, unsigned lds_bytes, hipStream_t stream, const RolloutArgs& a) {
+    hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, a.A, a.T, a.PA, a.PT, a.kp, a.state, a.episodes, a.agents_out, a.tasks_out,
+                       a.mask_out, a.steps_out, a.summary, a.ablog, a.sizes, a.budget_all, a.budget_in, a.gscr, a.retlog, a.retcap, a.rn);
+}
 }  // namespace
 
 #if defined(DCM_TU_G) || !defined(DCM_SPLIT_G)
 void dcm::launch_rollout_fast_g(int nac, int ntc, bool obs, unsigned grid, Lay L, hipStream_t stream, const RolloutArgs& a) {
-#define CALLG(NAC, NTC, OBS) launch_rollout(k_rollout_fast_g<NAC, NTC, OBS>, dim3(grid), dim3(WAVE), rollout_fast_g_lds_bytes(L), stream, a)
+#define CALLG(NAC, NTC, OBS)                                                                                                          \
+    do {                                                                                                                              \
+        if (a.rn.stride != 0) launch_rollout_rn(k_rn_rollout_fast_g<NAC, NTC, OBS>, dim3(grid), dim3(WAVE), rollout_fast_g_lds_bytes(L), stream, a); \
+        else launch_rollout(k_rollout_fast_g<NAC, NTC, OBS>, dim3(grid), dim3(WAVE), rollout_fast_g_lds_bytes(L), stream, a);        \
+    } while (0)
 #define CALLT(NAC, OBS) do { if (ntc > 3) { CALLG(NAC, 4, OBS); } else if (ntc > 2) { CALLG(NAC, 3, OBS); } else { CALLG(NAC, 2, OBS); } } while (0)
 #define CALLA(OBS) do { if (nac > 1) { CALLT(2, OBS); } else { CALLT(1, OBS); } } while (0)
     if (obs) { CALLA(true); } else { CALLA(false); }
@@ -1901,6 +1692,21 @@ bool stream_capturing(void* stream) {
     return hipStreamIsCapturing((hipStream_t)stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
 }
 
+// the last argument of the renewing kernel forms (k_rn_*), which are launched while the stride is not 0
+Renew renew_args(const dcm_env* env) { return Renew{env->inst_seeds, env->renew_stride, env->gen}; }
+// true while the stride is set, i.e. the launch about to be made is of a renewing form: it may replace instances, so the restart
+// image of k_step_fast (dcm_env::init, the records as dcm_reset saw them) is no longer theirs -- also after the stride is cleared.
+// Captured, the launch replaces instances at every replay, unseen by the host: the handle then counts as captured, which keeps
+// dcm_step from using an image for good
+bool renewing_launch(dcm_env* env, void* stream) {
+    if (env->renew_stride == 0) return false;
+    env->init_valid = false;
+    if (stream_capturing(stream)) env->captured = true;
+    return true;
+}
+// the handle's instances no longer come from dcm_generate_instances, or come from a new call of it: renewal is off
+void renewal_off(dcm_env* env, bool generated) { env->generated = generated; env->renew_stride = 0; }
+
 // the common tail of dcm_load_instances / dcm_load_instances_ragged (env->sizes: the per-env sizes of a ragged batch, or nullptr)
 int launch_load(dcm_env* env, const double* depot, const double* task_xy, const int32_t* req, const double* dur, void* stream) {
     hipLaunchKernelGGL(k_load_instances, GRID(env), 0, (hipStream_t)stream, DIMS(env), env->L.C, env->state, depot, task_xy,
@@ -1908,6 +1714,7 @@ int launch_load(dcm_env* env, const double* depot, const double* task_xy, const 
     LAUNCH_OK();
     env->loaded = true;
     env->reset_done = false;
+    renewal_off(env, false);
     return DCM_OK;
 }
 
@@ -1995,7 +1802,9 @@ int dcm_create(const dcm_params* params, dcm_env** out) {
     allow_lds(k_reset<CA, CT, RS, ##__VA_ARGS__>, lds);        \
     allow_lds(k_observe<CA, CT, RS, ##__VA_ARGS__>, lds);      \
     allow_lds(k_step<CA, CT, RS, ##__VA_ARGS__>, lds);         \
-    allow_lds(k_rollout_random<CA, CT, RS, ##__VA_ARGS__>, lds);
+    allow_lds(k_rollout_random<CA, CT, RS, ##__VA_ARGS__>, lds);  \
+    allow_lds(k_rn_step<CA, CT, RS, ##__VA_ARGS__>, lds);      \
+    allow_lds(k_rn_rollout_random<CA, CT, RS, ##__VA_ARGS__>, lds);
     FOR_EACH_INSTANCE(SET_ATTR)
 #undef SET_ATTR
 #define SET_FAST(KIND, CA, CT, RS)                             \
@@ -2003,11 +1812,18 @@ int dcm_create(const dcm_params* params, dcm_env** out) {
     allow_lds(k_rollout_fast<CA, CT, RS, false>, lds);         \
     allow_lds(k_rollout_fast<CA, CT, RS, true, true>, lds);    \
     allow_lds(k_rollout_fast<CA, CT, RS, false, true>, lds);   \
-    allow_lds(k_step_fast<CA, CT, RS>, lds);
+    allow_lds(k_step_fast<CA, CT, RS>, lds);                   \
+    allow_lds(k_rn_rollout_fast<CA, CT, RS, true>, lds);       \
+    allow_lds(k_rn_rollout_fast<CA, CT, RS, false>, lds);      \
+    allow_lds(k_rn_rollout_fast<CA, CT, RS, true, true>, lds); \
+    allow_lds(k_rn_rollout_fast<CA, CT, RS, false, true>, lds); \
+    allow_lds(k_rn_step_fast<CA, CT, RS>, lds);
     FOR_EACH_FAST(SET_FAST)
 #undef SET_FAST
     allow_lds(k_rollout_fast_mc<50, 200, true>, lds);
     allow_lds(k_rollout_fast_mc<50, 200, false>, lds);
+    allow_lds(k_rn_rollout_fast_mc<50, 200, true>, lds);
+    allow_lds(k_rn_rollout_fast_mc<50, 200, false>, lds);
     allow_lds(k_get_tasks<M>, lds);
     allow_lds(k_get_agents<M>, lds);
     allow_lds(k_get_tasks<MW>, lds);
@@ -2019,7 +1835,7 @@ int dcm_destroy(dcm_env* env) {
     if (!env) return DCM_OK;
     DeviceGuard guard(env->p.device);
     void* const owned[] = {env->state, env->summary, env->ablog, env->gscratch, env->routes, env->route_len,
-                           env->rmarr, env->sizes, env->side, env->pendq, env->init};
+                           env->rmarr, env->sizes, env->side, env->pendq, env->init, env->inst_seeds};
     for (void* p : owned)
         if (p) (void)hipFree(p);
     delete env;
@@ -2066,15 +1882,23 @@ int dcm_generate_instances(dcm_env* env, const uint64_t* inst_seeds, int32_t age
         return fail(DCM_ERR_INVALID, "dcm_generate_instances: need 1 <= max_coalition_size <= the member slots of the handle");
     if (!(max_duration >= 0.0)) return fail(DCM_ERR_INVALID, "dcm_generate_instances: need max_duration >= 0");
     DCM_TRY(dcm::drop_pending(env, stream));
+    // renewal is off before the sizes or the kept seeds change: a failure below cannot leave it on with seeds that are not the records'
+    renewal_off(env, false);
     const bool uniform = agents_lo == env->A && tasks_lo == env->T;    // (lo <= hi <= the dim: both ranges zero-width at the dims)
     if (uniform && env->sizes) { HIP_TRY(hipFree(env->sizes)); env->sizes = nullptr; }
     if (!uniform && !env->sizes) HIP_TRY(hipMalloc((void**)&env->sizes, (size_t)2 * env->p.n_envs * sizeof(int32_t)));
+    // the handle keeps the seeds and the scalar arguments: what a renewal draws the env's later instances from
+    const size_t seed_bytes = (size_t)env->p.n_envs * sizeof(uint64_t);
+    if (!env->inst_seeds) HIP_TRY(hipMalloc((void**)&env->inst_seeds, seed_bytes));
+    HIP_TRY(hipMemcpyAsync(env->inst_seeds, inst_seeds, seed_bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
     const GenArgs g{agents_lo, agents_hi, tasks_lo, tasks_hi, max_coalition_size, max_duration};
     hipLaunchKernelGGL(k_generate_instances, GRID(env), 0, (hipStream_t)stream, env->L.A, env->L.T, env->L.C, env->state, inst_seeds, g,
                        env->sizes);
     LAUNCH_OK();
     env->loaded = true;
     env->reset_done = false;
+    env->gen = g;
+    renewal_off(env, true);
     return DCM_OK;
 }
 
@@ -2084,6 +1908,25 @@ int dcm_get_instances(dcm_env* env, double* depot, double* task_xy, int32_t* req
     if (!env->loaded) return fail(DCM_ERR_STATE, "dcm_get_instances: no instances loaded");
     hipLaunchKernelGGL(k_get_instances, GRID(env), 0, (hipStream_t)stream, DIMS(env), env->L.C, (const unsigned char*)env->state,
                        (const int32_t*)env->sizes, depot, task_xy, req, dur, n_agents, n_tasks);
+    LAUNCH_OK();
+    return DCM_OK;
+}
+
+int dcm_set_instance_renewal(dcm_env* env, uint64_t stride) {
+    CHECK_HANDLE(env);
+    if (stride != 0 && !plan::renewal_ok(shape_of(env), env->loaded && env->generated))
+        return fail(DCM_ERR_STATE, "dcm_set_instance_renewal: needs a uniform batch made by dcm_generate_instances");
+    env->renew_stride = stride;
+    return DCM_OK;
+}
+
+int dcm_instance_index(dcm_env* env, uint32_t* index_out, void* stream) {
+    CHECK_ENV(env);
+    if (!index_out) return fail(DCM_ERR_INVALID, "dcm_instance_index: null index_out");
+    if (!env->loaded) return fail(DCM_ERR_STATE, "dcm_instance_index: no instances loaded");
+    const int B = env->p.n_envs;
+    hipLaunchKernelGGL(k_instance_index, dim3((B + WAVE - 1) / WAVE), dim3(WAVE), 0, (hipStream_t)stream, env->L.A, env->L.T, env->L.C,
+                       (const unsigned char*)env->state, B, index_out);
     LAUNCH_OK();
     return DCM_OK;
 }
@@ -2222,14 +2065,21 @@ int dcm_step(dcm_env* env, const int32_t* actions, const int32_t* leader_in, con
                 pendq = env->pendq;
             }
         }
-#define CALL(CA, CT, RS)                                                                                             \
-    hipLaunchKernelGGL((k_step_fast<CA, CT, RS>), GRID(env), (step_fast_lds_bytes<CA, CT, RS>(env->L)),                \
-                       (hipStream_t)stream, DIMS(env), env->kp,                                                            \
-                       env->state, actions, agents_out, tasks_out, mask_out, leader_out, active_out, env->summary, env->ablog,  \
+        const bool renew = renewing_launch(env, stream);
+        const unsigned char* const image = plan::step_restart_image(env->init_valid, pendq != nullptr, renew) ? env->init : nullptr;
+        const Renew rn = renew_args(env);
+#define STEP_FAST_ARGS DIMS(env), env->kp, env->state, actions, agents_out, tasks_out, mask_out, leader_out, active_out, env->summary, env->ablog,  \
                        env->p.flags, (const int32_t*)env->sizes, env->gscratch, env->p.auto_reset_episodes, env->retlog, (int)env->retcap, \
-                       env->side, env->side_pitch, pendq, (pendq && env->init_valid) ? (const unsigned char*)env->init : nullptr)
+                       env->side, env->side_pitch, pendq, image
+#define CALL(CA, CT, RS)                                                                             \
+    do {                                                                                             \
+        const unsigned lds = step_fast_lds_bytes<CA, CT, RS>(env->L);                                \
+        if (renew) hipLaunchKernelGGL((k_rn_step_fast<CA, CT, RS>), GRID(env), lds, (hipStream_t)stream, STEP_FAST_ARGS, rn); \
+        else hipLaunchKernelGGL((k_step_fast<CA, CT, RS>), GRID(env), lds, (hipStream_t)stream, STEP_FAST_ARGS); \
+    } while (0)
         DISPATCH_ONE_CHUNK(env);
 #undef CALL
+#undef STEP_FAST_ARGS
         LAUNCH_OK();
         if (pendq) {
             env->maybe_pending = true;
@@ -2238,13 +2088,20 @@ int dcm_step(dcm_env* env, const int32_t* actions, const int32_t* leader_in, con
         return DCM_OK;
     }
     DCM_TRY(dcm::flush_pending(env, stream));    // (the general kernel writes summary rows itself)
-#define CALL(CA, CT, RS, ...)                                                                                        \
-    hipLaunchKernelGGL((k_step<CA, CT, RS, ##__VA_ARGS__>), GRID(env), (env_kernel_lds_bytes<CA, CT, RS>(env->L)), (hipStream_t)stream, DIMS(env), env->kp,   \
-                       env->state, actions, leader_in, nfol_in, followers_in, agents_out, tasks_out, mask_out, leader_out, \
-                       active_out, env->summary, env->log, env->ablog, env->p.flags, (const int32_t*)env->sizes, env->gscratch, \
-                       env->p.auto_reset_episodes, env->retlog, (int)env->retcap)
+    const bool renew = renewing_launch(env, stream);
+    const Renew rn = renew_args(env);
+#define STEP_ARGS DIMS(env), env->kp, env->state, actions, leader_in, nfol_in, followers_in, agents_out, tasks_out, mask_out, leader_out, \
+                  active_out, env->summary, env->log, env->ablog, env->p.flags, (const int32_t*)env->sizes, env->gscratch, \
+                  env->p.auto_reset_episodes, env->retlog, (int)env->retcap
+#define CALL(CA, CT, RS, ...)                                                                        \
+    do {                                                                                             \
+        const unsigned lds = env_kernel_lds_bytes<CA, CT, RS>(env->L);                               \
+        if (renew) hipLaunchKernelGGL((k_rn_step<CA, CT, RS, ##__VA_ARGS__>), GRID(env), lds, (hipStream_t)stream, STEP_ARGS, rn); \
+        else hipLaunchKernelGGL((k_step<CA, CT, RS, ##__VA_ARGS__>), GRID(env), lds, (hipStream_t)stream, STEP_ARGS); \
+    } while (0)
     DISPATCH_ENV(env);
 #undef CALL
+#undef STEP_ARGS
     LAUNCH_OK();
     return DCM_OK;
 }
@@ -2257,13 +2114,18 @@ int dcm_rollout_random(dcm_env* env, int32_t episodes, int64_t max_decisions, co
     DCM_TRY(dcm::flush_pending(env, stream));
     const dcm::RolloutArgs ra{DIMS(env), env->kp, env->state, (int)episodes, agents_out, tasks_out, mask_out, steps_out, env->summary,
                               env->ablog, (const int32_t*)env->sizes, max_decisions, max_decisions_in, env->gscratch, env->retlog,
-                              (int)env->retcap};
+                              (int)env->retcap, renew_args(env)};
     // The register-resident kernels have the same contract and the same results as the general one (tests/test_gpu_rollout.py runs both)
     const bool all_obs = agents_out && tasks_out && mask_out, no_obs = !agents_out && !tasks_out && !mask_out;
+    // the renewing form of whichever kernel serves the handle, while a stride is set (dcm_set_instance_renewal)
+    const bool renew = renewing_launch(env, stream);
     switch (plan::rollout_kind(shape_of(env), all_obs || no_obs)) {
     case plan::Rollout::Fast: {
-#define CALLF(CA, CT, RS, OBS, PRIO) \
-    launch_rollout(k_rollout_fast<CA, CT, RS, OBS, PRIO>, GRID(env), rollout_fast_lds_bytes<CA, CT, RS>(env->L), (hipStream_t)stream, ra)
+#define CALLF(CA, CT, RS, OBS, PRIO)                                                                                                          \
+    do {                                                                                                                                          \
+        if (renew) launch_rollout_rn(k_rn_rollout_fast<CA, CT, RS, OBS, PRIO>, GRID(env), rollout_fast_lds_bytes<CA, CT, RS>(env->L), (hipStream_t)stream, ra); \
+        else launch_rollout(k_rollout_fast<CA, CT, RS, OBS, PRIO>, GRID(env), rollout_fast_lds_bytes<CA, CT, RS>(env->L), (hipStream_t)stream, ra);  \
+    } while (0)
         // wave priorities (k_rollout_fast, PRIO) for a launch that fills the machine by itself: 16 workgroups x 256 CUs
         const bool prio = env->p.n_envs >= 4096;
 #define CALL(CA, CT, RS) do { if (prio) { if (all_obs) { CALLF(CA, CT, RS, true, true); } else { CALLF(CA, CT, RS, false, true); } }   \
@@ -2274,16 +2136,24 @@ int dcm_rollout_random(dcm_env* env, int32_t episodes, int64_t max_decisions, co
         break;
     }
     case plan::Rollout::FastMc:
-        if (all_obs) launch_rollout(k_rollout_fast_mc<50, 200, true>, GRID(env), FastM<50, 200, true>::LDS_BYTES, (hipStream_t)stream, ra);
-        else launch_rollout(k_rollout_fast_mc<50, 200, false>, GRID(env), FastM<50, 200, false>::LDS_BYTES, (hipStream_t)stream, ra);
+#define CALLM(OBS)                                                                                                                      \
+    do {                                                                                                                                \
+        if (renew) launch_rollout_rn(k_rn_rollout_fast_mc<50, 200, OBS>, GRID(env), FastM<50, 200, OBS>::LDS_BYTES, (hipStream_t)stream, ra); \
+        else launch_rollout(k_rollout_fast_mc<50, 200, OBS>, GRID(env), FastM<50, 200, OBS>::LDS_BYTES, (hipStream_t)stream, ra);       \
+    } while (0)
+        if (all_obs) { CALLM(true); } else { CALLM(false); }
+#undef CALLM
         break;
     case plan::Rollout::FastG:
         dcm::launch_rollout_fast_g(plan::fast_g_agent_chunks(env->A), plan::fast_g_task_chunks(env->T), all_obs, (unsigned)env->p.n_envs,
                                    env->L, (hipStream_t)stream, ra);
         break;
     case plan::Rollout::General:
-#define CALL(CA, CT, RS, ...) \
-    launch_rollout(k_rollout_random<CA, CT, RS, ##__VA_ARGS__>, GRID(env), rollout_random_lds_bytes<CA, CT, RS>(env->L), (hipStream_t)stream, ra)
+#define CALL(CA, CT, RS, ...)                                                                                                                    \
+    do {                                                                                                                                         \
+        if (renew) launch_rollout_rn(k_rn_rollout_random<CA, CT, RS, ##__VA_ARGS__>, GRID(env), rollout_random_lds_bytes<CA, CT, RS>(env->L), (hipStream_t)stream, ra); \
+        else launch_rollout(k_rollout_random<CA, CT, RS, ##__VA_ARGS__>, GRID(env), rollout_random_lds_bytes<CA, CT, RS>(env->L), (hipStream_t)stream, ra); \
+    } while (0)
         DISPATCH_ENV(env);
 #undef CALL
         break;

@@ -13,7 +13,11 @@
 // size left behind -- and Lemire's method rejects a word now and then (at most 15 in 2^32 at max_coalition_size <= 16), which shifts
 // every later position.  wave_bounded therefore takes 128 words at a time on the assumption that none is rejected, and when one
 // is, the whole wave falls back to the sequential routine of np_stream.hpp from the start of that block on.
-#pragma once   // (inside dcmrta_env.hip's unnamed namespace: np_stream.hpp is included at the top of that file)
+//
+// Instance renewal (dcm_set_instance_renewal): the kernels that restart episodes -- the renewing forms (k_rn_*: see k_step.inc) of k_step, k_step_fast and
+// the four persistent rollout kernels -- call wave_renew_instance right before reset_state, so that every episode runs on a fresh
+// instance the way every reference Worker builds a fresh TaskEnv (worker.py:32).
+#pragma once   // (inside dcmrta_env.hip's unnamed namespace, in front of its kernels: np_stream.hpp is included at the top of that file)
 
 // n doubles of Generator.random from the wave-uniform stream p: put(j, value) is called by the lane that owns draw j.
 // lane_j = nps::jump_coeffs(lane + 1).  p is left behind the last of them.
@@ -73,16 +77,12 @@ __device__ __forceinline__ void wave_bounded(nps::Pcg& p, const nps::Jump& lane_
     }
 }
 
-// The scalar arguments of generate_env
-struct GenArgs {
-    int32_t a_lo, a_hi, t_lo, t_hi;   // agents_range, tasks_range (lo == hi: an int, or a tuple that draws nothing)
-    int32_t max_coalition_size;
-    double max_duration;
-};
-
 // generate_env for one env by one wave, written where k_load_instances puts it: the instance sections tx / ty / tdur, the
 // requirement in tinfo, the depot and the initial fields of the header.  The pointers may be into a record in HBM or its LDS image.
 // Rows beyond the env's own sizes are not touched.  (eA, eT) = the sizes it drew, wave-uniform.
+// INSTANCE_ONLY: of the header only the depot is written -- the form for a LIVE header (wave_renew_instance), whose flags, episode
+// count, decision counter and seed must survive.
+template <bool INSTANCE_ONLY = false>
 __device__ __forceinline__ void wave_generate_instance(uint64_t seed, const GenArgs& g, const nps::Jump& lane_j, int lane, Hdr* h,
                                                        double* tx, double* ty, double* td, uint32_t* ti, int& eA, int& eT) {
     nps::Pcg p = nps::pcg_seed(seed);
@@ -96,11 +96,71 @@ __device__ __forceinline__ void wave_generate_instance(uint64_t seed, const GenA
     });
     const double dur = g.max_duration;
     wave_bounded(p, lane_j, (uint32_t)(g.max_coalition_size - 1), eT, lane, [&](int t, uint32_t v) { ti[t] = 1u + v; td[t] = dur; });
-    if (lane == 0) {
-        h->flags = DCM_FLAG_DONE; h->episodes = 0; h->d = 0; h->seed = 0;
-        h->groups = 0; h->reserved = 0; h->max_arrival = 0.0;
+    if constexpr (!INSTANCE_ONLY) {
+        if (lane == 0) {
+            h->flags = DCM_FLAG_DONE; h->episodes = 0; h->d = 0; h->seed = 0;
+            h->groups = 0; h->reserved = 0; h->max_arrival = 0.0;
+        }
     }
 }
+
+// Instance renewal at an episode restart: env e's instance n + 1 (n = Hdr::reserved of the live header, the env's instance index)
+// replaces instance n, and the index moves on.  S.base is the kernel's LDS image with the live header, rec the env's HBM record.
+// The image does not always hold the instance -- the exact multi-chunk shapes keep task x / y in the XY registers, the
+// register-resident kernels hold x / y / duration per lane -- and a write-back of the mutable part alone must leave the record with
+// the new instance.  So the instance goes straight into the record's instance sections and requirement words, the depot and the
+// index into the live header, and then the wave reloads what the kernel keeps: the instance part of the image (requirement words,
+// durations, x / y where the image has them) and xy.  The caller runs reset_state next -- it expands the requirement words and reads
+// the depot -- and then reloads its own per-lane constants (load_consts).
+// The wave re-reads its own global stores, made by other lanes than those that read: the loads are agent-scope (past the CU's vector
+// L1, whose lines may date from the record copy at the head of the launch) and follow a release fence that waits for the stores,
+// the order step_fast.hpp keeps for its abandonment rows.
+template <class SimT>
+__device__ __forceinline__ void wave_renew_instance(const SimT& S, unsigned char* rec, const Renew& rn, int e, int lane,
+                                                    typename SimT::XY& xy) {
+    const Lay L = S.L();
+    Hdr* const live = (Hdr*)S.base;
+    const uint32_t n = uni(live->reserved) + 1u;
+    const uint64_t seed = uni(rn.seeds[e]) + (uint64_t)n * rn.stride;
+    const nps::Jump lane_j = nps::jump_coeffs((uint64_t)lane + 1);
+    unsigned long long* const gx = (unsigned long long*)(rec + L.tx());
+    unsigned long long* const gy = (unsigned long long*)(rec + L.ty());
+    unsigned long long* const gd = (unsigned long long*)(rec + L.tdur());
+    uint32_t* const gi = (uint32_t*)(rec + L.tinfo());
+    int eA, eT;                                                      // (the batch is uniform: the handle's dims)
+    wave_generate_instance<true>(seed, rn.g, lane_j, lane, live, (double*)gx, (double*)gy, (double*)gd, gi, eA, eT);
+    if (lane == 0) live->reserved = n;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+    auto gload = [](const unsigned long long* q) {
+        return __longlong_as_double((long long)__hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    };
+    S.for_tasks(lane, [&](int t) {
+        S.tinfo()[t] = __hip_atomic_load(gi + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        S.tdur()[t] = gload(gd + t);
+        if constexpr (!SimT::IRB) { S.tx()[t] = gload(gx + t); S.ty()[t] = gload(gy + t); }
+    });
+    if constexpr (SimT::IRB) {
+#pragma unroll
+        for (int c = 0; c < SimT::NTC; c++) {
+            const int t = c * WAVE + lane < S.T() ? c * WAVE + lane : 0;
+            xy.x[c] = gload(gx + t);
+            xy.y[c] = gload(gy + t);
+        }
+    }
+    WSYNC();
+}
+
+// The same out of line, for the persistent rollout kernels: it runs once per episode, and inlined its 128-bit multiplies cost their
+// decision loops up to nineteen VGPRs (k_rn_rollout_random<20,50, runtime sizes>: 129, three waves per SIMD instead of four; the
+// register-resident kernels spilled).  The lockstep kernels inline it: a callee's registers count as the caller's, and the general
+// k_step, which runs seven waves per SIMD on 68 VGPRs, would run five.
+template <class SimT>
+__device__ __noinline__ void wave_renew_instance_call(const SimT& S, unsigned char* rec, const Renew& rn, int e, int lane,
+                                                      typename SimT::XY& xy) {
+    wave_renew_instance(S, rec, rn, e, lane, xy);
+}
+
+#ifndef DCM_TU_G   // (the unit of k_rollout_fast_g needs the routines above only)
 
 // dcm_generate_instances: sizes = the handle's per-env sizes [B][2] on a ragged batch, else nullptr
 __global__ __launch_bounds__(WAVE) void k_generate_instances(int PA, int PT, int PC, unsigned char* state, const uint64_t* seeds, GenArgs g,
@@ -142,6 +202,14 @@ __global__ __launch_bounds__(WAVE) void k_get_instances(int A, int T, int PA, in
     }
 }
 
+// dcm_instance_index: Hdr::reserved of every env (layout dims: only the record pitch matters)
+__global__ __launch_bounds__(WAVE) void k_instance_index(int PA, int PT, int PC, const unsigned char* state, int B, uint32_t* index_out) {
+    const int e = blockIdx.x * WAVE + threadIdx.x;
+    if (e >= B) return;
+    const Lay L{PA, PT, PC};
+    index_out[e] = ((const Hdr*)(state + (size_t)e * L.rec_bytes()))->reserved;
+}
+
 // dcm_generator_draws: per seed the first n_doubles of Generator.random, then n_ints of Generator.integers(0, rng + 1), through the
 // routines the instance kernel uses
 __global__ __launch_bounds__(WAVE) void k_generator_draws(const uint64_t* seeds, int n_doubles, uint32_t rng, int n_ints, double* doubles_out,
@@ -152,3 +220,4 @@ __global__ __launch_bounds__(WAVE) void k_generator_draws(const uint64_t* seeds,
     wave_doubles(p, lane_j, n_doubles, lane, [&](int j, double v) { doubles_out[(size_t)e * n_doubles + j] = v; });
     wave_bounded(p, lane_j, rng, n_ints, lane, [&](int i, uint32_t v) { ints_out[(size_t)e * n_ints + i] = v; });
 }
+#endif   // DCM_TU_G

@@ -1,0 +1,100 @@
+// k_rollout_random.inc -- the kernel k_rollout_random, compiled twice by dcmrta_env.hip: as k_rollout_random (DCM_RENEW 0) and as its renewing form k_rn_rollout_random
+// (DCM_RENEW 1), which has one more argument, Renew rn, and is launched while dcm_set_instance_renewal has set a stride: an env that
+// restarts an episode first replaces its instance (wave_renew_instance, instgen.hpp).  Two kernels from one text: the plain
+// form holds nothing of the renewal and compiles to the code it had without it (DESIGN 6).
+#if DCM_RENEW
+#define KNAME k_rn_rollout_random
+#define KRENEW_PARAM , Renew rn
+#else
+#define KNAME k_rollout_random
+#define KRENEW_PARAM
+#endif
+template <int CA, int CT, bool RS, int MC = M>
+__global__ __launch_bounds__(WAVE, 3) void KNAME(int A, int T, int PA, int PT, KP P, unsigned char* state, int episodes,
+                                                        float* agents_out, float* tasks_out, uint8_t* mask_out,
+                                                        int64_t* steps_out, double* summary, uint16_t* ablog,
+                                                        const int32_t* sizes, int64_t budget_all, const int64_t* budget_in,
+                                                        unsigned char* gscr, double* retlog, int retcap KRENEW_PARAM) {
+    const int e = env_of_workgroup(), lane = threadIdx.x;
+    int eA, eT;
+    env_dims<CA, CT, RS>(sizes, e, A, T, eA, eT);
+    using SimT = Sim<CA, CT, RS, (CT > WAVE) && !RS, MC>;   // member arrival times in the HBM record (MG) for the exact multi-chunk shapes
+    SimT S{eA, eT, PA, PT, smem, nullptr};
+    using AMask = typename SimT::AMask;
+    const Lay L = S.L();
+    S.scr = SimT::SCR_IN_LDS ? smem + L.lds_rec() : gscr + (size_t)e * L.scratch_bytes();
+    const int BA = S.BA(A), BT = S.BT(T);
+    unsigned char* rec = state + (size_t)e * L.rec_bytes();
+    S.gm = (double*)(rec + L.marr());
+    typename SimT::XY xy;
+    S.template load_record<true, false>(rec, lane, xy);
+    S.set_ablog(ablog, e, BA, BT, lane);
+    S.set_retlog(retlog, retcap, e, lane);
+    if (lane == 0) S.inc_state()[1] = -1;  // incremental task_update: nothing is known about the last call of the previous launch
+    WSYNC();
+    HdrRegs h = load_hdr(smem);
+    float* ag = agents_out ? agents_out + (size_t)e * 6 * BA : nullptr;
+    float* tk = tasks_out ? tasks_out + (size_t)e * 5 * (BT + 1) : nullptr;
+    uint8_t* mk = mask_out ? mask_out + (size_t)e * (BT + 1) : nullptr;
+    if constexpr (RS || CA == 0) S.write_pad_obs(lane, BA, BT, ag, tk, mk);
+    // the usual call gives all three observation buffers: say so once, so that the per-decision null checks of observe() fold
+    // (wave-uniform branches otherwise, at every decision)
+    const bool all_obs = agents_out && tasks_out && mask_out;
+    double* row = summary + (size_t)e * 8;
+    const int left0 = rollout_budget(e, budget_all, budget_in);
+    int left = left0;
+    PH_DECL;
+    // key_1 = mix64(seed + GAMMA (d+1)): the argument is carried and advanced by GAMMA per decision (no 64-bit multiply,
+    // and neither seed nor d stay live in the loop: d = d0 + steps afterwards)
+    uint64_t gd = h.seed + GAMMA * (h.d + 1);
+    const uint64_t d0 = h.d;
+    for (int ep = 0; ep < episodes; ep++) {
+        if (h.flags & DCM_FLAG_DONE) {  // restart from the loaded instance; d keeps running
+            if (h.flags & ROLLOUT_ERR) break;
+            if (left == 0) break;       // budget spent at an episode boundary: the finished episode's results stay readable
+#if DCM_RENEW
+            wave_renew_instance_call(S, rec, rn, e, lane, xy);
+#endif
+            S.reset_state(h, lane);
+            S.advance(h, P, lane, row PH_PASS);
+            PH_MARK(10);
+        }
+        // (the budget test rides on the loop's own scalar branch; testing it between observe and the action pick instead
+        //  splits the hot block and was measured 2.3 % slower)
+        while (!(h.flags & DCM_FLAG_DONE) && left != 0) {
+            AMask gm;
+            const uint64_t k1 = mix64(gd);   // (computing the next decision's key early, under the LDS latency of apply, measured
+                                             //  0.9 % SLOWER: two more live registers across the whole decision)
+            const int leader = S.pick_leader(h, lane, -1, k1, gm);
+            if (leader < 0) break;
+            PH_MARK(0);
+            if (all_obs) { __builtin_assume(ag != nullptr); __builtin_assume(tk != nullptr); __builtin_assume(mk != nullptr); S.observe(h, lane, leader, ag, tk, mk, xy); }
+            else S.observe(h, lane, leader, ag, tk, mk, xy);
+            PH_MARK(1);
+            const int action = S.pick_random_action(lane, k1);
+            PH_MARK(2);
+            S.template apply_and_advance<true>(h, P, lane, leader, gm, action, k1, -1, nullptr, row PH_PASS, RouteLog{nullptr, nullptr, nullptr, 0}, 0, false, 0, true, false, &xy);
+            gd += GAMMA;
+            left--;
+        }
+        if (left == 0) break;
+    }
+    PH_FLUSH(lane);
+    const int64_t steps = (int64_t)(left0 - left);
+    if (lane == 0 && steps_out) steps_out[e] = steps;
+    h.d = d0 + (uint64_t)steps;   // every decision of this kernel is valid, so apply_and_advance counted exactly `steps`
+    {   // Hdr::max_arrival: this kernel only takes valid actions, under which every arrival list is monotone, so the maximum of
+        // the agents' last arrivals IS the running maximum of the episode so far -- folded in once per launch for a later
+        // dcm_step on the same episode
+        double m = 0.0;
+        S.for_agents(lane, [&](int a) { const double av = (S.cur()[a] != -2) ? S.arr()[a] : 0.0; m = av > m ? av : m; });
+        const double wm = wave_nanmax(m);
+        if (lane == 0) { Hdr* q = (Hdr*)smem; if (wm > q->max_arrival) q->max_arrival = wm; }
+    }
+    WSYNC();
+    store_hdr(h, lane);
+    WSYNC();
+    S.store_record(rec, lane);
+}
+#undef KNAME
+#undef KRENEW_PARAM

@@ -46,6 +46,15 @@ inline SimKind sim_kind(const Shape& s) {
 // with lane 63 free for the depot; sim_kind is then one of the first three.  (dcm_step adds its call-shape conditions.)
 inline bool one_chunk_ok(const Shape& s) { return s.quiet && !s.wide && s.A <= LANES && s.T <= LANES - 1; }
 
+// Instance renewal (dcm_set_instance_renewal with a non-zero stride): the handle's instances must have come from
+// dcm_generate_instances (`generated`: the handle then holds the seeds and scalar arguments the next instances are drawn from), and the
+// batch must be uniform -- on a ragged one an env's sizes would change inside a launch, which the kernels do not do.
+inline bool renewal_ok(const Shape& s, bool generated) { return generated && !s.ragged; }
+// k_step_fast restarts an auto-resetting env from a copy of the record dcm_reset left (dcm_env::init) when it has one and the terminal
+// metrics are deferred.  The copy describes the instance dcm_reset saw: with renewal on the kernel gets none and computes the
+// restart (reset_state + the first event) on the new instance.
+inline bool step_restart_image(bool image_valid, bool deferred_terminal, bool renewal) { return image_valid && deferred_terminal && !renewal; }
+
 // dcm_rollout_random.  obs_all_or_none: all three observation buffers given, or none (a template argument of the fast kernels)
 enum class Rollout { Fast, FastMc, FastG, General };
 inline Rollout rollout_kind(const Shape& s, bool obs_all_or_none) {

@@ -487,139 +487,10 @@ constexpr uint32_t rollout_fast_lds_bytes(Lay L) {
 
 // Same contract as k_rollout_random (see there); OBS: all three observation buffers given / none of them.
 // PRIO: wave priorities, longest remaining work first (see the main loop) -- the host picks it for launches that fill the machine alone
-template <int CA, int CT, bool RS, bool OBS, bool PRIO = false>
-__global__ __launch_bounds__(WAVE, 4) void k_rollout_fast(int A, int T, int PA, int PT, KP P, unsigned char* state, int episodes,
-                                                      float* agents_out, float* tasks_out, uint8_t* mask_out,
-                                                      int64_t* steps_out, double* summary, uint16_t* ablog,
-                                                      const int32_t* sizes, int64_t budget_all, const int64_t* budget_in,
-                                                      unsigned char* gscr, double* retlog, int retcap) {
-    const int e = env_of_workgroup(), lane = threadIdx.x;
-    int eA, eT;
-    env_dims<CA, CT, RS>(sizes, e, A, T, eA, eT);
-    using F = Fast<CA, CT, RS, OBS>;
-    using SimT = typename F::SimT;
-    SimT S{eA, eT, PA, PT, smem, nullptr};
-    const Lay L = S.L();
-    S.scr = SimT::SCR_IN_LDS ? smem + L.lds_rec() : gscr + (size_t)e * L.scratch_bytes();
-    const int BA = S.BA(A), BT = S.BT(T);
-    unsigned char* rec = state + (size_t)e * L.rec_bytes();
-    typename SimT::XY xy;
-    S.template load_record<true, false>(rec, lane, xy);
-    S.set_ablog(ablog, e, BA, BT, lane);
-    S.set_retlog(retlog, retcap, e, lane);
-    WSYNC();
-    HdrRegs h = load_hdr(smem);
-    // (the launch asks for 512 bytes of LDS behind everything the general code uses: the dummy slots)
-    F f{S, (double*)(smem + (SimT::SCR_IN_LDS ? L.lds_bytes() : SimT::lds_image_bytes(L)))};
-    f.init(lane);
-    float* agrow = nullptr; float* tkrow = nullptr; uint8_t* mkp = nullptr;
-    if constexpr (OBS) {
-        float* ag = agents_out + (size_t)e * 6 * BA;
-        float* tk = tasks_out + (size_t)e * 5 * (BT + 1);
-        uint8_t* mk = mask_out + (size_t)e * (BT + 1);
-        if constexpr (RS) S.write_pad_obs(lane, BA, BT, ag, tk, mk);
-        agrow = ag + 6 * f.la;
-        tkrow = tk + (f.inT ? 5 * (lane + 1) : 0);
-        mkp = mk + (f.inT ? lane + 1 : 0);
-    }
-    double* row = summary + (size_t)e * 8;
-    const int left0 = rollout_budget(e, budget_all, budget_in);
-    int left = left0;
-    uint64_t gd = h.seed + GAMMA * (h.d + 1);
-    // the choice-protocol keys of the next 64 decisions, one per lane (25 VALU instructions per 64 decisions instead of a dependent
-    // chain of 20 scalar ones at the head of every decision); ki = the lane that holds the current decision's key
-    uint64_t kv = mix64(gd + GAMMA * (uint64_t)lane);
-    uint64_t kv2 = mix64(kv + GAMMA);                  // ... and their second keys (follower draws 0 and 1)
-    int ki = 0;
-    const uint64_t d0 = h.d;
-    typename F::R r;
-    f.load_consts(r);
-    FPH_START(f);
-    PH_DECL;
-    int ep = 0;
-    bool need_adv = false;       // the general event code has to run on the (flushed) LDS image before the next decision
-    // Wave priority = longest remaining work first (s_setprio).  A launch that fills the machine by itself ends with its slowest env
-    // (430 of a mean 360 decisions at 20A/50T x 3 episodes) while the SIMDs it shares with envs that finished early idle; the waves
-    // with the most tasks still to serve -- episodes to come x T + the unmasked tasks of the last decision, in sixths of the launch's
-    // total: 4/6, 2/6, 1/6 -- win the instruction arbiter, so the four waves of a SIMD finish together: one 4096-env launch 1.237 ->
-    // 1.091 ms (3 episodes), 0.447 -> 0.426 (1 episode), 8192 envs 2.23 -> 2.05.  Re-evaluated at episode ends and at the key refill
-    // (every 64 decisions): nothing per decision.  Not for sub-batches that share the SIMDs with other launches (grid < 4096: several
-    // streams, whose tails already overlap the others' bodies; priorities across launches measured -1 ... -5 % there, also with a
-    // common deadline clock), nor in the multi-chunk kernels (their launches run in several rounds of workgroups: +0.5 / -3 %).
-    // A template parameter, not a run-time test: the bookkeeping alone (one more live scalar, the refill path) cost the
-    // unprioritised four-stream line 0.45 %.
-    constexpr bool use_prio = PRIO;
-    int nv_last = S.T(), prio_lv = 3;
-    auto set_prio = [&](int ep_now) {
-        const int rem6 = 6 * ((episodes - ep_now - 1) * S.T() + nv_last), tot = episodes * S.T();
-        const int lv = rem6 >= 4 * tot ? 3 : (rem6 >= 2 * tot ? 2 : (rem6 >= tot ? 1 : 0));
-        if (lv != prio_lv) {
-            prio_lv = lv;
-            if (lv == 3) __builtin_amdgcn_s_setprio(3); else if (lv == 2) __builtin_amdgcn_s_setprio(2);
-            else if (lv == 1) __builtin_amdgcn_s_setprio(1); else __builtin_amdgcn_s_setprio(0);
-        }
-    };
-    if constexpr (use_prio) __builtin_amdgcn_s_setprio(3);
-    for (;;) {
-        if (!need_adv) {         // head of an episode slot (the `for ep` of k_rollout_random)
-            if (ep >= episodes) break;
-            if (h.flags & DCM_FLAG_DONE) {   // restart from the loaded instance; d keeps running
-                if (h.flags & ROLLOUT_ERR) break;
-                if (left == 0) break;        // budget spent at an episode boundary: the finished episode's results stay readable
-                S.reset_state(h, lane);
-                need_adv = true;
-            }
-        }
-        if (need_adv) {
-            CNT(15);
-            S.advance(h, P, lane, row PH_PASS);
-            need_adv = false;
-            // wave-uniform by construction; tell the compiler so (scalar branches in the fast loop)
-            h.now = uni(h.now); h.flags = uni(h.flags); h.cur_group = uni(h.cur_group); h.n_groups = uni(h.n_groups);
-            h.empty_passes = uni(h.empty_passes);
-        }
-        if (!(h.flags & DCM_FLAG_DONE) && left != 0) {
-            WSYNC();
-            f.reload(r);
-            FPHK(f, 13);
-            for (;;) {
-                FPHK(f, 12);
-                CNT(0);
-                const uint64_t k1 = rl(kv, ki), k2 = rl(kv2, ki);
-                const int rlen = f.decide(r, h, P, lane, k1, agrow, tkrow, mkp, &k2, use_prio ? &nv_last : nullptr);
-                if (h.flags & DCM_FLAG_DONE) break;
-                gd += GAMMA;
-                if (++ki == WAVE) { kv = mix64(gd + GAMMA * (uint64_t)lane); kv2 = mix64(kv + GAMMA); ki = 0; if constexpr (use_prio) set_prio(ep); }
-                left--;
-                if (rlen == 0) {                                                  // worker.py:53 else same group, next leader
-                    CNT(8);
-                    if (h.cur_group < h.n_groups) { CNT(9); h.cur_group++; }                  // worker.py:52 next group
-                    else if (!f.next_event(r, h, P, lane)) { need_adv = true; break; }   // worker.py:85 -> :45
-                }
-                if (left == 0) break;
-            }
-            f.flush(r);
-            FPHK(f, 12);
-            if (need_adv) continue;
-        }
-        if (left == 0) break;
-        ep++;
-        if constexpr (use_prio) { if (ep < episodes) { nv_last = S.T(); set_prio(ep); } }
-    }
-    PH_FLUSH(lane);
-    FPHK(f, 13);
-    FPH_FLUSH(f, lane);
-    const int64_t steps = (int64_t)(left0 - left);
-    if (lane == 0 && steps_out) steps_out[e] = steps;
-    h.d = d0 + (uint64_t)steps;
-    {   // Hdr::max_arrival (see k_rollout_random)
-        double m = 0.0;
-        S.for_agents(lane, [&](int a) { const double av = (S.cur()[a] != -2) ? S.arr()[a] : 0.0; m = av > m ? av : m; });
-        const double wm = wave_nanmax(m);
-        if (lane == 0) { Hdr* q = (Hdr*)smem; if (wm > q->max_arrival) q->max_arrival = wm; }
-    }
-    WSYNC();
-    store_hdr(h, lane);
-    WSYNC();
-    S.store_record(rec, lane);
-}
+// k_rollout_fast and its renewing form k_rn_rollout_fast: see k_rollout_fast.inc
+#define DCM_RENEW 0
+#include "k_rollout_fast.inc"
+#undef DCM_RENEW
+#define DCM_RENEW 1
+#include "k_rollout_fast.inc"
+#undef DCM_RENEW

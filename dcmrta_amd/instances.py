@@ -73,6 +73,14 @@ def generate_batch_ranges(seeds, agents_range, tasks_range, max_coalition_size=5
     return out
 
 
+def renewal_seeds(seeds, n, stride):
+    """Seeds of the instances an env plays under instance renewal (BatchedTaskEnv.set_instance_renewal): seeds + n * stride
+    mod 2**64, elementwise with numpy broadcasting, as uint64.  seeds / n / stride: ints or integer arrays; negative values count
+    mod 2**64.  n = 0 gives the seeds themselves."""
+    obj = lambda x: np.asarray(x).astype(object)                     # exact Python-int arithmetic, reduced once at the end
+    return np.asarray((obj(seeds) + obj(n) * obj(stride)) % (1 << 64)).astype(np.uint64)
+
+
 def instance_from_dicts(task_dic, agent_dic, depot):
     """(A, instance dict) from the reference's own containers (env/task_env.py:76-113): what `env.reset(test_env)` of
     RL_test.py:36-42 / baselines/CTAS-D.py:60-66 receives after unpickling a test-set env."""

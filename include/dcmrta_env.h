@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define DCM_ABI_VERSION 5 /* v3: dcm_build_id, dcm_set_visibility, dcm_load_instances validates req on the device; v4: dcm_set_replay_placement; v5: DCM_PARAM_WIDE_MEMBERS; still v5, additions only: dcm_generate_instances, dcm_get_instances, dcm_generator_draws */
+#define DCM_ABI_VERSION 5 /* v3: dcm_build_id, dcm_set_visibility, dcm_load_instances validates req on the device; v4: dcm_set_replay_placement; v5: DCM_PARAM_WIDE_MEMBERS; still v5, additions only: dcm_generate_instances, dcm_get_instances, dcm_generator_draws, dcm_set_instance_renewal, dcm_instance_index */
 
 typedef struct dcm_env dcm_env; /* opaque */
 
@@ -73,7 +73,8 @@ typedef enum {
  * Honoured by dcm_reset / dcm_observe / dcm_step; dcm_rollout_random always groups by location. */
 #define DCM_PARAM_NO_GROUPING 1u
 /* dcm_params.flags: auto-reset for the lockstep API -- when a dcm_step ends an env's episode (terminal box of worker.py:87,
- * results written to its dcm_summary row), the same call restarts the env from its loaded instance (reset + clear_decisions
+ * results written to its dcm_summary row), the same call restarts the env from the instance its record holds -- or, with
+ * dcm_set_instance_renewal, from the env's next instance, drawn right there -- (reset + clear_decisions
  * + the first event, exactly what dcm_rollout_random does between its episodes: the decision counter keeps running) and the
  * fused observation is the first decision of the new episode; the env stays active.  dcm_env_episodes counts the finished
  * episodes.  This is SURVEY.md §8(d)'s "consecutive episodes, auto-reset to the same instance" for a policy in the loop: the
@@ -163,6 +164,30 @@ int dcm_generate_instances(dcm_env *env, const uint64_t *inst_seeds, int32_t age
 int dcm_get_instances(dcm_env *env, double *depot, double *task_xy, int32_t *req, double *dur, int32_t *n_agents,
                       int32_t *n_tasks, void *stream);
 
+/* A fresh instance at every episode restart, drawn on the device: the reference never plays an instance twice, every Worker builds a
+ * new TaskEnv(..., seed=...) (worker.py:32).  dcm_generate_instances keeps a device copy of inst_seeds[B] and its scalar arguments in
+ * the handle and sets every env's INSTANCE INDEX to 0.  With stride != 0, whenever env e restarts an episode inside a kernel -- the
+ * auto-reset of dcm_step (DCM_PARAM_AUTO_RESET), the restart between or before episodes of dcm_rollout_random -- it first replaces
+ * its instance by the one of seed inst_seeds[e] + (n + 1) * stride (mod 2^64), n its index so far, and its index becomes n + 1; then
+ * reset + clear_decisions and the first event as always.  With stride = B and seeds base + 0..B-1, episode k of env e plays instance
+ * base + k * B + e.  stride == 0 (the default) turns renewal off: behaviour is then exactly that of a handle that never set it.
+ * Valid only while the handle's instances came from dcm_generate_instances and the batch is uniform; otherwise DCM_ERR_STATE, and
+ * nothing changes.  A ragged batch (a range with lo < hi) is refused: an env's sizes would change inside a launch, which is out of
+ * scope.  dcm_load_instances[_ragged] and a new dcm_generate_instances turn renewal off.
+ * What does not renew: dcm_reset restarts the instance the record holds and leaves the index alone; an env that stops at an episode
+ * boundary -- the last of a call's `episodes`, a spent decision budget, the auto_reset_episodes limit, an error flag -- keeps the
+ * finished episode's instance and results until a later call restarts it, so every getter stays valid for that episode.  The
+ * index lives in the env's record: dcm_clone_state / dcm_restore_state carry it with the instance, and dcm_state_bytes is unchanged.
+ * The seeds, the generator's arguments and the stride are the handle's and are not part of a snapshot: dcm_restore_state leaves them
+ * and the setting as they are, so restore only snapshots of the instances the handle's last dcm_generate_instances made (or of
+ * their renewals) while a stride is set -- a snapshot from before that call, or of loaded instances, would renew from seeds that are
+ * not its own; turn renewal off first.
+ * dcm_get_instances returns the instance a record holds now.  Host-side setter; takes effect at the next launch (a captured graph
+ * keeps the setting it was captured with). */
+int dcm_set_instance_renewal(dcm_env *env, uint64_t stride);
+/* index_out[B] u32: every env's instance index n (0 after dcm_generate_instances / dcm_load_instances; see above). */
+int dcm_instance_index(dcm_env *env, uint32_t *index_out, void *stream);
+
 /* Known-answer entry point of the instance generator's random stream (no handle, like dcm_distance): for each of the n seeds
  * (u64[n]) the first n_doubles values of np.random.default_rng(seed).random(), then n_ints values of .integers(0, bound),
  * 1 <= bound <= 2^32 - 1, through the device routines dcm_generate_instances uses: doubles_out f64[n, n_doubles],
@@ -232,7 +257,8 @@ int dcm_set_return_log(dcm_env *env, double *returns, int32_t cap);
  * policy inside ONE persistent launch (worker.py:45-87 with the action drawn from slot 1 of the
  * protocol); the observation tensors + mask are produced at every decision exactly as dcm_observe
  * does and written to agents_out/tasks_out/mask_out (nullable: skip the stores).  Envs restart
- * from their loaded instance between episodes; the decision counter keeps running.  An env that is in the middle of an
+ * from the instance their record holds between episodes -- or, with dcm_set_instance_renewal, from their next instance, drawn at
+ * the restart --; the decision counter keeps running.  An env that is in the middle of an
  * episode when the call starts first plays that episode to its end (it counts as one of the `episodes`).
  * Decision budget: max_decisions_in[B] i64 (nullable device array) or, when NULL, the scalar max_decisions -- an env
  * takes at most that many decisions in this call (< 0 = unlimited).  When the budget runs out the env stays at the
