@@ -16,6 +16,7 @@ FOLLOWER_COLS = 4
 MAX_MEMBERS = 5
 MAX_MEMBERS_WIDE = 16    # DCM_PARAM_WIDE_MEMBERS handles
 PARAM_NO_GROUPING, PARAM_AUTO_RESET, PARAM_STRICT_MASK, PARAM_WIDE_MEMBERS = 1, 2, 4, 8
+PARAM_RENEW_SIZES = 16    # set_instance_renewal also on a ragged generated batch: the sizes are renewed with the instances
 MAX_AGENTS = 128
 MAX_TASKS = 1023
 

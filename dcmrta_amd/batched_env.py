@@ -46,7 +46,8 @@ _RAW_STREAM = getattr(torch._C, "_cuda_getCurrentRawStream", None) or (lambda i:
 
 class BatchedTaskEnv:
     def __init__(self, n_envs, n_agents, n_tasks, device="cuda:0", max_waiting_time=10.0, max_time=100.0,
-                 individual_selection=False, auto_reset=False, auto_reset_episodes=0, strict_mask=False, member_cap=5):
+                 individual_selection=False, auto_reset=False, auto_reset_episodes=0, strict_mask=False, member_cap=5,
+                 renew_sizes=False):
         self._h = None
         self._lib = _lib.load()
         self.device = torch.device(device)
@@ -65,11 +66,15 @@ class BatchedTaskEnv:
         # simulating it like the reference's TaskEnv.step does
         # member_cap: member slots per task -- 5 (COALITION_SIZE, parameters.py:17) or, for a mask-ignoring policy (worker.py:140) or
         # max_coalition_size > 5 (env/task_env.py:71), 16 (DCM_PARAM_WIDE_MEMBERS: larger records, runtime-size kernels, no replay)
+        # renew_sizes: set_instance_renewal also takes a ragged batch made by generate_instances (DCM_PARAM_RENEW_SIZES): an env that
+        # restarts an episode then draws its next sizes with its next instance, as every reference Worker's TaskEnv does with tuple
+        # ranges (env/task_env.py:58-65); nothing else changes
         if not 1 <= int(member_cap) <= _lib.MAX_MEMBERS_WIDE:
             raise DcmError(f"member_cap must be in 1..{_lib.MAX_MEMBERS_WIDE}")
         self.member_cap = _lib.MAX_MEMBERS if int(member_cap) <= _lib.MAX_MEMBERS else _lib.MAX_MEMBERS_WIDE
         flags = (1 if individual_selection else 0) | (2 if auto_reset else 0) | (4 if strict_mask else 0) | \
-                (_lib.PARAM_WIDE_MEMBERS if self.member_cap > _lib.MAX_MEMBERS else 0)
+                (_lib.PARAM_WIDE_MEMBERS if self.member_cap > _lib.MAX_MEMBERS else 0) | (_lib.PARAM_RENEW_SIZES if renew_sizes else 0)
+        self.renew_sizes = bool(renew_sizes)
         # auto_reset_episodes: an env stops restarting after that many finished episodes (0 = never)
         p = DcmParams(self.B, self.A, self.T, idx, self.max_waiting_time, self.max_time, flags, int(auto_reset_episodes))
         h = C.c_void_p()
@@ -84,6 +89,9 @@ class BatchedTaskEnv:
         self._leader = torch.empty((B,), dtype=torch.int32, device=dev)
         self._active = torch.empty((B,), dtype=torch.uint8, device=dev)
         self._instances = None
+        # host copies of a ragged batch's per-env sizes, taken when the batch is loaded or generated.  Under size renewal
+        # (renew_sizes=True, set_instance_renewal on a ragged batch) the device changes an env's sizes at its restarts: these two
+        # then still describe instance 0, and instances() returns the sizes of the instance each env holds now
         self.n_agents = self.n_tasks = None
         # the lockstep hot path (step() once per decision of a policy in the loop): everything that does not change between calls is
         # bound once -- the output pointers as plain ints, the Observation over the static buffers, the entry point
@@ -205,8 +213,12 @@ class BatchedTaskEnv:
         inside step() (auto_reset) or rollout_random() first replaces its instance by the one of seed seeds[b] + (n + 1) * stride
         (mod 2**64; seeds = what generate_instances was given, n = instance_index()[b]) -- instances.renewal_seeds -- the way every
         reference Worker builds a new TaskEnv (worker.py:32).  With stride = B and seeds base + arange(B), episode k of env b plays
-        instance base + k * B + b.  0 turns it off.  Needs a uniform batch made by generate_instances (DcmError otherwise);
-        load_instances and a new generate_instances turn it off; reset() does not renew."""
+        instance base + k * B + b.  0 turns it off.  Needs a batch made by generate_instances (DcmError otherwise): a uniform one,
+        or, on an env created with renew_sizes=True, a ragged one -- the restarting env then draws its next sizes as well (the number of
+        tasks, then the number of agents, then the instance, as generate_instances does for that seed), self.n_agents / self.n_tasks
+        keep describing instance 0 and instances() returns the current sizes.  A ragged batch from load_instances is always refused.
+        load_instances and a new generate_instances turn it off; reset() does not renew, nor does an env that stops at an episode
+        boundary: it keeps the finished episode's instance, sizes and results."""
         check(self._lib.dcm_set_instance_renewal(self._h, int(stride) % (1 << 64)))
         self.graph_epoch += 1          # a captured dcm_step has the kernel form and its arguments baked in
         return self
@@ -221,7 +233,8 @@ class BatchedTaskEnv:
     def instances(self):
         """The instances the env holds, however they got there, as device tensors in the keyword format of load_instances:
         depot[B,2], task_xy[B,T,2], req[B,T], dur[B,T], n_agents[B], n_tasks[B] (rows beyond an env's own sizes: xy 0, req 1, dur 0, the
-        padding of instances.generate_batch_ranges; n_agents / n_tasks are None on a uniform batch)."""
+        padding of instances.generate_batch_ranges; n_agents / n_tasks are None on a uniform batch, and under size renewal they are
+        the sizes of the instance each env holds NOW)."""
         B, T, dev = self.B, self.T, self.device
         o = dict(depot=torch.empty((B, 2), dtype=torch.float64, device=dev), task_xy=torch.empty((B, T, 2), dtype=torch.float64, device=dev),
                  req=torch.empty((B, T), dtype=torch.int32, device=dev), dur=torch.empty((B, T), dtype=torch.float64, device=dev),
@@ -482,6 +495,13 @@ class BatchedTaskEnv:
         return buf
 
     def restore_state(self, buf):
+        # dcm_restore_state takes no length, and the blob of a renew_sizes handle is 8 * B bytes longer while its batch is ragged: a
+        # snapshot taken from the other kind of batch would be read past its end
+        n = C.c_size_t()
+        check(self._lib.dcm_state_bytes(self._h, C.byref(n)))
+        if buf.numel() * buf.element_size() != n.value:
+            raise DcmError(f"restore_state: the snapshot holds {buf.numel() * buf.element_size()} bytes, this env's state is {n.value} "
+                           "(taken from another env, or before the batch changed between uniform and ragged)")
         with torch.cuda.device(self.device):
             check(self._lib.dcm_restore_state(self._h, _ptr(buf), self._stream()))
 

@@ -155,7 +155,8 @@ struct GenArgs {
     double max_duration;
 };
 // Instance renewal (dcm_set_instance_renewal): what a kernel that restarts episodes needs to draw the env's next instance, the last
-// argument of the renewing kernel forms (k_rn_*).  The batch is uniform: both ranges of g are zero-width at the handle's dims.
+// argument of the renewing kernel forms.  k_rn_*: the batch is uniform, both ranges of g are zero-width at the handle's dims.
+// k_rs_* (DCM_PARAM_RENEW_SIZES, a ragged generated batch): g carries the real ranges and the env's next sizes are drawn as well.
 struct Renew {
     const uint64_t* seeds;            // [B] inst_seeds of dcm_generate_instances (the handle's device copy)
     uint64_t stride;                  // instance n of env e has the seed seeds[e] + n * stride (mod 2^64); never 0 here
@@ -481,12 +482,13 @@ struct dcm_env {
     uint16_t* ablog = nullptr;       // [B][A][AB_CAP] abandonment log (side table of the state)
     bool loaded = false, reset_done = false;
     // instance renewal (dcm_set_instance_renewal): what dcm_generate_instances was last called with.  `generated` while the records'
-    // instances came from it; renew_stride != 0 while renewal is on (only ever with generated && !sizes)
+    // instances came from it; renew_stride != 0 while renewal is on (only ever with generated, and with !sizes unless the handle has
+    // DCM_PARAM_RENEW_SIZES: the kernels then rewrite `sizes` at restarts)
     uint64_t* inst_seeds = nullptr;  // [B] device copy of its inst_seeds
     dcm::GenArgs gen{};
     bool generated = false;
     uint64_t renew_stride = 0;
-    int32_t* sizes = nullptr;        // [B][2] (A_e, T_e) of a ragged batch (dcm_load_instances_ragged), else nullptr
+    int32_t* sizes = nullptr;        // [B][2] (A_e, T_e) of a ragged batch (dcm_load_instances_ragged, dcm_generate_instances), else nullptr
     std::vector<int32_t> sizes_host;
     // route replay (dcmrta_replay.hip)
     int32_t* routes = nullptr;       // [B][A][route_cap] actions

@@ -55,9 +55,10 @@ struct RolloutArgs {
     int64_t* steps_out; double* summary; uint16_t* ablog;
     const int32_t* sizes; int64_t budget_all; const int64_t* budget_in;
     unsigned char* gscr; double* retlog; int retcap;
-    Renew rn;            // last argument of the renewing forms (k_rn_*), which are launched while rn.stride != 0
+    Renew rn;            // last argument of the renewing forms (k_rn_*, k_rs_*)
+    plan::RenewForm form;  // which form the launch takes (plan::renew_form)
 };
-// k_rollout_fast_g<NAC, NTC, OBS> / k_rn_rollout_fast_g<NAC, NTC, OBS> (rollout_fast_g.hpp, its own translation unit)
+// k_rollout_fast_g<NAC, NTC, OBS> / k_rn_rollout_fast_g / k_rs_rollout_fast_g (rollout_fast_g.hpp, its own translation unit)
 void launch_rollout_fast_g(int nac, int ntc, bool obs, unsigned grid, Lay L, hipStream_t stream, const RolloutArgs& a);
 }  // namespace dcm
 
@@ -1010,6 +1011,21 @@ struct Sim {
         }
     }
 
+    // The count table (HBM, 2*A*T bytes, indexed a * T + t with the env's own T) only holds the abandonments beyond the log's 16 per
+    // agent, so it needs clearing only after an episode in which some agent overflowed its log.  Judged by, and sized for, the sizes
+    // the simulator has NOW: a kernel form that changes an env's sizes at a restart (wave_renew_instance_sized) calls this with the
+    // finished episode's sizes still in place -- before they change -- so that every agent of that episode is looked at and its
+    // whole table is cleared; the table is then all zero whenever an episode starts, whatever sizes it starts with.
+    __device__ __forceinline__ void clear_spilled_counts(int lane) const {
+        bool spilled = false;
+        for_agents(lane, [&](int a) { spilled = spilled || (ainfo()[a] >> 16) > (uint32_t)AB_CAP; });
+        if (__any(spilled)) {
+            uint4* c = (uint4*)abcnt();
+            const int n16 = (int)(abcnt_pitch(A(), T()) / 16);
+            for (int i = lane; i < n16; i += WAVE) c[i] = uint4{0u, 0u, 0u, 0u};
+        }
+    }
+
     // reset + clear_decisions (env/task_env.py:116-140); keeps seed, d, episodes
     __device__ __forceinline__ void reset_state(HdrRegs& h, int lane) const {
         const int PT_ = PT();
@@ -1023,16 +1039,7 @@ struct Sim {
 #pragma unroll
             for (int j = 0; j < MC; j++) marr()[j * PT_ + t] = __builtin_nan("");  // empty member slots
         });
-        {   // abandoned_agent = [] :131.  The count table (HBM, 2*A*T bytes) only holds the abandonments beyond the log's
-            // 16 per agent, so it needs clearing only after an episode in which some agent overflowed its log
-            bool spilled = false;
-            for_agents(lane, [&](int a) { spilled = spilled || (ainfo()[a] >> 16) > (uint32_t)AB_CAP; });
-            if (__any(spilled)) {
-                uint4* c = (uint4*)abcnt();
-                const int n16 = (int)(abcnt_pitch(A(), T()) / 16);
-                for (int i = lane; i < n16; i += WAVE) c[i] = uint4{0u, 0u, 0u, 0u};
-            }
-        }
+        clear_spilled_counts(lane);              // abandoned_agent = [] :131
         for_agents(lane, [&](int a) {
             ax()[a] = ((const Hdr*)base)->depot_x; ay()[a] = ((const Hdr*)base)->depot_y;      // :134
             arr()[a] = 0.0; nd()[a] = 0.0; tdist()[a] = 0.0;  // :135
@@ -1439,11 +1446,14 @@ __global__ __launch_bounds__(WAVE) void k_observe(int A, int T, int PA, int PT, 
     }
 }
 
-// k_step and its renewing form k_rn_step: see k_step.inc
+// k_step, its renewing form k_rn_step and its size-renewing form k_rs_step: see k_step.inc
 #define DCM_RENEW 0
 #include "k_step.inc"
 #undef DCM_RENEW
 #define DCM_RENEW 1
+#include "k_step.inc"
+#undef DCM_RENEW
+#define DCM_RENEW 2   // the size-renewing form (k_rs_*): runtime-size instantiations only
 #include "k_step.inc"
 #undef DCM_RENEW
 
@@ -1475,11 +1485,14 @@ constexpr uint32_t rollout_random_lds_bytes(Lay L) {
 // 50A/200T instantiation wants 176 -- two waves per SIMD although its LDS image (10.9 KB with the member arrival times left in
 // the HBM record) would let twelve workgroups share a CU -- and with 168 (five spilled) it runs three: 8.65 -> 6.90 ms per
 // 8192-env launch.  Four (128 VGPRs, 47 spilled) measured slower again (7.15 ms).
-// k_rollout_random and its renewing form k_rn_rollout_random: see k_rollout_random.inc
+// k_rollout_random, its renewing form k_rn_rollout_random and its size-renewing form k_rs_rollout_random: see k_rollout_random.inc
 #define DCM_RENEW 0
 #include "k_rollout_random.inc"
 #undef DCM_RENEW
 #define DCM_RENEW 1
+#include "k_rollout_random.inc"
+#undef DCM_RENEW
+#define DCM_RENEW 2   // the size-renewing form (k_rs_*): runtime-size instantiations only
 #include "k_rollout_random.inc"
 #undef DCM_RENEW
 
@@ -1629,6 +1642,14 @@ __global__ void k_distance(const double* ax, const double* ay, const double* bx,
 #define DISPATCH_ENV(env) switch (plan::sim_kind(shape_of(env))) { FOR_EACH_INSTANCE(SIM_CASE) }
 #define DISPATCH_ONE_CHUNK(env) \
     switch (plan::sim_kind(shape_of(env))) { FOR_EACH_FAST(SIM_CASE) default: return fail(DCM_ERR_STATE, "internal error: a one-chunk kernel on another layout"); }
+// The instantiations that read per-env sizes, i.e. what plan::sim_kind gives a ragged batch: the only ones the size-renewing kernel
+// forms (k_rs_*) exist for.  DISPATCH_RAGGED / DISPATCH_ONE_CHUNK_RAGGED: the same two switches over them.
+#define FOR_EACH_FAST_RAGGED(X) X(S20x50_RS, 20, 50, true) X(S64x64_RS, 64, 64, true)
+#define FOR_EACH_RAGGED(X) FOR_EACH_FAST_RAGGED(X) X(S128x256_RS, 128, 256, true) X(Runtime, 0, 0, false) X(RuntimeWide, 0, 0, false, MW)
+#define DISPATCH_RAGGED(env) \
+    switch (plan::sim_kind(shape_of(env))) { FOR_EACH_RAGGED(SIM_CASE) default: return fail(DCM_ERR_STATE, "internal error: a size-renewing kernel on an exact shape"); }
+#define DISPATCH_ONE_CHUNK_RAGGED(env) \
+    switch (plan::sim_kind(shape_of(env))) { FOR_EACH_FAST_RAGGED(SIM_CASE) default: return fail(DCM_ERR_STATE, "internal error: a size-renewing one-chunk kernel on another layout"); }
 // kernel arguments every env kernel starts with: batch dims, layout dims
 #define DIMS(env) (env)->A, (env)->T, (env)->L.A, (env)->L.T
 
@@ -1653,13 +1674,21 @@ void launch_rollout_rn(K kernel, dim3 grid, dim3 block, unsigned lds_bytes, hipS
     hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, a.A, a.T, a.PA, a.PT, a.kp, a.state, a.episodes, a.agents_out, a.tasks_out,
                        a.mask_out, a.steps_out, a.summary, a.ablog, a.sizes, a.budget_all, a.budget_in, a.gscr, a.retlog, a.retcap, a.rn);
 }
+// ... and for the size-renewing form (k_rs_*), which writes the drawn sizes to the handle's size table
+template <class K>
+void launch_rollout_rs(K kernel, dim3 grid, dim3 block, unsigned lds_bytes, hipStream_t stream, const RolloutArgs& a) {
+    hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, a.A, a.T, a.PA, a.PT, a.kp, a.state, a.episodes, a.agents_out, a.tasks_out,
+                       a.mask_out, a.steps_out, a.summary, a.ablog, const_cast<int32_t*>(a.sizes), a.budget_all, a.budget_in, a.gscr, a.retlog,
+                       a.retcap, a.rn);
+}
 }  // namespace
 
 #if defined(DCM_TU_G) || !defined(DCM_SPLIT_G)
 void dcm::launch_rollout_fast_g(int nac, int ntc, bool obs, unsigned grid, Lay L, hipStream_t stream, const RolloutArgs& a) {
 #define CALLG(NAC, NTC, OBS)                                                                                                          \
     do {                                                                                                                              \
-        if (a.rn.stride != 0) launch_rollout_rn(k_rn_rollout_fast_g<NAC, NTC, OBS>, dim3(grid), dim3(WAVE), rollout_fast_g_lds_bytes(L), stream, a); \
+        if (a.form == plan::RenewForm::Sizes) launch_rollout_rs(k_rs_rollout_fast_g<NAC, NTC, OBS>, dim3(grid), dim3(WAVE), rollout_fast_g_lds_bytes(L), stream, a); \
+        else if (a.form == plan::RenewForm::Instance) launch_rollout_rn(k_rn_rollout_fast_g<NAC, NTC, OBS>, dim3(grid), dim3(WAVE), rollout_fast_g_lds_bytes(L), stream, a); \
         else launch_rollout(k_rollout_fast_g<NAC, NTC, OBS>, dim3(grid), dim3(WAVE), rollout_fast_g_lds_bytes(L), stream, a);        \
     } while (0)
 #define CALLT(NAC, OBS) do { if (ntc > 3) { CALLG(NAC, 4, OBS); } else if (ntc > 2) { CALLG(NAC, 3, OBS); } else { CALLG(NAC, 2, OBS); } } while (0)
@@ -1692,17 +1721,24 @@ bool stream_capturing(void* stream) {
     return hipStreamIsCapturing((hipStream_t)stream, &cs) != hipSuccess || cs != hipStreamCaptureStatusNone;
 }
 
-// the last argument of the renewing kernel forms (k_rn_*), which are launched while the stride is not 0
+// the last argument of the renewing kernel forms (k_rn_*, k_rs_*), which are launched while the stride is not 0; on a ragged batch
+// (k_rs_*) env->gen holds the real ranges
 Renew renew_args(const dcm_env* env) { return Renew{env->inst_seeds, env->renew_stride, env->gen}; }
-// true while the stride is set, i.e. the launch about to be made is of a renewing form: it may replace instances, so the restart
-// image of k_step_fast (dcm_env::init, the records as dcm_reset saw them) is no longer theirs -- also after the stride is cleared.
-// Captured, the launch replaces instances at every replay, unseen by the host: the handle then counts as captured, which keeps
-// dcm_step from using an image for good
-bool renewing_launch(dcm_env* env, void* stream) {
-    if (env->renew_stride == 0) return false;
+bool renew_sizes_opted_in(const dcm_env* env) { return (env->p.flags & DCM_PARAM_RENEW_SIZES) != 0; }
+// The form the handle's next launch of a restarting kernel takes (plan::renew_form); changes nothing
+plan::RenewForm launch_form(const dcm_env* env) {
+    return plan::renew_form(shape_of(env), env->renew_stride != 0, renew_sizes_opted_in(env));
+}
+// ... and what the host has to note when that launch is really about to be made.  While the stride is set it is a renewing one: it
+// may replace instances, so the restart image of k_step_fast (dcm_env::init, the records as dcm_reset saw them) is no longer theirs
+// -- also after the stride is cleared.  Captured, the launch replaces instances at every replay, unseen by the host: the handle then
+// counts as captured, which keeps dcm_step from using an image for good.  Called behind every check that can still refuse the call.
+plan::RenewForm renewing_launch(dcm_env* env, void* stream) {
+    const plan::RenewForm form = launch_form(env);
+    if (form == plan::RenewForm::Plain) return form;
     env->init_valid = false;
     if (stream_capturing(stream)) env->captured = true;
-    return true;
+    return form;
 }
 // the handle's instances no longer come from dcm_generate_instances, or come from a new call of it: renewal is off
 void renewal_off(dcm_env* env, bool generated) { env->generated = generated; env->renew_stride = 0; }
@@ -1728,11 +1764,13 @@ int launch_env_status(dcm_env* env, uint32_t* flags_out, int64_t* decisions_out,
 }
 
 // the blob of dcm_state_bytes / dcm_clone_state / dcm_restore_state: these sections of the handle, in this order
+// (the last one only where the per-env sizes can change after the load: a ragged batch on a DCM_PARAM_RENEW_SIZES handle; else empty)
 struct Section { void* ptr; size_t bytes; };
-std::array<Section, 3> state_sections(const dcm_env* env) {
+std::array<Section, 4> state_sections(const dcm_env* env) {
     const size_t B = (size_t)env->p.n_envs;
+    const bool with_sizes = env->sizes && renew_sizes_opted_in(env);
     return {{{env->state, B * env->L.rec_bytes()}, {env->summary, B * 8 * sizeof(double)},
-             {env->ablog, side_bytes(env->p.n_envs, env->A, env->T)}}};
+             {env->ablog, side_bytes(env->p.n_envs, env->A, env->T)}, {env->sizes, with_sizes ? B * 2 * sizeof(int32_t) : 0}}};
 }
 }  // namespace
 
@@ -1807,6 +1845,11 @@ int dcm_create(const dcm_params* params, dcm_env** out) {
     allow_lds(k_rn_rollout_random<CA, CT, RS, ##__VA_ARGS__>, lds);
     FOR_EACH_INSTANCE(SET_ATTR)
 #undef SET_ATTR
+#define SET_ATTR(KIND, CA, CT, RS, ...)                        \
+    allow_lds(k_rs_step<CA, CT, RS, ##__VA_ARGS__>, lds);      \
+    allow_lds(k_rs_rollout_random<CA, CT, RS, ##__VA_ARGS__>, lds);
+    FOR_EACH_RAGGED(SET_ATTR)
+#undef SET_ATTR
 #define SET_FAST(KIND, CA, CT, RS)                             \
     allow_lds(k_rollout_fast<CA, CT, RS, true>, lds);          \
     allow_lds(k_rollout_fast<CA, CT, RS, false>, lds);         \
@@ -1819,6 +1862,14 @@ int dcm_create(const dcm_params* params, dcm_env** out) {
     allow_lds(k_rn_rollout_fast<CA, CT, RS, false, true>, lds); \
     allow_lds(k_rn_step_fast<CA, CT, RS>, lds);
     FOR_EACH_FAST(SET_FAST)
+#undef SET_FAST
+#define SET_FAST(KIND, CA, CT, RS)                             \
+    allow_lds(k_rs_rollout_fast<CA, CT, RS, true>, lds);       \
+    allow_lds(k_rs_rollout_fast<CA, CT, RS, false>, lds);      \
+    allow_lds(k_rs_rollout_fast<CA, CT, RS, true, true>, lds); \
+    allow_lds(k_rs_rollout_fast<CA, CT, RS, false, true>, lds); \
+    allow_lds(k_rs_step_fast<CA, CT, RS>, lds);
+    FOR_EACH_FAST_RAGGED(SET_FAST)
 #undef SET_FAST
     allow_lds(k_rollout_fast_mc<50, 200, true>, lds);
     allow_lds(k_rollout_fast_mc<50, 200, false>, lds);
@@ -1914,8 +1965,9 @@ int dcm_get_instances(dcm_env* env, double* depot, double* task_xy, int32_t* req
 
 int dcm_set_instance_renewal(dcm_env* env, uint64_t stride) {
     CHECK_HANDLE(env);
-    if (stride != 0 && !plan::renewal_ok(shape_of(env), env->loaded && env->generated))
-        return fail(DCM_ERR_STATE, "dcm_set_instance_renewal: needs a uniform batch made by dcm_generate_instances");
+    const bool generated = env->loaded && env->generated;
+    if (stride != 0 && !plan::renewal_ok(shape_of(env), generated) && !plan::renewal_sizes_ok(shape_of(env), generated, renew_sizes_opted_in(env)))
+        return fail(DCM_ERR_STATE, "dcm_set_instance_renewal: needs a batch made by dcm_generate_instances, uniform unless the handle has DCM_PARAM_RENEW_SIZES");
     env->renew_stride = stride;
     return DCM_OK;
 }
@@ -2044,12 +2096,14 @@ int dcm_step(dcm_env* env, const int32_t* actions, const int32_t* leader_in, con
         // Deferred terminal metrics (dcm_env::side) for auto-resetting handles: not under stream capture -- the periodic flush is a
         // host-side decision and the buffers are allocated on first use -- where episode ends keep computing their metrics inline.
         uint32_t* pendq = nullptr;
+        const plan::RenewForm form = launch_form(env);
+        const bool renew = form != plan::RenewForm::Plain;
         if (env->p.flags & DCM_PARAM_AUTO_RESET) {
             if (stream_capturing(stream)) {
                 if (env->maybe_pending)
                     return fail(DCM_ERR_STATE, "dcm_step under stream capture: deferred episode summaries are waiting; call dcm_summary (or dcm_reset) before the capture");
                 env->captured = true;      // a replay of this graph writes summary rows unseen by the host: no snapshots on this handle any more
-            } else if (!env->captured) {
+            } else if (plan::defer_terminal(env->captured, form)) {
                 if (!env->side && !env->side_failed) {
                     const uint32_t pitch = dcm::align16(env->L.rec_bytes() + (uint32_t)env->L.A * dcm::AB_CAP * (uint32_t)sizeof(uint16_t));
                     const size_t qn = (size_t)env->p.n_envs;
@@ -2065,20 +2119,30 @@ int dcm_step(dcm_env* env, const int32_t* actions, const int32_t* leader_in, con
                 pendq = env->pendq;
             }
         }
-        const bool renew = renewing_launch(env, stream);
+        // (a size-renewing launch defers nothing, plan::defer_terminal: rows still waiting from earlier eager launches are computed
+        //  first, while the size table still holds their episodes' sizes; under capture none can be waiting, see above)
+        if (form == plan::RenewForm::Sizes && !stream_capturing(stream)) DCM_TRY(dcm::flush_pending(env, stream));
+        (void)renewing_launch(env, stream);
         const unsigned char* const image = plan::step_restart_image(env->init_valid, pendq != nullptr, renew) ? env->init : nullptr;
         const Renew rn = renew_args(env);
-#define STEP_FAST_ARGS DIMS(env), env->kp, env->state, actions, agents_out, tasks_out, mask_out, leader_out, active_out, env->summary, env->ablog,  \
-                       env->p.flags, (const int32_t*)env->sizes, env->gscratch, env->p.auto_reset_episodes, env->retlog, (int)env->retcap, \
+#define STEP_FAST_ARGS(SIZES) DIMS(env), env->kp, env->state, actions, agents_out, tasks_out, mask_out, leader_out, active_out, env->summary, env->ablog,  \
+                       env->p.flags, SIZES, env->gscratch, env->p.auto_reset_episodes, env->retlog, (int)env->retcap, \
                        env->side, env->side_pitch, pendq, image
+        if (form == plan::RenewForm::Sizes) {
+#define CALL(CA, CT, RS) hipLaunchKernelGGL((k_rs_step_fast<CA, CT, RS>), GRID(env), (step_fast_lds_bytes<CA, CT, RS>(env->L)), (hipStream_t)stream, \
+                                            STEP_FAST_ARGS(env->sizes), rn)
+            DISPATCH_ONE_CHUNK_RAGGED(env);
+#undef CALL
+        } else {
 #define CALL(CA, CT, RS)                                                                             \
     do {                                                                                             \
         const unsigned lds = step_fast_lds_bytes<CA, CT, RS>(env->L);                                \
-        if (renew) hipLaunchKernelGGL((k_rn_step_fast<CA, CT, RS>), GRID(env), lds, (hipStream_t)stream, STEP_FAST_ARGS, rn); \
-        else hipLaunchKernelGGL((k_step_fast<CA, CT, RS>), GRID(env), lds, (hipStream_t)stream, STEP_FAST_ARGS); \
+        if (renew) hipLaunchKernelGGL((k_rn_step_fast<CA, CT, RS>), GRID(env), lds, (hipStream_t)stream, STEP_FAST_ARGS((const int32_t*)env->sizes), rn); \
+        else hipLaunchKernelGGL((k_step_fast<CA, CT, RS>), GRID(env), lds, (hipStream_t)stream, STEP_FAST_ARGS((const int32_t*)env->sizes)); \
     } while (0)
-        DISPATCH_ONE_CHUNK(env);
+            DISPATCH_ONE_CHUNK(env);
 #undef CALL
+        }
 #undef STEP_FAST_ARGS
         LAUNCH_OK();
         if (pendq) {
@@ -2088,19 +2152,27 @@ int dcm_step(dcm_env* env, const int32_t* actions, const int32_t* leader_in, con
         return DCM_OK;
     }
     DCM_TRY(dcm::flush_pending(env, stream));    // (the general kernel writes summary rows itself)
-    const bool renew = renewing_launch(env, stream);
+    const plan::RenewForm form = renewing_launch(env, stream);
+    const bool renew = form != plan::RenewForm::Plain;
     const Renew rn = renew_args(env);
-#define STEP_ARGS DIMS(env), env->kp, env->state, actions, leader_in, nfol_in, followers_in, agents_out, tasks_out, mask_out, leader_out, \
-                  active_out, env->summary, env->log, env->ablog, env->p.flags, (const int32_t*)env->sizes, env->gscratch, \
+#define STEP_ARGS(SIZES) DIMS(env), env->kp, env->state, actions, leader_in, nfol_in, followers_in, agents_out, tasks_out, mask_out, leader_out, \
+                  active_out, env->summary, env->log, env->ablog, env->p.flags, SIZES, env->gscratch, \
                   env->p.auto_reset_episodes, env->retlog, (int)env->retcap
+    if (form == plan::RenewForm::Sizes) {
+#define CALL(CA, CT, RS, ...) hipLaunchKernelGGL((k_rs_step<CA, CT, RS, ##__VA_ARGS__>), GRID(env), (env_kernel_lds_bytes<CA, CT, RS>(env->L)), \
+                                                 (hipStream_t)stream, STEP_ARGS(env->sizes), rn)
+        DISPATCH_RAGGED(env);
+#undef CALL
+    } else {
 #define CALL(CA, CT, RS, ...)                                                                        \
     do {                                                                                             \
         const unsigned lds = env_kernel_lds_bytes<CA, CT, RS>(env->L);                               \
-        if (renew) hipLaunchKernelGGL((k_rn_step<CA, CT, RS, ##__VA_ARGS__>), GRID(env), lds, (hipStream_t)stream, STEP_ARGS, rn); \
-        else hipLaunchKernelGGL((k_step<CA, CT, RS, ##__VA_ARGS__>), GRID(env), lds, (hipStream_t)stream, STEP_ARGS); \
+        if (renew) hipLaunchKernelGGL((k_rn_step<CA, CT, RS, ##__VA_ARGS__>), GRID(env), lds, (hipStream_t)stream, STEP_ARGS((const int32_t*)env->sizes), rn); \
+        else hipLaunchKernelGGL((k_step<CA, CT, RS, ##__VA_ARGS__>), GRID(env), lds, (hipStream_t)stream, STEP_ARGS((const int32_t*)env->sizes)); \
     } while (0)
-    DISPATCH_ENV(env);
+        DISPATCH_ENV(env);
 #undef CALL
+    }
 #undef STEP_ARGS
     LAUNCH_OK();
     return DCM_OK;
@@ -2112,30 +2184,38 @@ int dcm_rollout_random(dcm_env* env, int32_t episodes, int64_t max_decisions, co
     if (!env->reset_done) return fail(DCM_ERR_STATE, "dcm_rollout_random: call dcm_reset first");
     if (episodes < 1) return fail(DCM_ERR_INVALID, "dcm_rollout_random: episodes must be >= 1");
     DCM_TRY(dcm::flush_pending(env, stream));
+    // the renewing (k_rn_*) or size-renewing (k_rs_*) form of whichever kernel serves the handle, while a stride is set (dcm_set_instance_renewal)
+    const plan::RenewForm form = renewing_launch(env, stream);
+    const bool renew = form == plan::RenewForm::Instance, renew_sizes = form == plan::RenewForm::Sizes;
     const dcm::RolloutArgs ra{DIMS(env), env->kp, env->state, (int)episodes, agents_out, tasks_out, mask_out, steps_out, env->summary,
                               env->ablog, (const int32_t*)env->sizes, max_decisions, max_decisions_in, env->gscratch, env->retlog,
-                              (int)env->retcap, renew_args(env)};
+                              (int)env->retcap, renew_args(env), form};
     // The register-resident kernels have the same contract and the same results as the general one (tests/test_gpu_rollout.py runs both)
     const bool all_obs = agents_out && tasks_out && mask_out, no_obs = !agents_out && !tasks_out && !mask_out;
-    // the renewing form of whichever kernel serves the handle, while a stride is set (dcm_set_instance_renewal)
-    const bool renew = renewing_launch(env, stream);
     switch (plan::rollout_kind(shape_of(env), all_obs || no_obs)) {
     case plan::Rollout::Fast: {
+        // wave priorities (k_rollout_fast, PRIO) for a launch that fills the machine by itself: 16 workgroups x 256 CUs
+        const bool prio = env->p.n_envs >= 4096;
+#define CALL(CA, CT, RS) do { if (prio) { if (all_obs) { CALLF(CA, CT, RS, true, true); } else { CALLF(CA, CT, RS, false, true); } }   \
+                              else { if (all_obs) { CALLF(CA, CT, RS, true, false); } else { CALLF(CA, CT, RS, false, false); } } } while (0)
+        if (renew_sizes) {
+#define CALLF(CA, CT, RS, OBS, PRIO) \
+    launch_rollout_rs(k_rs_rollout_fast<CA, CT, RS, OBS, PRIO>, GRID(env), rollout_fast_lds_bytes<CA, CT, RS>(env->L), (hipStream_t)stream, ra)
+            DISPATCH_ONE_CHUNK_RAGGED(env);
+#undef CALLF
+        } else {
 #define CALLF(CA, CT, RS, OBS, PRIO)                                                                                                          \
     do {                                                                                                                                          \
         if (renew) launch_rollout_rn(k_rn_rollout_fast<CA, CT, RS, OBS, PRIO>, GRID(env), rollout_fast_lds_bytes<CA, CT, RS>(env->L), (hipStream_t)stream, ra); \
         else launch_rollout(k_rollout_fast<CA, CT, RS, OBS, PRIO>, GRID(env), rollout_fast_lds_bytes<CA, CT, RS>(env->L), (hipStream_t)stream, ra);  \
     } while (0)
-        // wave priorities (k_rollout_fast, PRIO) for a launch that fills the machine by itself: 16 workgroups x 256 CUs
-        const bool prio = env->p.n_envs >= 4096;
-#define CALL(CA, CT, RS) do { if (prio) { if (all_obs) { CALLF(CA, CT, RS, true, true); } else { CALLF(CA, CT, RS, false, true); } }   \
-                              else { if (all_obs) { CALLF(CA, CT, RS, true, false); } else { CALLF(CA, CT, RS, false, false); } } } while (0)
-        DISPATCH_ONE_CHUNK(env);
-#undef CALL
+            DISPATCH_ONE_CHUNK(env);
 #undef CALLF
+        }
+#undef CALL
         break;
     }
-    case plan::Rollout::FastMc:
+    case plan::Rollout::FastMc:                                                 // (exact shape, never ragged: no size-renewing form)
 #define CALLM(OBS)                                                                                                                      \
     do {                                                                                                                                \
         if (renew) launch_rollout_rn(k_rn_rollout_fast_mc<50, 200, OBS>, GRID(env), FastM<50, 200, OBS>::LDS_BYTES, (hipStream_t)stream, ra); \
@@ -2149,13 +2229,20 @@ int dcm_rollout_random(dcm_env* env, int32_t episodes, int64_t max_decisions, co
                                    env->L, (hipStream_t)stream, ra);
         break;
     case plan::Rollout::General:
+        if (renew_sizes) {
+#define CALL(CA, CT, RS, ...) \
+    launch_rollout_rs(k_rs_rollout_random<CA, CT, RS, ##__VA_ARGS__>, GRID(env), rollout_random_lds_bytes<CA, CT, RS>(env->L), (hipStream_t)stream, ra)
+            DISPATCH_RAGGED(env);
+#undef CALL
+        } else {
 #define CALL(CA, CT, RS, ...)                                                                                                                    \
     do {                                                                                                                                         \
         if (renew) launch_rollout_rn(k_rn_rollout_random<CA, CT, RS, ##__VA_ARGS__>, GRID(env), rollout_random_lds_bytes<CA, CT, RS>(env->L), (hipStream_t)stream, ra); \
         else launch_rollout(k_rollout_random<CA, CT, RS, ##__VA_ARGS__>, GRID(env), rollout_random_lds_bytes<CA, CT, RS>(env->L), (hipStream_t)stream, ra); \
     } while (0)
-        DISPATCH_ENV(env);
+            DISPATCH_ENV(env);
 #undef CALL
+        }
         break;
     }
     LAUNCH_OK();
@@ -2240,6 +2327,7 @@ int dcm_clone_state(dcm_env* env, void* dst, void* stream) {
     DCM_TRY(dcm::flush_pending(env, stream));
     unsigned char* out = (unsigned char*)dst;
     for (const Section& s : state_sections(env)) {
+        if (s.bytes == 0) continue;
         HIP_TRY(hipMemcpyAsync(out, s.ptr, s.bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
         out += s.bytes;
     }
@@ -2252,6 +2340,7 @@ int dcm_restore_state(dcm_env* env, const void* src, void* stream) {
     DCM_TRY(dcm::drop_pending(env, stream));
     const unsigned char* in = (const unsigned char*)src;
     for (const Section& s : state_sections(env)) {
+        if (s.bytes == 0) continue;
         HIP_TRY(hipMemcpyAsync(s.ptr, in, s.bytes, hipMemcpyDeviceToDevice, (hipStream_t)stream));
         in += s.bytes;
     }

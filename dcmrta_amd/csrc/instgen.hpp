@@ -16,7 +16,8 @@
 //
 // Instance renewal (dcm_set_instance_renewal): the kernels that restart episodes -- the renewing forms (k_rn_*: see k_step.inc) of k_step, k_step_fast and
 // the four persistent rollout kernels -- call wave_renew_instance right before reset_state, so that every episode runs on a fresh
-// instance the way every reference Worker builds a fresh TaskEnv (worker.py:32).
+// instance the way every reference Worker builds a fresh TaskEnv (worker.py:32).  The size-renewing forms (k_rs_*) of the
+// instantiations that read per-env sizes call wave_renew_instance_sized instead: the env's sizes are drawn anew as well.
 #pragma once   // (inside dcmrta_env.hip's unnamed namespace, in front of its kernels: np_stream.hpp is included at the top of that file)
 
 // n doubles of Generator.random from the wave-uniform stream p: put(j, value) is called by the lane that owns draw j.
@@ -115,6 +116,8 @@ __device__ __forceinline__ void wave_generate_instance(uint64_t seed, const GenA
 // The wave re-reads its own global stores, made by other lanes than those that read: the loads are agent-scope (past the CU's vector
 // L1, whose lines may date from the record copy at the head of the launch) and follow a release fence that waits for the stores,
 // the order step_fast.hpp keeps for its abandonment rows.
+// (renew_draw + renew_reload below are this body in two halves, for the size-renewing forms: a change here -- the release fence, the
+//  agent-scope loads, their order -- has to be made there as well, by hand.)
 template <class SimT>
 __device__ __forceinline__ void wave_renew_instance(const SimT& S, unsigned char* rec, const Renew& rn, int e, int lane,
                                                     typename SimT::XY& xy) {
@@ -158,6 +161,83 @@ template <class SimT>
 __device__ __noinline__ void wave_renew_instance_call(const SimT& S, unsigned char* rec, const Renew& rn, int e, int lane,
                                                       typename SimT::XY& xy) {
     wave_renew_instance(S, rec, rn, e, lane, xy);
+}
+
+// The same in two halves, for the form that also renews the sizes and changes them in between: renew_draw makes the instance,
+// renew_reload brings it into what the kernel keeps.  (wave_renew_instance above keeps its one-piece text: the k_rn_* forms must
+// compile to what they compiled to before the size-renewing forms existed, and they do not when it is rebuilt from these two.)
+template <class SimT>
+__device__ __forceinline__ void renew_draw(const SimT& S, unsigned char* rec, const Renew& rn, int e, int lane, int& eA, int& eT) {
+    const Lay L = S.L();
+    Hdr* const live = (Hdr*)S.base;
+    const uint32_t n = uni(live->reserved) + 1u;
+    const uint64_t seed = uni(rn.seeds[e]) + (uint64_t)n * rn.stride;
+    const nps::Jump lane_j = nps::jump_coeffs((uint64_t)lane + 1);
+    wave_generate_instance<true>(seed, rn.g, lane_j, lane, live, (double*)(rec + L.tx()), (double*)(rec + L.ty()), (double*)(rec + L.tdur()),
+                                 (uint32_t*)(rec + L.tinfo()), eA, eT);
+    if (lane == 0) live->reserved = n;
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "agent");
+}
+template <class SimT>
+__device__ __forceinline__ void renew_reload(const SimT& S, unsigned char* rec, int lane, typename SimT::XY& xy) {
+    const Lay L = S.L();
+    const unsigned long long* const gx = (const unsigned long long*)(rec + L.tx());
+    const unsigned long long* const gy = (const unsigned long long*)(rec + L.ty());
+    const unsigned long long* const gd = (const unsigned long long*)(rec + L.tdur());
+    const uint32_t* const gi = (const uint32_t*)(rec + L.tinfo());
+    auto gload = [](const unsigned long long* q) {
+        return __longlong_as_double((long long)__hip_atomic_load(q, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
+    };
+    S.for_tasks(lane, [&](int t) {
+        S.tinfo()[t] = __hip_atomic_load(gi + t, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        S.tdur()[t] = gload(gd + t);
+        if constexpr (!SimT::IRB) { S.tx()[t] = gload(gx + t); S.ty()[t] = gload(gy + t); }
+    });
+    if constexpr (SimT::IRB) {
+#pragma unroll
+        for (int c = 0; c < SimT::NTC; c++) {
+            const int t = c * WAVE + lane < S.T() ? c * WAVE + lane : 0;
+            xy.x[c] = gload(gx + t);
+            xy.y[c] = gload(gy + t);
+        }
+    }
+    WSYNC();
+}
+// Size renewal (DCM_PARAM_RENEW_SIZES, a ragged generated batch): the size-renewing kernel forms (k_rs_*: see k_step.inc).  rn.g
+// carries the real ranges, so the draw gives the env's next sizes with its next instance -- eT first, then eA, then the instance,
+// what k_generate_instances does for that seed -- and the env becomes an (eA, eT) env: lane 0 writes the sizes to the handle's
+// size table (sizes[2e], sizes[2e + 1]: where every getter, dcm_observe and the next launch read them), and the instance is
+// reloaded under the new sizes.  Returns them packed, eA | eT << 16 (wave-uniform; by value, so that the out-of-line form does
+// not force the caller's simulator into memory): the CALLER puts them into every copy of the simulator it holds (Sim::rA / rT,
+// the copy inside Fast / FastG) and re-derives what it derived from the old ones -- lane ownership (Fast::init), observation row
+// pointers, the padding rows (write_pad_obs) -- before reset_state.
+// The abandonment count table: its spill check and clear (Sim::clear_spilled_counts) run here, FIRST, with the finished
+// episode's sizes -- reset_state, which runs under the new ones, would miss agents beyond the new A and would not clear the old
+// a * T + t layout in full.  reset_state's own check then sees stale counters of the agents both episodes have and at most clears
+// an already clean table again.
+template <class SimT>
+__device__ __forceinline__ uint32_t wave_renew_instance_sized(const SimT& S, unsigned char* rec, const Renew& rn, int32_t* sizes, int e,
+                                                              int lane, typename SimT::XY& xy) {
+    static_assert(!SimT::EXACT, "size renewal needs an instantiation that reads per-env sizes");
+    S.clear_spilled_counts(lane);
+    int eA, eT;
+    renew_draw(S, rec, rn, e, lane, eA, eT);
+    if (lane == 0) { sizes[2 * e] = eA; sizes[2 * e + 1] = eT; }
+    SimT N = S;
+    N.rA = eA; N.rT = eT;
+    renew_reload(N, rec, lane, xy);
+    return (uint32_t)eA | ((uint32_t)eT << 16);
+}
+template <class SimT>
+__device__ __noinline__ uint32_t wave_renew_instance_sized_call(const SimT& S, unsigned char* rec, const Renew& rn, int32_t* sizes, int e,
+                                                                int lane, typename SimT::XY& xy) {
+    return wave_renew_instance_sized(S, rec, rn, sizes, e, lane, xy);
+}
+// ... and the caller's part for a plain simulator: S takes the sizes (wave-uniform, in SGPRs)
+template <class SimT>
+__device__ __forceinline__ void take_sizes(SimT& S, uint32_t packed) {
+    packed = uni(packed);
+    S.rA = (int)(packed & 0xFFFFu); S.rT = (int)(packed >> 16);
 }
 
 #ifndef DCM_TU_G   // (the unit of k_rollout_fast_g needs the routines above only)

@@ -2,18 +2,27 @@
 // (DCM_RENEW 1), which has one more argument, Renew rn, and is launched while dcm_set_instance_renewal has set a stride: an env that
 // restarts an episode first replaces its instance (wave_renew_instance, instgen.hpp).  Two kernels from one text: the plain
 // form holds nothing of the renewal and compiles to the code it had without it (DESIGN 6).
-#if DCM_RENEW
+// A third form, k_rs_rollout_random (DCM_RENEW 2, DCM_PARAM_RENEW_SIZES), for the instantiations that read per-env sizes: on a ragged generated
+// batch the restarting env draws its next SIZES with its next instance (wave_renew_instance_sized) and carries on as an env of those
+// sizes: everything the kernel derived from the old ones at its head is derived again at the restart.  `sizes` is writable there.
+#if DCM_RENEW == 2
+#define KNAME k_rs_rollout_random
+#define KRENEW_PARAM , Renew rn
+#define KSIZES int32_t* sizes
+#elif DCM_RENEW
 #define KNAME k_rn_rollout_random
 #define KRENEW_PARAM , Renew rn
+#define KSIZES const int32_t* sizes
 #else
 #define KNAME k_rollout_random
 #define KRENEW_PARAM
+#define KSIZES const int32_t* sizes
 #endif
 template <int CA, int CT, bool RS, int MC = M>
 __global__ __launch_bounds__(WAVE, 3) void KNAME(int A, int T, int PA, int PT, KP P, unsigned char* state, int episodes,
                                                         float* agents_out, float* tasks_out, uint8_t* mask_out,
                                                         int64_t* steps_out, double* summary, uint16_t* ablog,
-                                                        const int32_t* sizes, int64_t budget_all, const int64_t* budget_in,
+                                                        KSIZES, int64_t budget_all, const int64_t* budget_in,
                                                         unsigned char* gscr, double* retlog, int retcap KRENEW_PARAM) {
     const int e = env_of_workgroup(), lane = threadIdx.x;
     int eA, eT;
@@ -52,7 +61,10 @@ __global__ __launch_bounds__(WAVE, 3) void KNAME(int A, int T, int PA, int PT, K
         if (h.flags & DCM_FLAG_DONE) {  // restart from the loaded instance; d keeps running
             if (h.flags & ROLLOUT_ERR) break;
             if (left == 0) break;       // budget spent at an episode boundary: the finished episode's results stay readable
-#if DCM_RENEW
+#if DCM_RENEW == 2
+            take_sizes(S, wave_renew_instance_sized_call(S, rec, rn, sizes, e, lane, xy));
+            if constexpr (RS || CA == 0) S.write_pad_obs(lane, BA, BT, ag, tk, mk);   // rows between the new and the old sizes
+#elif DCM_RENEW
             wave_renew_instance_call(S, rec, rn, e, lane, xy);
 #endif
             S.reset_state(h, lane);
@@ -98,3 +110,4 @@ __global__ __launch_bounds__(WAVE, 3) void KNAME(int A, int T, int PA, int PT, K
 }
 #undef KNAME
 #undef KRENEW_PARAM
+#undef KSIZES

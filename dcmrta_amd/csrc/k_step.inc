@@ -2,19 +2,28 @@
 // (DCM_RENEW 1), which has one more argument, Renew rn, and is launched while dcm_set_instance_renewal has set a stride: an env that
 // restarts an episode first replaces its instance (wave_renew_instance, instgen.hpp).  Two kernels from one text: the plain
 // form holds nothing of the renewal and compiles to the code it had without it (DESIGN 6).
-#if DCM_RENEW
+// A third form, k_rs_step (DCM_RENEW 2, DCM_PARAM_RENEW_SIZES), for the instantiations that read per-env sizes: on a ragged generated
+// batch the restarting env draws its next SIZES with its next instance (wave_renew_instance_sized) and carries on as an env of those
+// sizes: everything the kernel derived from the old ones at its head is derived again at the restart.  `sizes` is writable there.
+#if DCM_RENEW == 2
+#define KNAME k_rs_step
+#define KRENEW_PARAM , Renew rn
+#define KSIZES int32_t* sizes
+#elif DCM_RENEW
 #define KNAME k_rn_step
 #define KRENEW_PARAM , Renew rn
+#define KSIZES const int32_t* sizes
 #else
 #define KNAME k_step
 #define KRENEW_PARAM
+#define KSIZES const int32_t* sizes
 #endif
 template <int CA, int CT, bool RS, int MC = M>
 __global__ __launch_bounds__(WAVE) void KNAME(int A, int T, int PA, int PT, KP P, unsigned char* state, const int32_t* actions,
                                               const int32_t* leader_in, const int32_t* nfol_in, const int16_t* fol_in,
                                               float* agents_out, float* tasks_out, uint8_t* mask_out,
                                               int32_t* leader_out, uint8_t* active_out, double* summary, RouteLog log,
-                                              uint16_t* ablog, uint32_t mode, const int32_t* sizes, unsigned char* gscr,
+                                              uint16_t* ablog, uint32_t mode, KSIZES, unsigned char* gscr,
                                               uint32_t max_episodes, double* retlog, int retcap KRENEW_PARAM) {
     const int e = env_of_workgroup(), lane = threadIdx.x;
     int eA, eT;
@@ -60,9 +69,15 @@ __global__ __launch_bounds__(WAVE) void KNAME(int A, int T, int PA, int PT, KP P
             if ((mode & DCM_PARAM_AUTO_RESET) && (h.flags & DCM_FLAG_DONE) &&
                 !(h.flags & (DCM_FLAG_BAD_ACTION | DCM_FLAG_OVERFLOW | DCM_FLAG_BAD_LEADER | DCM_FLAG_BAD_INSTANCE)) &&
                 (max_episodes == 0 || uni(((const Hdr*)smem)->episodes) < max_episodes)) {
+#if DCM_RENEW == 2
+                // (every row of the batch shape: agents beyond the new A read length 0 as well)
+                if (log.len) for (int a = lane; a < BA; a += WAVE) log.len[(size_t)e * BA + a] = 0;
+                take_sizes(S, wave_renew_instance_sized(S, rec, rn, sizes, e, lane, xy));   // the observation and its padding below: new sizes
+#else
                 if (log.len) for (int a = lane; a < eA; a += WAVE) log.len[(size_t)e * BA + a] = 0;
 #if DCM_RENEW
                 wave_renew_instance(S, rec, rn, e, lane, xy);
+#endif
 #endif
                 S.reset_state(h, lane);
                 if (lane == 0) *S.dirty() = SimT::DIRTY_ALL;
@@ -162,3 +177,4 @@ __global__ __launch_bounds__(WAVE) void KNAME(int A, int T, int PA, int PT, KP P
 }
 #undef KNAME
 #undef KRENEW_PARAM
+#undef KSIZES

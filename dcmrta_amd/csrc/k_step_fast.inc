@@ -2,18 +2,27 @@
 // (DCM_RENEW 1), which has one more argument, Renew rn, and is launched while dcm_set_instance_renewal has set a stride: an env that
 // restarts an episode first replaces its instance (wave_renew_instance, instgen.hpp).  Two kernels from one text: the plain
 // form holds nothing of the renewal and compiles to the code it had without it (DESIGN 6).
-#if DCM_RENEW
+// A third form, k_rs_step_fast (DCM_RENEW 2, DCM_PARAM_RENEW_SIZES), for the instantiations that read per-env sizes: on a ragged generated
+// batch the restarting env draws its next SIZES with its next instance (wave_renew_instance_sized) and carries on as an env of those
+// sizes: everything the kernel derived from the old ones at its head is derived again at the restart.  `sizes` is writable there.
+#if DCM_RENEW == 2
+#define KNAME k_rs_step_fast
+#define KRENEW_PARAM , Renew rn
+#define KSIZES int32_t* sizes
+#elif DCM_RENEW
 #define KNAME k_rn_step_fast
 #define KRENEW_PARAM , Renew rn
+#define KSIZES const int32_t* sizes
 #else
 #define KNAME k_step_fast
 #define KRENEW_PARAM
+#define KSIZES const int32_t* sizes
 #endif
 template <int CA, int CT, bool RS>
 __global__ __launch_bounds__(WAVE, DCM_STEP_WAVES) void KNAME(int A, int T, int PA, int PT, KP P, unsigned char* state, const int32_t* actions,
                                                    float* agents_out, float* tasks_out, uint8_t* mask_out, int32_t* leader_out,
                                                    uint8_t* active_out, double* summary, uint16_t* ablog, uint32_t mode,
-                                                   const int32_t* sizes, unsigned char* gscr, uint32_t max_episodes, double* retlog,
+                                                   KSIZES, unsigned char* gscr, uint32_t max_episodes, double* retlog,
                                                    int retcap, unsigned char* side, uint32_t side_pitch, uint32_t* pendq, const unsigned char* init KRENEW_PARAM) {
     const int e = env_of_workgroup(), lane = threadIdx.x;
     int eA, eT;
@@ -254,7 +263,15 @@ __global__ __launch_bounds__(WAVE, DCM_STEP_WAVES) void KNAME(int A, int T, int 
                     // (behind the snapshot's reads of the old image -- LDS operations of a wave execute in order -- so that
                     //  k_terminal_flush computes the metrics of the instance the episode ran on; the host gives the renewing form no
                     //  restart image, which describes the instance dcm_reset saw: plan::step_restart_image)
+#if DCM_RENEW == 2
+                    // (nab above -- the rows of a parked snapshot -- keeps the finished episode's A; the host gives this form no
+                    //  snapshot buffer at all: plan::defer_terminal)
+                    take_sizes(S, wave_renew_instance_sized(S, rec, rn, sizes, e, lane, xy));
+                    f.S.rA = S.rA; f.S.rT = S.rT;
+                    f.init(lane);
+#else
                     wave_renew_instance(S, rec, rn, e, lane, xy);
+#endif
 #endif
                     S.reset_state(h, lane);
                     if (lane == 0) *S.dirty() = SimT::DIRTY_ALL;
@@ -280,3 +297,4 @@ __global__ __launch_bounds__(WAVE, DCM_STEP_WAVES) void KNAME(int A, int T, int 
 }
 #undef KNAME
 #undef KRENEW_PARAM
+#undef KSIZES

@@ -48,11 +48,30 @@ inline bool one_chunk_ok(const Shape& s) { return s.quiet && !s.wide && s.A <= L
 
 // Instance renewal (dcm_set_instance_renewal with a non-zero stride): the handle's instances must have come from
 // dcm_generate_instances (`generated`: the handle then holds the seeds and scalar arguments the next instances are drawn from), and the
-// batch must be uniform -- on a ragged one an env's sizes would change inside a launch, which the kernels do not do.
+// batch must be uniform -- on a ragged one an env's sizes would change inside a launch, which the k_rn_* forms do not do.
 inline bool renewal_ok(const Shape& s, bool generated) { return generated && !s.ragged; }
+// ... unless the handle opted in at dcm_create (DCM_PARAM_RENEW_SIZES): a ragged batch made by dcm_generate_instances then renews
+// its sizes with its instances.  (A loaded ragged batch has no seeds to draw from; a uniform batch is renewal_ok's.)
+inline bool renewal_sizes_ok(const Shape& s, bool generated, bool opted_in) { return generated && opted_in && s.ragged; }
+// Which form of a restarting kernel a launch takes: the plain one (k_*) without a stride, the renewing one (k_rn_*) with a stride
+// on a uniform batch, the size-renewing one (k_rs_*) with a stride on a ragged batch -- which dcm_set_instance_renewal only
+// accepts on a handle that opted in; the flag is asked again here so that an unflagged handle can never reach that form.
+// A ragged batch runs a runtime-size instantiation (sim_kind: *_RS, Runtime, RuntimeWide; rollout_kind: Fast, FastG or General,
+// never FastMc), and the k_rs_* forms exist for exactly those.
+enum class RenewForm { Plain, Instance, Sizes };
+inline RenewForm renew_form(const Shape& s, bool stride_set, bool opted_in) {
+    if (!stride_set) return RenewForm::Plain;
+    return (s.ragged && opted_in) ? RenewForm::Sizes : RenewForm::Instance;
+}
+// Deferred terminal metrics (k_step_fast parks the final record, k_terminal_flush computes its summary row later with the env's sizes
+// from the handle's size table): not for a size-renewing launch, after which the table holds the NEXT episode's sizes -- those
+// launches compute the metrics inline, as under stream capture.
+// (captured: a dcm_step of the handle has been captured into a graph; the caller has dealt with a capture in progress)
+inline bool defer_terminal(bool captured, RenewForm form) { return !captured && form != RenewForm::Sizes; }
 // k_step_fast restarts an auto-resetting env from a copy of the record dcm_reset left (dcm_env::init) when it has one and the terminal
 // metrics are deferred.  The copy describes the instance dcm_reset saw: with renewal on the kernel gets none and computes the
 // restart (reset_state + the first event) on the new instance.
+// (renewal: any renewing form, RenewForm::Instance or RenewForm::Sizes)
 inline bool step_restart_image(bool image_valid, bool deferred_terminal, bool renewal) { return image_valid && deferred_terminal && !renewal; }
 
 // dcm_rollout_random.  obs_all_or_none: all three observation buffers given, or none (a template argument of the fast kernels)

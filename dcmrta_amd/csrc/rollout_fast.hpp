@@ -494,3 +494,6 @@ constexpr uint32_t rollout_fast_lds_bytes(Lay L) {
 #define DCM_RENEW 1
 #include "k_rollout_fast.inc"
 #undef DCM_RENEW
+#define DCM_RENEW 2   // the size-renewing form (k_rs_*): runtime-size instantiations only
+#include "k_rollout_fast.inc"
+#undef DCM_RENEW

@@ -551,3 +551,6 @@ constexpr uint32_t rollout_fast_g_lds_bytes(Lay L) { return Sim<128, 256, true>:
 #define DCM_RENEW 1
 #include "k_rollout_fast_g.inc"
 #undef DCM_RENEW
+#define DCM_RENEW 2   // the size-renewing form (k_rs_*): runtime-size instantiations only
+#include "k_rollout_fast_g.inc"
+#undef DCM_RENEW

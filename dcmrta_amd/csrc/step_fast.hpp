@@ -33,6 +33,9 @@ constexpr uint32_t step_fast_lds_bytes(Lay L) {
 #define DCM_RENEW 1
 #include "k_step_fast.inc"
 #undef DCM_RENEW
+#define DCM_RENEW 2   // the size-renewing form (k_rs_*): runtime-size instantiations only
+#include "k_step_fast.inc"
+#undef DCM_RENEW
 
 
 // Reward + perf metrics (env/task_env.py:344-364,420-425, worker.py:103-108) of the episodes whose final records k_step_fast parked

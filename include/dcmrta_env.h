@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define DCM_ABI_VERSION 5 /* v3: dcm_build_id, dcm_set_visibility, dcm_load_instances validates req on the device; v4: dcm_set_replay_placement; v5: DCM_PARAM_WIDE_MEMBERS; still v5, additions only: dcm_generate_instances, dcm_get_instances, dcm_generator_draws, dcm_set_instance_renewal, dcm_instance_index */
+#define DCM_ABI_VERSION 5 /* v3: dcm_build_id, dcm_set_visibility, dcm_load_instances validates req on the device; v4: dcm_set_replay_placement; v5: DCM_PARAM_WIDE_MEMBERS; still v5, additions only: dcm_generate_instances, dcm_get_instances, dcm_generator_draws, dcm_set_instance_renewal, dcm_instance_index, DCM_PARAM_RENEW_SIZES */
 
 typedef struct dcm_env dcm_env; /* opaque */
 
@@ -103,6 +103,17 @@ typedef enum {
  * records are 96 * T bytes larger, every shape runs the runtime-size kernels, dcm_get_members returns ids_out[B][T][16], and route
  * replay (which has its own member_cap) is not available on it.  Injected follower lists still hold at most DCM_FOLLOWER_COLS. */
 #define DCM_PARAM_WIDE_MEMBERS 8u
+/* dcm_params.flags: size renewal.  With this flag dcm_set_instance_renewal also accepts a RAGGED batch made by
+ * dcm_generate_instances (a range with lo < hi: the reference's own training configuration, AGENTS_RANGE = (10, 20), TASKS_RANGE =
+ * (20, 50), parameters.py:15-16): an env that restarts an episode inside a kernel then draws its next instance WITH its next sizes --
+ * TaskEnv(agents_range, tasks_range, ..., seed = inst_seeds[e] + (n + 1) * stride), the number of tasks first, then the number of
+ * agents, then the instance (env/task_env.py:58-71) -- and carries on as an env of those sizes.  The handle's per-env sizes then
+ * change inside launches: dcm_get_instances returns the sizes of the instance an env holds now, observation rows beyond them are
+ * padding, getters follow them, and they are part of a snapshot (see dcm_state_bytes).  Episode ends of such launches compute their
+ * summary rows inline (no lazy rows, see DCM_PARAM_AUTO_RESET).  Without the flag, and on every other batch of a flagged handle,
+ * nothing changes: a uniform generated batch renews exactly as on an unflagged handle, a ragged batch from
+ * dcm_load_instances_ragged is still refused. */
+#define DCM_PARAM_RENEW_SIZES 16u
 
 typedef struct {
     int32_t n_envs;             /* B */
@@ -172,12 +183,16 @@ int dcm_get_instances(dcm_env *env, double *depot, double *task_xy, int32_t *req
  * reset + clear_decisions and the first event as always.  With stride = B and seeds base + 0..B-1, episode k of env e plays instance
  * base + k * B + e.  stride == 0 (the default) turns renewal off: behaviour is then exactly that of a handle that never set it.
  * Valid only while the handle's instances came from dcm_generate_instances and the batch is uniform; otherwise DCM_ERR_STATE, and
- * nothing changes.  A ragged batch (a range with lo < hi) is refused: an env's sizes would change inside a launch, which is out of
- * scope.  dcm_load_instances[_ragged] and a new dcm_generate_instances turn renewal off.
+ * nothing changes.  A ragged batch (a range with lo < hi) is refused, because an env's sizes would change inside a launch -- unless
+ * the handle was created with DCM_PARAM_RENEW_SIZES: a ragged batch made by dcm_generate_instances is then accepted, and a
+ * restarting env draws its next sizes with its next instance (see the flag; its sizes in the handle's table move with it, and an
+ * env that does not renew -- below -- keeps the sizes of the episode it finished).  A ragged batch from dcm_load_instances_ragged
+ * is refused with or without the flag.  dcm_load_instances[_ragged] and a new dcm_generate_instances turn renewal off.
  * What does not renew: dcm_reset restarts the instance the record holds and leaves the index alone; an env that stops at an episode
  * boundary -- the last of a call's `episodes`, a spent decision budget, the auto_reset_episodes limit, an error flag -- keeps the
  * finished episode's instance and results until a later call restarts it, so every getter stays valid for that episode.  The
- * index lives in the env's record: dcm_clone_state / dcm_restore_state carry it with the instance, and dcm_state_bytes is unchanged.
+ * index lives in the env's record: dcm_clone_state / dcm_restore_state carry it with the instance, and dcm_state_bytes is unchanged
+ * (on a DCM_PARAM_RENEW_SIZES handle with a ragged batch the per-env sizes are carried as well: see dcm_state_bytes).
  * The seeds, the generator's arguments and the stride are the handle's and are not part of a snapshot: dcm_restore_state leaves them
  * and the setting as they are, so restore only snapshots of the instances the handle's last dcm_generate_instances made (or of
  * their renewals) while a stride is set -- a snapshot from before that call, or of loaded instances, would renew from seeds that are
@@ -302,7 +317,11 @@ int dcm_get_members(dcm_env *env, int16_t *ids_out, void *stream);
 int dcm_get_abandoned(dcm_env *env, uint16_t *counts_out, void *stream);
 
 /* copy.deepcopy(env) (worker.py:33): snapshot / restore of the mutable SoA state.
- * dcm_state_bytes gives the buffer size (device memory) needed for all B envs. */
+ * dcm_state_bytes gives the buffer size (device memory) needed for all B envs.
+ * Size renewal: while a DCM_PARAM_RENEW_SIZES handle holds a ragged batch, its per-env sizes change with the instances, so they
+ * are part of the snapshot -- 8 * B more bytes at its end -- and dcm_restore_state brings them back with the records; dcm_state_bytes
+ * reports the larger size.  Ask again after the batch changes between uniform and ragged, and restore a snapshot only into the
+ * kind of batch it was taken from.  Handles without the flag are unchanged: their sizes never change after the load. */
 int dcm_state_bytes(dcm_env *env, size_t *bytes_out);
 int dcm_clone_state(dcm_env *env, void *dst, void *stream);
 int dcm_restore_state(dcm_env *env, const void *src, void *stream);
