@@ -235,13 +235,37 @@ __device__ __forceinline__ uint64_t key1(uint64_t seed, uint64_t d) { return mix
 __device__ __forceinline__ int below(uint32_t r, int n) { return (int)(((uint64_t)r * (uint64_t)(uint32_t)n) >> 32); }
 
 // ---------------------------------------------------------------------------------- wave reductions (DPP)
+// One DPP move of an fp64 value for the reductions below.  A lane WITHOUT a source (the first 1/2/4/8 lanes of a row under row_shr,
+// the rows outside ROWMASK under row_bcast) gets an UNSPECIFIED value: the move has no `old` operand (v_mov_b32_dpp alone; tying
+// `old` to the value itself cost two v_mov_b32 + an s_nop in front of every stage of a serially dependent chain).
+// INVARIANT the reductions rely on: they read ONLY their last lane (15, 31 or 63), and that lane never depends on a lane without a
+// source.  row_shr:s is applied with s = 1, 2, 4, 8: before the stage, lane l of a row holds the reduction of lanes max(0, l-s+1)..l
+// when l >= s-1 and is unspecified below that; lane 15 reads lane 15-s >= s-1 (14, 13, 11, 7), a specified lane, so after the four
+// stages lane 15 of every row holds the reduction of its whole row, whatever the low lanes hold.  row_bcast:15 (ROWMASK 0xA) writes rows 1 and 3 from
+// lane 15 of rows 0 and 2, leaving rows 0 and 2 unspecified; row_bcast:31 (ROWMASK 0xC) then reads lane 31, in row 1, into rows 2
+// and 3, and the lane that is read afterwards is 31 or 63: rows 0 and 2 never reach it.
+// Nothing else may use this helper: a scan that reads other lanes needs dpp_f64_tied.
 template <int CTRL, int ROWMASK>
-__device__ __forceinline__ double dpp_f64(double v) {
+__device__ __forceinline__ double dpp_f64_lastlane(double v) {
+    const int lo = __builtin_amdgcn_mov_dpp(__double2loint(v), CTRL, ROWMASK, 0xF, false);
+    const int hi = __builtin_amdgcn_mov_dpp(__double2hiint(v), CTRL, ROWMASK, 0xF, false);
+    return __hiloint2double(hi, lo);
+}
+// The same move, correct on EVERY lane: a lane without a source keeps its own value (`old` tied to the value).
+template <int CTRL, int ROWMASK>
+__device__ __forceinline__ double dpp_f64_tied(double v) {
     int lo = __double2loint(v), hi = __double2hiint(v);
-    lo = __builtin_amdgcn_update_dpp(lo, lo, CTRL, ROWMASK, 0xF, false);  // lanes without a source keep their own value
+    lo = __builtin_amdgcn_update_dpp(lo, lo, CTRL, ROWMASK, 0xF, false);
     hi = __builtin_amdgcn_update_dpp(hi, hi, CTRL, ROWMASK, 0xF, false);
     return __hiloint2double(hi, lo);
 }
+// The move the reductions are built from.  The route-replay unit (dcmrta_replay.hip defines DCM_REDUCE_TIED_DPP) keeps the tied
+// one: k_replay_fast, compiled without max-ilp, measured 0.15 % slower in every round of an interleaved A/B with the other.
+#ifdef DCM_REDUCE_TIED_DPP
+#define DPP_RED dpp_f64_tied
+#else
+#define DPP_RED dpp_f64_lastlane
+#endif
 // v_min_f64 / v_max_f64 return the other operand when one is a quiet NaN (IEEE minNum/maxNum) and are
 // exact; written as asm so the compiler does not add a canonicalising v_max_f64 x,x in front of each.
 __device__ __forceinline__ double nanmin2(double a, double b) {
@@ -256,12 +280,12 @@ __device__ __forceinline__ double nanmax2(double a, double b) {
 }
 // NaN-ignoring minimum over the wave (np.nanmin), NaN when every lane is NaN.
 __device__ __forceinline__ double wave_nanmin(double v) {
-    v = nanmin2(v, dpp_f64<0x111, 0xF>(v));  // row_shr:1
-    v = nanmin2(v, dpp_f64<0x112, 0xF>(v));  // row_shr:2
-    v = nanmin2(v, dpp_f64<0x114, 0xF>(v));  // row_shr:4
-    v = nanmin2(v, dpp_f64<0x118, 0xF>(v));  // row_shr:8  -> lane 15 of each row holds the row minimum
-    v = nanmin2(v, dpp_f64<0x142, 0xA>(v));  // row_bcast:15 into rows 1,3
-    v = nanmin2(v, dpp_f64<0x143, 0xC>(v));  // row_bcast:31 into rows 2,3 -> lane 63 holds the wave minimum
+    v = nanmin2(v, DPP_RED<0x111, 0xF>(v));  // row_shr:1
+    v = nanmin2(v, DPP_RED<0x112, 0xF>(v));  // row_shr:2
+    v = nanmin2(v, DPP_RED<0x114, 0xF>(v));  // row_shr:4
+    v = nanmin2(v, DPP_RED<0x118, 0xF>(v));  // row_shr:8  -> lane 15 of each row holds the row minimum
+    v = nanmin2(v, DPP_RED<0x142, 0xA>(v));  // row_bcast:15 into rows 1,3
+    v = nanmin2(v, DPP_RED<0x143, 0xC>(v));  // row_bcast:31 into rows 2,3 -> lane 63 holds the wave minimum
     const int lo = __builtin_amdgcn_readlane(__double2loint(v), 63), hi = __builtin_amdgcn_readlane(__double2hiint(v), 63);
     return __hiloint2double(hi, lo);
 }
@@ -269,22 +293,22 @@ __device__ __forceinline__ double wave_nanmin(double v) {
 template <int NL>
 __device__ __forceinline__ double wave_nanmin_n(double v) {
     if constexpr (NL > 32) return wave_nanmin(v);
-    v = nanmin2(v, dpp_f64<0x111, 0xF>(v));
-    v = nanmin2(v, dpp_f64<0x112, 0xF>(v));
-    v = nanmin2(v, dpp_f64<0x114, 0xF>(v));
-    v = nanmin2(v, dpp_f64<0x118, 0xF>(v));                    // lane 15 / 31: minimum of row 0 / 1
-    if constexpr (NL > 16) v = nanmin2(v, dpp_f64<0x142, 0xA>(v));   // row_bcast:15 -> lane 31: minimum of rows 0 and 1
+    v = nanmin2(v, DPP_RED<0x111, 0xF>(v));
+    v = nanmin2(v, DPP_RED<0x112, 0xF>(v));
+    v = nanmin2(v, DPP_RED<0x114, 0xF>(v));
+    v = nanmin2(v, DPP_RED<0x118, 0xF>(v));                    // lane 15 / 31: minimum of row 0 / 1
+    if constexpr (NL > 16) v = nanmin2(v, DPP_RED<0x142, 0xA>(v));   // row_bcast:15 -> lane 31: minimum of rows 0 and 1
     constexpr int SRC = NL > 16 ? 31 : 15;
     const int lo = __builtin_amdgcn_readlane(__double2loint(v), SRC), hi = __builtin_amdgcn_readlane(__double2hiint(v), SRC);
     return __hiloint2double(hi, lo);
 }
 __device__ __forceinline__ double wave_nanmax(double v) {
-    v = nanmax2(v, dpp_f64<0x111, 0xF>(v));
-    v = nanmax2(v, dpp_f64<0x112, 0xF>(v));
-    v = nanmax2(v, dpp_f64<0x114, 0xF>(v));
-    v = nanmax2(v, dpp_f64<0x118, 0xF>(v));
-    v = nanmax2(v, dpp_f64<0x142, 0xA>(v));
-    v = nanmax2(v, dpp_f64<0x143, 0xC>(v));
+    v = nanmax2(v, DPP_RED<0x111, 0xF>(v));
+    v = nanmax2(v, DPP_RED<0x112, 0xF>(v));
+    v = nanmax2(v, DPP_RED<0x114, 0xF>(v));
+    v = nanmax2(v, DPP_RED<0x118, 0xF>(v));
+    v = nanmax2(v, DPP_RED<0x142, 0xA>(v));
+    v = nanmax2(v, DPP_RED<0x143, 0xC>(v));
     const int lo = __builtin_amdgcn_readlane(__double2loint(v), 63), hi = __builtin_amdgcn_readlane(__double2hiint(v), 63);
     return __hiloint2double(hi, lo);
 }

@@ -17,6 +17,7 @@
 // is the busiest resource, so what counts is the number of scalar instructions per agent step.  Like task_update,
 // agent_update is incremental after an agent_step (only the agents whose inputs the step changed are recomputed), each phase
 // issues its LDS reads back to back before it uses any of them, and wave-uniform words are NOT forced into SGPRs.
+#define DCM_REDUCE_TIED_DPP 1   // the wave reductions of this unit keep the tied DPP move (common.hpp, DPP_RED)
 #include "common.hpp"
 
 using namespace dcm;

@@ -142,10 +142,16 @@ __global__ __launch_bounds__(WAVE, 4) void KNAME(int A, int T, int PA, int PT, K
                 gd += GAMMA;
                 if (++ki == WAVE) { kv = mix64(gd + GAMMA * (uint64_t)lane); kv2 = mix64(kv + GAMMA); ki = 0; if constexpr (use_prio) set_prio(ep); }
                 left--;
-                if (rlen == 0) {                                                  // worker.py:53 else same group, next leader
-                    CNT(8);
-                    if (h.cur_group < h.n_groups) { CNT(9); h.cur_group++; }                  // worker.py:52 next group
-                    else if (!f.next_event(r, h, P, lane)) { need_adv = true; break; }   // worker.py:85 -> :45
+                // worker.py:53 else same group, next leader.  The next-group step is an add, not a branch: as an arm of an
+                // if / else-if beside next_event() it shared a latch block with the event, whose task_update / agent_update results
+                // were then computed in shadow registers and copied back (11 v_mov behind every event, 8 of them 64-bit).
+                const bool more_groups = h.cur_group < h.n_groups;
+#ifdef DCM_COUNT_PATHS
+                if (rlen == 0) { CNT(8); if (more_groups) CNT(9); }
+#endif
+                h.cur_group += (rlen == 0 && more_groups) ? 1 : 0;                // worker.py:52 next group
+                if (rlen == 0 && !more_groups) {
+                    if (!f.next_event(r, h, P, lane)) { need_adv = true; break; }   // worker.py:85 -> :45
                 }
                 if (left == 0) break;
             }

@@ -79,9 +79,11 @@ __global__ __launch_bounds__(WAVE, DCM_MC_WAVES) void KNAME(int A, int T, int PA
                 if (h.flags & DCM_FLAG_DONE) break;
                 gd += GAMMA;
                 left--;
-                if (rlen == 0) {                                                  // worker.py:53 else same group, next leader
-                    if (h.cur_group < h.n_groups) h.cur_group++;                  // worker.py:52 next group
-                    else if (!f.next_event(r, h, P, lane)) { need_adv = true; break; }   // worker.py:85 -> :45
+                // worker.py:53 else same group, next leader; the next-group step branch-free (see k_rollout_fast.inc)
+                const bool more_groups = h.cur_group < h.n_groups;
+                h.cur_group += (rlen == 0 && more_groups) ? 1 : 0;                // worker.py:52 next group
+                if (rlen == 0 && !more_groups) {
+                    if (!f.next_event(r, h, P, lane)) { need_adv = true; break; }   // worker.py:85 -> :45
                 }
                 if (left == 0) break;
             }

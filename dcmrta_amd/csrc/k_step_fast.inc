@@ -170,10 +170,10 @@ __global__ __launch_bounds__(WAVE, DCM_STEP_WAVES) void KNAME(int A, int T, int 
                 const int rlen = f.apply(r, h, P, lane, k1, gm, leader, act_in);
                 h.d += 1;
                 regs = true;
-                if (rlen == 0) {                                                  // worker.py:53 else same group, next leader
-                    if (h.cur_group < h.n_groups) h.cur_group++;                  // worker.py:52 next group
-                    else general = !f.next_event(r, h, P, lane);                  // worker.py:85 -> :45
-                }
+                // worker.py:53 else same group, next leader; the next-group step branch-free (see k_rollout_fast.inc)
+                const bool more_groups = h.cur_group < h.n_groups;
+                h.cur_group += (rlen == 0 && more_groups) ? 1 : 0;                // worker.py:52 next group
+                if (rlen == 0 && !more_groups) general = !f.next_event(r, h, P, lane);   // worker.py:85 -> :45
             }
         }
         if (uni((uint32_t)general) != 0u) {

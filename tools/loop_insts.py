@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Static instruction census of a persistent kernel's DECISION loop (developer tool, build container: needs only hipcc).
 
-    python tools/loop_insts.py [-D...] [--kernel 'k_rollout_fast<20, 50, false, true>'] [--keep out.s] [--blocks]
+    python tools/loop_insts.py [-D...] [--kernel 'k_rollout_fast<20, 50, false, true, false>'] [--keep out.s] [--blocks]
 
 Compiles ONE explicit instantiation of the kernel (a scratch translation unit that includes dcmrta_env.hip with its host API
 compiled out: seconds instead of the minute the whole library takes), finds the decision loop -- the loop around decide()'s
@@ -60,7 +60,7 @@ def cheap(op):
 
 def main():
     args = sys.argv[1:]
-    kernel = "k_rollout_fast<20, 50, false, true>"
+    kernel = "k_rollout_fast<20, 50, false, true, false>"
     keep, blocks, defs, dump, phases, weights = None, False, [], None, False, None
     i = 0
     while i < len(args):
