@@ -17,6 +17,7 @@ MAX_MEMBERS = 5
 MAX_MEMBERS_WIDE = 16    # DCM_PARAM_WIDE_MEMBERS handles
 PARAM_NO_GROUPING, PARAM_AUTO_RESET, PARAM_STRICT_MASK, PARAM_WIDE_MEMBERS = 1, 2, 4, 8
 PARAM_RENEW_SIZES = 16    # set_instance_renewal also on a ragged generated batch: the sizes are renewed with the instances
+POLICY_RANDOM, POLICY_FIRST, POLICY_NEAREST = 0, 1, 2    # dcm_rollout_policy
 MAX_AGENTS = 128
 MAX_TASKS = 1023
 
@@ -54,6 +55,7 @@ SIGNATURES = {
     "dcm_observe": (C.c_int, [_vp] * 8),
     "dcm_step": (C.c_int, [_vp] * 11),
     "dcm_rollout_random": (C.c_int, [_vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),   # env, episodes, max_decisions, max_decisions_in, obs x3, steps, stream
+    "dcm_rollout_policy": (C.c_int, [_vp, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),   # env, policy, then as dcm_rollout_random
     "dcm_summary": (C.c_int, [_vp] * 3),
     "dcm_env_status": (C.c_int, [_vp] * 5),
     "dcm_get_tasks": (C.c_int, [_vp] * 10),

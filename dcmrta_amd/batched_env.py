@@ -210,7 +210,7 @@ class BatchedTaskEnv:
 
     def set_instance_renewal(self, stride):
         """A fresh instance at every episode restart (dcm_set_instance_renewal): with stride != 0 an env that restarts an episode
-        inside step() (auto_reset) or rollout_random() first replaces its instance by the one of seed seeds[b] + (n + 1) * stride
+        inside step() (auto_reset) or rollout() / rollout_random() first replaces its instance by the one of seed seeds[b] + (n + 1) * stride
         (mod 2**64; seeds = what generate_instances was given, n = instance_index()[b]) -- instances.renewal_seeds -- the way every
         reference Worker builds a new TaskEnv (worker.py:32).  With stride = B and seeds base + arange(B), episode k of env b plays
         instance base + k * B + b.  0 turns it off.  Needs a batch made by generate_instances (DcmError otherwise): a uniform one,
@@ -296,10 +296,21 @@ class BatchedTaskEnv:
         return self._obs() if observe else None
 
     def rollout_random(self, episodes=1, write_obs=True, max_decisions=-1):
-        """Config-2 hot path: `episodes` full random-policy episodes per env in one persistent launch.
+        """Config-2 hot path: `episodes` full random-policy episodes per env in one persistent launch: rollout("random", ...),
+        which see for max_decisions and the returned steps."""
+        return self.rollout("random", episodes, write_obs, max_decisions)
+
+    POLICIES = {"random": _lib.POLICY_RANDOM, "first": _lib.POLICY_FIRST, "nearest": _lib.POLICY_NEAREST}
+
+    def rollout(self, policy="random", episodes=1, write_obs=True, max_decisions=-1):
+        """`episodes` full episodes per env in one persistent launch under a device policy (dcm_rollout_policy): "random" (uniform
+        over the unmasked tasks: the config-2 hot path), "first" (the lowest unmasked task) or "nearest" (the unmasked task closest
+        to the deciding agent, ties to the lowest index).
         max_decisions: int (all envs) or int64[B] (numpy/torch) -- decision budget of this call (< 0 = unlimited); an env that
         runs out of budget stays at its pending decision, the obs buffers (obs()) hold what its last decision TAKEN saw.
         Returns steps int64[B] (device tensor)."""
+        if policy not in self.POLICIES:
+            raise DcmError("policy must be one of %s" % ", ".join(repr(p) for p in self.POLICIES))
         steps = torch.empty((self.B,), dtype=torch.int64, device=self.device)
         o = (self._agents, self._tasks, self._mask) if write_obs else (None, None, None)
         per_env = None
@@ -309,12 +320,12 @@ class BatchedTaskEnv:
                 raise DcmError("max_decisions must be an int or int64[B]")
             max_decisions = -1
         with torch.cuda.device(self.device):
-            check(self._lib.dcm_rollout_random(self._h, int(episodes), int(max_decisions), _ptr(per_env),
+            check(self._lib.dcm_rollout_policy(self._h, self.POLICIES[policy], int(episodes), int(max_decisions), _ptr(per_env),
                                                *[_ptr(x) for x in o], _ptr(steps), self._stream()))
         return steps
 
     def obs(self):
-        """The env's static observation buffers (written by the last observe / step / rollout_random call)."""
+        """The env's static observation buffers (written by the last observe / step / rollout / rollout_random call)."""
         return self._obs()
 
     # ------------------------------------------------------------------ results

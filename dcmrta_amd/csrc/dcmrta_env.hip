@@ -33,11 +33,20 @@ using namespace dcm;
 // and the unit of k_rollout_fast_g alone (-DDCM_TU_G) without that option -- it costs that kernel 4 % (8.19 -> 8.53 ms per 4096 x
 // 70A/130T launch) while it buys the one-chunk and the 50A/200T kernel 2.1 % / 1.3 %.  With neither macro (the developer tools'
 // one-command builds) everything is in one unit.
-#ifdef DCM_TU_G
+// A third unit (-DDCM_TU_P) holds the greedy-policy forms of the persistent kernels alone (k_hp_* / k_hprn_*, dcm_rollout_policy), with
+// the main unit's options: the main unit reaches them through dcm::launch_rollout_policy, and every kernel that existed before them
+// compiles from the text, and to the code, it had without them.
+#if defined(DCM_TU_G) || defined(DCM_TU_P)
 #define DCM_DEVICE_ONLY_TU 1
 #endif
+#if defined(DCM_TU_G) || (!defined(DCM_SPLIT_G) && !defined(DCM_TU_P))
+#define DCM_HAVE_FAST_G 1     // this unit holds k_rollout_fast_g and its launcher
+#endif
+#if defined(DCM_TU_P) || (!defined(DCM_SPLIT_G) && !defined(DCM_TU_G))
+#define DCM_HAVE_POLICY 1     // this unit holds the greedy-policy forms and their launcher
+#endif
 namespace dcm {
-#ifndef DCM_TU_G
+#if !defined(DCM_TU_G) && !defined(DCM_TU_P)
 thread_local char g_err[512] = "";
 int fail(int code, const char* fmt, const char* a, const char* b) {
     snprintf(g_err, sizeof(g_err), fmt, a, b);
@@ -57,9 +66,14 @@ struct RolloutArgs {
     unsigned char* gscr; double* retlog; int retcap;
     Renew rn;            // last argument of the renewing forms (k_rn_*, k_rs_*)
     plan::RenewForm form;  // which form the launch takes (plan::renew_form)
+    int policy = DCM_POLICY_RANDOM;   // last argument of the greedy-policy forms (k_hp_*, k_hprn_*)
 };
 // k_rollout_fast_g<NAC, NTC, OBS> / k_rn_rollout_fast_g / k_rs_rollout_fast_g (rollout_fast_g.hpp, its own translation unit)
 void launch_rollout_fast_g(int nac, int ntc, bool obs, unsigned grid, Lay L, hipStream_t stream, const RolloutArgs& a);
+// the greedy-policy forms k_hp_rollout_fast / k_hp_rollout_random and their renewing forms k_hprn_* (rollout_policy.hpp, their own
+// translation unit).  fast: plan::policy_rollout_kind said Fast; a.policy: DCM_POLICY_FIRST or DCM_POLICY_NEAREST; a.form: Plain or Instance
+int launch_rollout_policy(plan::SimKind kind, bool fast, bool obs, unsigned grid, Lay L, hipStream_t stream, const RolloutArgs& a);
+void allow_lds_policy(int lds);
 }  // namespace dcm
 
 namespace {
@@ -1150,6 +1164,58 @@ struct Sim {
         }
     }
 
+    // The greedy device policies (dcm_rollout_policy; policy_pick of the oracle): functions of the same unmasked tasks, no draw
+    // (protocol slot 1 is not consumed).  FIRST: the lowest unmasked task.  NEAREST: the unmasked task with the smallest fp64
+    // distance from the leader -- dist2, agent first, the ROUNDED distances compared (two different squares can round to one root)
+    // with strict <, so a tie goes to the lowest index.  Lane l walks tasks l, l + 64, ... in ascending order and keeps its first
+    // minimum; the wave minimum of the distances, then the wave minimum of the indices of the lanes that hold it, is the lowest
+    // index overall.  No unmasked task: the depot (0).  Instantiated by the k_hp_* kernel forms only.
+    __device__ __forceinline__ int pick_policy_action(int lane, int leader, int policy, const XY& xy) const {
+        const int T_ = T();
+        const double lx = ax()[leader], ly = ay()[leader];
+        const bool nearest = policy == DCM_POLICY_NEAREST;   // wave-uniform
+        double bd = __builtin_nan("");
+        int bt = 0x7FFFFFFF;
+        auto visit = [&](int t, int c) {                      // t = c * 64 + lane; every lane calls (ballot-free, but keeps fp64 work on all lanes)
+            const bool in = t < T_;
+            const int ts_ = in ? t : 0;
+            const uint32_t info = tinfo()[ts_];
+            const bool open = in && !(info & T_FEAS) && ((int)(int8_t)((info >> 8) & 0xFF) > 0);
+            double dd = 0.0;
+            if (nearest) {
+                double x, y;
+                if constexpr (IRB) {
+                    x = 0.; y = 0.;
+#pragma unroll
+                    for (int k = 0; k < NTC; k++) if (k == c) { x = xy.x[k]; y = xy.y[k]; }
+                } else { x = tx()[ts_]; y = ty()[ts_]; }
+                dd = dist2(lx, ly, x, y);
+            }
+            const bool better = open && (bt == 0x7FFFFFFF || dd < bd);
+            bd = better ? dd : bd;
+            bt = better ? t : bt;
+        };
+        if constexpr (CT != 0) {
+#pragma unroll
+            for (int c = 0; c < NTC; c++) visit(c * WAVE + lane, c);
+        } else {
+            for (int t0 = 0, c = 0; t0 < T_; t0 += WAVE, c++) visit(t0 + lane, c);
+        }
+        const bool have = bt != 0x7FFFFFFF;
+        if (__ballot(have) == 0ull) return 0;                // only the depot is unmasked
+        bool cand = have;
+        if (nearest) {
+            const double m = wave_nanmin(have ? bd : __builtin_nan(""));
+            cand = have && bd == m;
+        }
+        if constexpr (CT != 0 && CT <= 64) {
+            return __ffsll((unsigned long long)__ballot(cand));          // one chunk: lane = task, action = task + 1
+        } else {
+            const double mt = wave_nanmin(cand ? (double)bt : __builtin_nan(""));   // (indices below 2^10: exact in fp64)
+            return (mt == mt) ? (int)mt + 1 : 0;
+        }
+    }
+
     // TaskEnv.step (env/task_env.py:326-342) + agent_step (:300-324) for leader + followers, then
     // task_update / agent_update (worker.py:74-76) and the move to the next decision point.
     // DEV: the action comes from the device's own valid-action policy on a validated instance (persistent kernel): the error
@@ -1499,8 +1565,11 @@ constexpr uint32_t rollout_random_lds_bytes(Lay L) {
 #include "rollout_fast.hpp"
 #include "step_fast.hpp"
 #include "rollout_fast_mc.hpp"
-#if defined(DCM_TU_G) || !defined(DCM_SPLIT_G)
+#ifdef DCM_HAVE_FAST_G
 #include "rollout_fast_g.hpp"
+#endif
+#ifdef DCM_HAVE_POLICY
+#include "rollout_policy.hpp"
 #endif
 
 __global__ __launch_bounds__(WAVE) void k_env_status(int PA, int PT, int PC, const unsigned char* state, int B, uint32_t* flags_out,
@@ -1683,7 +1752,7 @@ void launch_rollout_rs(K kernel, dim3 grid, dim3 block, unsigned lds_bytes, hipS
 }
 }  // namespace
 
-#if defined(DCM_TU_G) || !defined(DCM_SPLIT_G)
+#ifdef DCM_HAVE_FAST_G
 void dcm::launch_rollout_fast_g(int nac, int ntc, bool obs, unsigned grid, Lay L, hipStream_t stream, const RolloutArgs& a) {
 #define CALLG(NAC, NTC, OBS)                                                                                                          \
     do {                                                                                                                              \
@@ -1697,6 +1766,65 @@ void dcm::launch_rollout_fast_g(int nac, int ntc, bool obs, unsigned grid, Lay L
 #undef CALLA
 #undef CALLT
 #undef CALLG
+}
+#endif
+
+#ifdef DCM_HAVE_POLICY
+namespace {
+// the greedy-policy forms take `policy` last (k_hp_*), behind the renewal argument in the renewing ones (k_hprn_*)
+template <class K>
+void launch_rollout_hp(K kernel, dim3 grid, dim3 block, unsigned lds_bytes, hipStream_t stream, const RolloutArgs& a) {
+    hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, a.A, a.T, a.PA, a.PT, a.kp, a.state, a.episodes, a.agents_out, a.tasks_out,
+                       a.mask_out, a.steps_out, a.summary, a.ablog, a.sizes, a.budget_all, a.budget_in, a.gscr, a.retlog, a.retcap, a.policy);
+}
+template <class K>
+void launch_rollout_hprn(K kernel, dim3 grid, dim3 block, unsigned lds_bytes, hipStream_t stream, const RolloutArgs& a) {
+    hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, a.A, a.T, a.PA, a.PT, a.kp, a.state, a.episodes, a.agents_out, a.tasks_out,
+                       a.mask_out, a.steps_out, a.summary, a.ablog, a.sizes, a.budget_all, a.budget_in, a.gscr, a.retlog, a.retcap, a.rn,
+                       a.policy);
+}
+template <class K>
+void allow_lds_hp(K kernel, int bytes) { (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes); }
+}  // namespace
+
+// Returns 0, or -1 when `kind` has no one-chunk kernel (the caller asked plan::policy_rollout_kind, so it has)
+int dcm::launch_rollout_policy(plan::SimKind kind, bool fast, bool obs, unsigned grid, Lay L, hipStream_t stream, const RolloutArgs& a) {
+    const bool renew = a.form == plan::RenewForm::Instance;
+    if (fast) {
+#define CALLF(CA, CT, RS, OBS)                                                                                                             \
+    do {                                                                                                                                   \
+        if (renew) launch_rollout_hprn(k_hprn_rollout_fast<CA, CT, RS, OBS>, dim3(grid), dim3(WAVE), rollout_fast_lds_bytes<CA, CT, RS>(L), stream, a); \
+        else launch_rollout_hp(k_hp_rollout_fast<CA, CT, RS, OBS>, dim3(grid), dim3(WAVE), rollout_fast_lds_bytes<CA, CT, RS>(L), stream, a);           \
+    } while (0)
+#define CALL(CA, CT, RS) do { if (obs) { CALLF(CA, CT, RS, true); } else { CALLF(CA, CT, RS, false); } } while (0)
+        switch (kind) { FOR_EACH_FAST(SIM_CASE) default: return -1; }
+#undef CALL
+#undef CALLF
+        return 0;
+    }
+#define CALL(CA, CT, RS, ...)                                                                                                              \
+    do {                                                                                                                                   \
+        if (renew) launch_rollout_hprn(k_hprn_rollout_random<CA, CT, RS, ##__VA_ARGS__>, dim3(grid), dim3(WAVE), rollout_random_lds_bytes<CA, CT, RS>(L), stream, a); \
+        else launch_rollout_hp(k_hp_rollout_random<CA, CT, RS, ##__VA_ARGS__>, dim3(grid), dim3(WAVE), rollout_random_lds_bytes<CA, CT, RS>(L), stream, a);           \
+    } while (0)
+    switch (kind) { FOR_EACH_INSTANCE(SIM_CASE) }
+#undef CALL
+    return 0;
+}
+// dcm_create: the greedy forms' share of the dynamic-LDS limit (see there)
+void dcm::allow_lds_policy(int lds) {
+#define SET_ATTR(KIND, CA, CT, RS, ...)                                  \
+    allow_lds_hp(k_hp_rollout_random<CA, CT, RS, ##__VA_ARGS__>, lds);   \
+    allow_lds_hp(k_hprn_rollout_random<CA, CT, RS, ##__VA_ARGS__>, lds);
+    FOR_EACH_INSTANCE(SET_ATTR)
+#undef SET_ATTR
+#define SET_FAST(KIND, CA, CT, RS)                                       \
+    allow_lds_hp(k_hp_rollout_fast<CA, CT, RS, true>, lds);              \
+    allow_lds_hp(k_hp_rollout_fast<CA, CT, RS, false>, lds);             \
+    allow_lds_hp(k_hprn_rollout_fast<CA, CT, RS, true>, lds);            \
+    allow_lds_hp(k_hprn_rollout_fast<CA, CT, RS, false>, lds);
+    FOR_EACH_FAST(SET_FAST)
+#undef SET_FAST
 }
 #endif
 
@@ -1875,6 +2003,7 @@ int dcm_create(const dcm_params* params, dcm_env** out) {
     allow_lds(k_rollout_fast_mc<50, 200, false>, lds);
     allow_lds(k_rn_rollout_fast_mc<50, 200, true>, lds);
     allow_lds(k_rn_rollout_fast_mc<50, 200, false>, lds);
+    dcm::allow_lds_policy(lds);
     allow_lds(k_get_tasks<M>, lds);
     allow_lds(k_get_agents<M>, lds);
     allow_lds(k_get_tasks<MW>, lds);
@@ -2245,6 +2374,36 @@ int dcm_rollout_random(dcm_env* env, int32_t episodes, int64_t max_decisions, co
         }
         break;
     }
+    LAUNCH_OK();
+    return DCM_OK;
+}
+
+int dcm_rollout_policy(dcm_env* env, int32_t policy, int32_t episodes, int64_t max_decisions, const int64_t* max_decisions_in,
+                       float* agents_out, float* tasks_out, uint8_t* mask_out, int64_t* steps_out, void* stream) {
+    if (policy == DCM_POLICY_RANDOM)
+        return dcm_rollout_random(env, episodes, max_decisions, max_decisions_in, agents_out, tasks_out, mask_out, steps_out, stream);
+    CHECK_ENV(env);
+    if (policy != DCM_POLICY_FIRST && policy != DCM_POLICY_NEAREST)
+        return fail(DCM_ERR_INVALID, "dcm_rollout_policy: unknown policy (DCM_POLICY_RANDOM, DCM_POLICY_FIRST, DCM_POLICY_NEAREST)");
+    if (!env->reset_done) return fail(DCM_ERR_STATE, "dcm_rollout_policy: call dcm_reset first");
+    if (episodes < 1) return fail(DCM_ERR_INVALID, "dcm_rollout_policy: episodes must be >= 1");
+    if (plan::policy_needs_budget(shape_of(env)) && !max_decisions_in && max_decisions < 0)
+        return fail(DCM_ERR_INVALID, "dcm_rollout_policy: with max_waiting_time <= 0 a greedy policy does not end its episodes (a dropped member takes "
+                                     "the same task again at the same time): give a decision budget");
+    if (!plan::policy_form_ok(launch_form(env)))
+        return fail(DCM_ERR_STATE, "dcm_rollout_policy: no greedy policy while a ragged batch renews its sizes (DCM_PARAM_RENEW_SIZES with a stride set): "
+                                   "clear the stride with dcm_set_instance_renewal(env, 0), or use DCM_POLICY_RANDOM");
+    DCM_TRY(dcm::flush_pending(env, stream));
+    const plan::RenewForm form = renewing_launch(env, stream);
+    dcm::RolloutArgs ra{DIMS(env), env->kp, env->state, (int)episodes, agents_out, tasks_out, mask_out, steps_out, env->summary,
+                        env->ablog, (const int32_t*)env->sizes, max_decisions, max_decisions_in, env->gscratch, env->retlog,
+                        (int)env->retcap, renew_args(env), form};
+    ra.policy = policy;
+    const bool all_obs = agents_out && tasks_out && mask_out, no_obs = !agents_out && !tasks_out && !mask_out;
+    const plan::Shape shape = shape_of(env);
+    const bool fast = plan::policy_rollout_kind(shape, all_obs || no_obs) == plan::Rollout::Fast;
+    if (dcm::launch_rollout_policy(plan::sim_kind(shape), fast, all_obs, (unsigned)env->p.n_envs, env->L, (hipStream_t)stream, ra) != 0)
+        return fail(DCM_ERR_STATE, "internal error: a one-chunk kernel on another layout");
     LAUNCH_OK();
     return DCM_OK;
 }

@@ -5,7 +5,26 @@
 // A third form, k_rs_rollout_fast (DCM_RENEW 2, DCM_PARAM_RENEW_SIZES), for the instantiations that read per-env sizes: on a ragged generated
 // batch the restarting env draws its next SIZES with its next instance (wave_renew_instance_sized) and carries on as an env of those
 // sizes: everything the kernel derived from the old ones at its head is derived again at the restart.  `sizes` is writable there.
+// The greedy-policy forms (DCM_POLICY defined; dcm_rollout_policy with DCM_POLICY_FIRST / DCM_POLICY_NEAREST): k_hp_rollout_fast and its
+// renewing form k_hprn_rollout_fast, the same text with one more wave-uniform argument, `policy`, and the action taken from it instead of
+// protocol slot 1.  Compiled in a translation unit of their own; the forms above hold nothing of them.  No size-renewing form.
+#ifdef DCM_POLICY
 #if DCM_RENEW == 2
+#error "no size-renewing greedy form"
+#endif
+#define KPOLICY_PARAM , int policy
+#else
+#define KPOLICY_PARAM
+#endif
+#if defined(DCM_POLICY) && DCM_RENEW
+#define KNAME k_hprn_rollout_fast
+#define KRENEW_PARAM , Renew rn
+#define KSIZES const int32_t* sizes
+#elif defined(DCM_POLICY)
+#define KNAME k_hp_rollout_fast
+#define KRENEW_PARAM
+#define KSIZES const int32_t* sizes
+#elif DCM_RENEW == 2
 #define KNAME k_rs_rollout_fast
 #define KRENEW_PARAM , Renew rn
 #define KSIZES int32_t* sizes
@@ -23,7 +42,7 @@ __global__ __launch_bounds__(WAVE, 4) void KNAME(int A, int T, int PA, int PT, K
                                                       float* agents_out, float* tasks_out, uint8_t* mask_out,
                                                       int64_t* steps_out, double* summary, uint16_t* ablog,
                                                       KSIZES, int64_t budget_all, const int64_t* budget_in,
-                                                      unsigned char* gscr, double* retlog, int retcap KRENEW_PARAM) {
+                                                      unsigned char* gscr, double* retlog, int retcap KRENEW_PARAM KPOLICY_PARAM) {
     const int e = env_of_workgroup(), lane = threadIdx.x;
     int eA, eT;
     env_dims<CA, CT, RS>(sizes, e, A, T, eA, eT);
@@ -137,7 +156,11 @@ __global__ __launch_bounds__(WAVE, 4) void KNAME(int A, int T, int PA, int PT, K
                 FPHK(f, 12);
                 CNT(0);
                 const uint64_t k1 = rl(kv, ki), k2 = rl(kv2, ki);
+#ifdef DCM_POLICY
+                const int rlen = f.decide_policy(r, h, P, lane, k1, agrow, tkrow, mkp, &k2, policy);
+#else
                 const int rlen = f.decide(r, h, P, lane, k1, agrow, tkrow, mkp, &k2, use_prio ? &nv_last : nullptr);
+#endif
                 if (h.flags & DCM_FLAG_DONE) break;
                 gd += GAMMA;
                 if (++ki == WAVE) { kv = mix64(gd + GAMMA * (uint64_t)lane); kv2 = mix64(kv + GAMMA); ki = 0; if constexpr (use_prio) set_prio(ep); }
@@ -183,3 +206,4 @@ __global__ __launch_bounds__(WAVE, 4) void KNAME(int A, int T, int PA, int PT, K
 #undef KNAME
 #undef KRENEW_PARAM
 #undef KSIZES
+#undef KPOLICY_PARAM

@@ -5,7 +5,26 @@
 // A third form, k_rs_rollout_random (DCM_RENEW 2, DCM_PARAM_RENEW_SIZES), for the instantiations that read per-env sizes: on a ragged generated
 // batch the restarting env draws its next SIZES with its next instance (wave_renew_instance_sized) and carries on as an env of those
 // sizes: everything the kernel derived from the old ones at its head is derived again at the restart.  `sizes` is writable there.
+// The greedy-policy forms (DCM_POLICY defined; dcm_rollout_policy with DCM_POLICY_FIRST / DCM_POLICY_NEAREST): k_hp_rollout_random and its
+// renewing form k_hprn_rollout_random, the same text with one more wave-uniform argument, `policy`, and the action taken from it instead of
+// protocol slot 1.  Compiled in a translation unit of their own; the forms above hold nothing of them.  No size-renewing form.
+#ifdef DCM_POLICY
 #if DCM_RENEW == 2
+#error "no size-renewing greedy form"
+#endif
+#define KPOLICY_PARAM , int policy
+#else
+#define KPOLICY_PARAM
+#endif
+#if defined(DCM_POLICY) && DCM_RENEW
+#define KNAME k_hprn_rollout_random
+#define KRENEW_PARAM , Renew rn
+#define KSIZES const int32_t* sizes
+#elif defined(DCM_POLICY)
+#define KNAME k_hp_rollout_random
+#define KRENEW_PARAM
+#define KSIZES const int32_t* sizes
+#elif DCM_RENEW == 2
 #define KNAME k_rs_rollout_random
 #define KRENEW_PARAM , Renew rn
 #define KSIZES int32_t* sizes
@@ -23,7 +42,7 @@ __global__ __launch_bounds__(WAVE, 3) void KNAME(int A, int T, int PA, int PT, K
                                                         float* agents_out, float* tasks_out, uint8_t* mask_out,
                                                         int64_t* steps_out, double* summary, uint16_t* ablog,
                                                         KSIZES, int64_t budget_all, const int64_t* budget_in,
-                                                        unsigned char* gscr, double* retlog, int retcap KRENEW_PARAM) {
+                                                        unsigned char* gscr, double* retlog, int retcap KRENEW_PARAM KPOLICY_PARAM) {
     const int e = env_of_workgroup(), lane = threadIdx.x;
     int eA, eT;
     env_dims<CA, CT, RS>(sizes, e, A, T, eA, eT);
@@ -50,7 +69,11 @@ __global__ __launch_bounds__(WAVE, 3) void KNAME(int A, int T, int PA, int PT, K
     // (wave-uniform branches otherwise, at every decision)
     const bool all_obs = agents_out && tasks_out && mask_out;
     double* row = summary + (size_t)e * 8;
+#ifdef DCM_POLICY
+    const int left0 = rollout_budget_policy(e, budget_all, budget_in, P);
+#else
     const int left0 = rollout_budget(e, budget_all, budget_in);
+#endif
     int left = left0;
     PH_DECL;
     // key_1 = mix64(seed + GAMMA (d+1)): the argument is carried and advanced by GAMMA per decision (no 64-bit multiply,
@@ -83,7 +106,11 @@ __global__ __launch_bounds__(WAVE, 3) void KNAME(int A, int T, int PA, int PT, K
             if (all_obs) { __builtin_assume(ag != nullptr); __builtin_assume(tk != nullptr); __builtin_assume(mk != nullptr); S.observe(h, lane, leader, ag, tk, mk, xy); }
             else S.observe(h, lane, leader, ag, tk, mk, xy);
             PH_MARK(1);
+#ifdef DCM_POLICY
+            const int action = S.pick_policy_action(lane, leader, policy, xy);
+#else
             const int action = S.pick_random_action(lane, k1);
+#endif
             PH_MARK(2);
             S.template apply_and_advance<true>(h, P, lane, leader, gm, action, k1, -1, nullptr, row PH_PASS, RouteLog{nullptr, nullptr, nullptr, 0}, 0, false, 0, true, false, &xy);
             gd += GAMMA;
@@ -111,3 +138,4 @@ __global__ __launch_bounds__(WAVE, 3) void KNAME(int A, int T, int PA, int PT, K
 #undef KNAME
 #undef KRENEW_PARAM
 #undef KSIZES
+#undef KPOLICY_PARAM

@@ -84,6 +84,18 @@ inline Rollout rollout_kind(const Shape& s, bool obs_all_or_none) {
     if (s.A <= 2 * LANES && s.T <= 4 * LANES && !one_chunk_layout) return Rollout::FastG;  // the mid-size class: rollout_fast_g.hpp
     return Rollout::General;
 }
+// dcm_rollout_policy with a greedy policy (DCM_POLICY_FIRST / DCM_POLICY_NEAREST).  The greedy kernel forms exist for the one-chunk
+// register-resident kernel and for the general one only: where rollout_kind says FastMc or FastG (50A/200T, the mid sizes) a greedy
+// launch takes the general kernel.  DCM_POLICY_RANDOM is dcm_rollout_random and asks rollout_kind.
+inline Rollout policy_rollout_kind(const Shape& s, bool obs_all_or_none) {
+    return rollout_kind(s, obs_all_or_none) == Rollout::Fast ? Rollout::Fast : Rollout::General;
+}
+// ... and there is no size-renewing greedy form: a launch that would take the k_rs_* form is refused under a greedy policy
+inline bool policy_form_ok(RenewForm form) { return form != RenewForm::Sizes; }
+// A greedy policy on a handle with max_waiting_time <= 0 does not end its episodes in general: a member that has waited 0 is dropped
+// at once (env/task_env.py:269), decides again at the same time and, the policy being a function of the state, takes the same task
+// again -- in the reference as here.  Such a launch must carry a decision budget (the scalar one, or per-env budgets).
+inline bool policy_needs_budget(const Shape& s) { return !s.quiet; }
 // k_rollout_fast_g<NAC, NTC>: lane chunks of agents (1..2) and of tasks (2..4) from the batch dims
 inline int fast_g_agent_chunks(int A) { return A > LANES ? 2 : 1; }
 inline int fast_g_task_chunks(int T) { return T > 3 * LANES ? 4 : (T > 2 * LANES ? 3 : 2); }

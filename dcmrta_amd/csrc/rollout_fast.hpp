@@ -324,6 +324,31 @@ struct Fast {
         FPH(2);
         return apply(r, h, P, lane, k1, gm, leader, action, k2p);
     }
+    // The same decision under a greedy device policy (dcm_rollout_policy, the k_hp_* kernel forms; `policy` wave-uniform): a
+    // function of the ballot observe() returns, protocol slot 1 is not consumed.  FIRST: the lowest unmasked task.  NEAREST: every
+    // task lane computes its own fp64 distance from the leader (dist2, agent first -- the routine agent_step travels by); the argmin
+    // is the NaN-ignoring wave minimum of the ROUNDED distances (masked lanes hold NaN) and a ballot of the lanes equal to it, whose
+    // lowest bit is the lowest task index: strict < in the oracle's policy_pick.  No unmasked task: the depot.
+    __device__ __forceinline__ int decide_policy(R& r, HdrRegs& h, const KP& P, int lane, uint64_t k1, float* agrow, float* tkrow, uint8_t* mkp,
+                                                 const uint64_t* k2p, int policy) const {
+        uint64_t gm;
+        int leader = pick_leader(r, h, k1, gm);
+        if (leader < 0) { h.flags |= DCM_FLAG_BAD_LEADER | DCM_FLAG_DONE; leader = 0; gm = 1ull; }
+        FPH(0);
+        const uint64_t bm = observe(r, h.now, leader, agrow, tkrow, mkp);
+        FPH(1);
+        uint64_t pick = bm;
+        if (policy == DCM_POLICY_NEAREST) {
+            const double lx = rl(r.ax, leader), ly = rl(r.ay, leader);
+            const double dd = dist2(lx, ly, r.tx, r.ty);
+            const bool open = (bm >> lane) & 1ull;
+            const double m = wave_nanmin_n<CT>(open ? dd : __builtin_nan(""));
+            pick = __ballot(open && dd == m);
+        }
+        const int action = __ffsll((unsigned long long)pick);                    // lowest set bit + 1 = the action; 0 = depot
+        FPH(2);
+        return apply(r, h, P, lane, k1, gm, leader, action, k2p);
+    }
     // TaskEnv.step :326-342 with the leader's (valid: unmasked task or depot) action, then task_update / agent_update
     __device__ __forceinline__ int apply(R& r, const HdrRegs& h, const KP& P, int lane, uint64_t k1, uint64_t gm, int leader, int action,
                                          const uint64_t* k2p = nullptr) const {

@@ -1,0 +1,33 @@
+// rollout_policy.hpp -- the greedy device policies of the persistent rollout (dcm_rollout_policy: DCM_POLICY_FIRST, DCM_POLICY_NEAREST).
+// Included by dcmrta_env.hip inside its anonymous namespace, after rollout_fast.hpp, in the translation unit of the greedy forms only
+// (-DDCM_TU_P, or a one-unit developer build).
+//
+// The forms are the existing kernel texts compiled once more ("two kernels from one text leave them as they were"):
+//   k_hp_rollout_fast   / k_hprn_rollout_fast    from k_rollout_fast.inc   (Fast<>::decide_policy)     one-chunk layouts
+//   k_hp_rollout_random / k_hprn_rollout_random  from k_rollout_random.inc (Sim<>::pick_policy_action)  every other launch
+// with one more wave-uniform argument, `policy`.  A kernel argument rather than a template argument: the two policies differ by one
+// distance chain and one wave minimum in front of the same ballot, and half as many kernels are compiled.  k_hprn_* renew a uniform
+// generated batch's instances at episode restarts like k_rn_*; there is no size-renewing form (the host refuses that launch), no
+// wave-priority (PRIO) instantiation -- its estimate of the work left is calibrated on the random policy's episodes -- and no greedy
+// form of k_rollout_fast_mc / k_rollout_fast_g: their shapes take k_hp_rollout_random (plan::policy_rollout_kind).
+#pragma once
+
+// The budget of a greedy launch.  With max_waiting_time <= 0 a greedy episode does not end in general (plan::policy_needs_budget), so
+// there "no limit" (a negative entry of max_decisions_in; the host refuses a negative scalar) counts as 0: the env takes no decision
+// in this launch instead of spinning at a constant clock.  (Only the general form runs on such a handle.)
+__device__ __forceinline__ int rollout_budget_policy(int e, int64_t budget_all, const int64_t* budget_in, const KP& P) {
+    const int64_t bud = budget_in ? budget_in[e] : budget_all;
+    const int left = rollout_budget(e, budget_all, budget_in);
+    return uni((!(P.mwt > 0.0) && bud < 0) ? 0 : left);
+}
+
+#define DCM_POLICY 1
+#define DCM_RENEW 0
+#include "k_rollout_random.inc"
+#include "k_rollout_fast.inc"
+#undef DCM_RENEW
+#define DCM_RENEW 1
+#include "k_rollout_random.inc"
+#include "k_rollout_fast.inc"
+#undef DCM_RENEW
+#undef DCM_POLICY

@@ -285,6 +285,29 @@ int dcm_set_return_log(dcm_env *env, double *returns, int32_t cap);
 int dcm_rollout_random(dcm_env *env, int32_t episodes, int64_t max_decisions, const int64_t *max_decisions_in,
                        float *agents_out, float *tasks_out, uint8_t *mask_out, int64_t *steps_out, void *stream);
 
+/* The same persistent launch under a device policy.  Every argument other than `policy` means what it means in dcm_rollout_random:
+ * the decision budget and the stop at a decision point with nothing applied, the per-decision observation stores, the restart
+ * between episodes (with dcm_set_instance_renewal: on the env's next instance), the return log and the summary rows.
+ *   DCM_POLICY_RANDOM   dcm_rollout_random itself: the same kernels, the same launch, the same results.
+ *   DCM_POLICY_FIRST    the lowest unmasked task.
+ *   DCM_POLICY_NEAREST  the unmasked task with the smallest fp64 Euclidean distance (env/task_env.py:161-163) from the deciding
+ *                       agent's position; a tie goes to the lowest task index (the rounded distances are compared, strict <).
+ * Both greedy policies take the depot (0) when no task is unmasked, like the random one.  Choice protocol: the leader (slot 0) and
+ * the followers (slots 2+j) are drawn as always, slot 1 is simply not consumed, the decision counter advances as before.
+ * An unknown policy: DCM_ERR_INVALID, nothing is launched.  A greedy policy while a ragged batch renews its SIZES
+ * (DCM_PARAM_RENEW_SIZES handle, ragged generated batch, stride set): DCM_ERR_STATE, nothing changes -- ragged batches without
+ * renewal, and uniform batches with it, work.
+ * On a handle with max_waiting_time <= 0 a greedy policy does not end its episodes in general -- a member that has waited 0 is dropped
+ * at once (env/task_env.py:269), decides again at the same time and takes the same task again, in the reference as here -- so such
+ * a launch must be bounded: max_decisions >= 0 or max_decisions_in given, else DCM_ERR_INVALID; a negative entry of max_decisions_in counts as 0
+ * there (the env takes no decision in the launch). */
+#define DCM_POLICY_RANDOM 0
+#define DCM_POLICY_FIRST 1
+#define DCM_POLICY_NEAREST 2
+int dcm_rollout_policy(dcm_env *env, int32_t policy, int32_t episodes, int64_t max_decisions,
+                       const int64_t *max_decisions_in, float *agents_out, float *tasks_out,
+                       uint8_t *mask_out, int64_t *steps_out, void *stream);
+
 /* Terminal results of the last finished episode (worker.py:87,103-108):
  * out[B,8] f64 = reward(-makespan), n_finished_tasks, success_rate, makespan, time_cost,
  *                waiting_time, travel_dist, efficiency. Rows of envs not yet done are NaN. */

@@ -1,0 +1,69 @@
+#!/usr/bin/env python3
+"""What the device policies of the persistent rollout cost and give: BatchedTaskEnv.rollout(policy, episodes=3) at 4096 x 20A/50T for
+"random", "first" and "nearest", each with renewal off (every episode on the instance the record holds) and on (a fresh instance at
+every restart, set_instance_renewal(B)).
+
+    python tools/policy_time.py [--reps 10] [--warmup 2]
+
+Each call starts from generate_instances + reset (outside the timed region), so every timed call plays the same episodes; a figure is
+the median of `reps` calls after `warmup`, host clock around one call that ends in a synchronise of the stream.  The episodes differ
+between policies in length and in their mix of paths (the greedy ones finish tasks, the random one mostly runs into MAX_TIME), so the
+time is reported with the decisions taken and per decision; for the greedy policies also the mean number of finished tasks and the
+mean makespan of the last episode (summary rows).  "random" runs the wave-priority instantiation of k_rollout_fast at this batch size,
+the greedy policies k_hp_rollout_fast, which has none.  Prints one JSON line per policy and mode; sets no threshold; needs a HIP device."""
+import argparse
+import json
+import os
+import statistics
+import sys
+import time
+
+import torch
+
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from dcmrta_amd.batched_env import BatchedTaskEnv  # noqa: E402
+from dcmrta_amd.choice import env_seeds  # noqa: E402
+
+B, A, T, EPISODES = 4096, 20, 50, 3
+
+
+def timed_rollouts(env, seeds, policy, stride, reps, warmup):
+    """(median seconds, decisions of one call) of rollout(policy, EPISODES) from a fresh generate_instances + reset."""
+    out, steps = [], 0
+    for i in range(warmup + reps):
+        env.generate_instances(0)
+        env.set_instance_renewal(stride)
+        env.reset(seeds, observe=False)
+        torch.cuda.synchronize(env.device)
+        t = time.perf_counter()
+        s = env.rollout(policy, episodes=EPISODES)
+        torch.cuda.synchronize(env.device)
+        if i >= warmup:
+            out.append(time.perf_counter() - t)
+        steps = int(s.sum())
+    return statistics.median(out), steps
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--reps", type=int, default=10)
+    ap.add_argument("--warmup", type=int, default=2)
+    ap.add_argument("--device", default="cuda:0")
+    args = ap.parse_args()
+    if args.reps < 1:
+        ap.error("--reps must be >= 1")
+    env = BatchedTaskEnv(B, A, T, device=args.device)
+    seeds = env_seeds(1, 0, B)
+    for policy in ("random", "first", "nearest"):
+        for mode, stride in (("off", 0), ("on", B)):
+            sec, steps = timed_rollouts(env, seeds, policy, stride, args.reps, args.warmup)
+            assert int(env.instance_index().min()) == int(env.instance_index().max()) == (EPISODES - 1 if stride else 0)
+            row = dict(shape=f"{B}x{A}A{T}T", policy=policy, renewal=mode, episodes=EPISODES, ms=round(sec * 1e3, 4), decisions=steps,
+                       ns_per_decision=round(sec * 1e9 / steps, 4), reps=args.reps)
+            sm = env.summary()
+            row.update(mean_finished_tasks=round(float(sm[:, 1].mean()), 3), mean_makespan=round(float(sm[:, 3].mean()), 3))
+            print(json.dumps(row), flush=True)
+
+
+if __name__ == "__main__":
+    main()
