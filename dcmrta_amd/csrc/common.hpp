@@ -330,6 +330,22 @@ __device__ __forceinline__ uint64_t rl(uint64_t v, int src) {
 }
 __device__ __forceinline__ uint32_t rl(uint32_t v, int src) { return (uint32_t)__builtin_amdgcn_readlane((int)v, src); }
 __device__ __forceinline__ int rli(int v, int src) { return __builtin_amdgcn_readlane(v, src); }
+// Lane predicates and their masks.  THE RULE of the register-resident kernels: a __ballot takes ONE direct compare (it then is the
+// bare v_cmp, whose SGPR-pair result is the mask); predicates are combined ON THE MASKS (s_and / s_or / s_andn2 on the scalar unit);
+// a per-lane constant (inT, inA, isD) enters as its mask (tm, am, 1 << 63), never as a bool inside the ballot's argument.  The
+// ballot of a logical combination makes the compiler materialise the combination -- which it already holds as an SGPR mask -- as a
+// 0/1 VGPR and compare that back (v_cndmask_b32 v, 0, 1, s[..] + v_cmp_ne_u32 s[..], 0, v: two VOP3 per ballot), and a lane-bit
+// test `(m >> lane) & 1` of a wave-uniform mask costs a 64-bit vector shift, an and and a compare.
+// lane_of(m): this lane's bit of the mask m as a predicate, with no VALU instruction: the SGPR pair is used as the condition of the
+// select / s_and_saveexec itself.  m MUST be wave-uniform (a ballot, or scalar arithmetic on ballots and other uniform values).
+__device__ __forceinline__ bool lane_of(uint64_t m) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return __builtin_amdgcn_inverse_ballot_w64(m);
+#else
+    (void)m;
+    return false;
+#endif
+}
 // value of a per-chunk register array at the wave-uniform position (chunk, lane): every chunk's lane is read, scalar selects pick
 // (branches around two v_readlane cost more than the reads)
 __device__ __forceinline__ uint32_t sel(bool c, uint32_t a, uint32_t b) { return c ? a : b; }

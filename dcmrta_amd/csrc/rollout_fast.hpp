@@ -104,8 +104,7 @@ struct Fast {
             auto ne = [](double a, double b) { return __double_as_longlong(a) != __double_as_longlong(b); };
             const int ch_ = (int)ne(r.ax, S.ax()[la]) | (int)ne(r.ay, S.ay()[la]) | (int)ne(r.arr, S.arr()[la]) | (int)ne(r.nd, S.nd()[la]) |
                             (int)ne(r.td, S.tdist()[la]) | (int)(r.cur != S.cur()[la]) | (int)(r.ai != S.ainfo()[la]);
-            const bool ch = inA && ch_ != 0;
-            achg = __ballot(ch);
+            achg = __ballot(ch_ != 0) & am;
         } }
         if (inA) {
             S.ax()[la] = r.ax; S.ay()[la] = r.ay; S.arr()[la] = r.arr; S.nd()[la] = r.nd; S.tdist()[la] = r.td;
@@ -135,25 +134,33 @@ struct Fast {
 #pragma unroll
         for (int j = 1; j < M; j++) mn = nanmin2(mn, av[j]);
         const bool le0 = status <= 0;                                            // :254
+        // The predicates live as wave-uniform masks (common.hpp, lane_of): every ballot is one direct compare, the combinations are
+        // scalar.  The lanes that own no task hold a copy of task 0's words (lt is clamped): whatever decides anything passes through
+        // tm -- `open` -- exactly where inT stood.
+        const uint64_t nfm = __ballot((info & T_FEAS) == 0u);                    // !feas0
+        const uint64_t open = nfm & tm;                                          // the tasks without a feasible assignment
+        const uint64_t le0m = __ballot(status <= 0);
         double mx = 0.0, thr = 0.0;
-        bool ok = false;
-        if (__ballot(inT && !feas0 && le0)) {
+        uint64_t okm = 0ull, sdrop = 0ull;
+        if (open & le0m) {
             mx = av[0];
 #pragma unroll
             for (int j = 1; j < M; j++) mx = nanmax2(mx, av[j]);
-            ok = le0 && (mx - mn <= mwt);                                        // :255
+            okm = le0m & __ballot(mx - mn <= mwt);                               // :255
             thr = mx - mwt;                                                      // :262
+            sdrop = open & le0m & ~okm & __ballot(mn <= thr);                    // the spread rule's leavers (none without such a task)
         }
+        const bool ok = lane_of(okm);
         // does any member leave?  (see Sim::task_update: decided on the earliest arrival alone)
-        const bool any_drop = inT && !feas0 && (le0 ? (!ok && mn <= thr) : (now - mn >= mwt));
-        const bool becomes = !feas0 && ok;                                       // :256-258
+        const uint64_t wdrop = open & ~le0m & __ballot(now - mn >= mwt);         // the waiting rule's
+        const uint64_t dmask = sdrop | wdrop;
+        const bool becomes = lane_of(nfm & okm);                                 // :256-258
         // time_start / time_finish change -- and are written through for agent_update's gather -- only when a task becomes feasible
         // (:256-257): wave-uniform test
-        const uint64_t bec = __ballot(becomes && inT);
+        const uint64_t bec = open & okm;
         double nts = r.ts, ntf = tfin;
         if (bec) { nts = becomes ? mx : nts; ntf = becomes ? mx + dur : ntf; }
         int nn = n;
-        const uint64_t dmask = __ballot(any_drop);
         if (dmask) {
             CNT(6 + site);
             FPM(20);
@@ -163,7 +170,7 @@ struct Fast {
             uint64_t gone = 0ull;
             // (which of the two removal rules is in play is wave-uniform almost always -- the spread rule fires ~3 times per
             //  episode -- so the per-slot tests of the other one are skipped by a scalar branch)
-            const bool any_spread = __ballot(any_drop && le0) != 0ull, any_wait = __ballot(any_drop && !le0) != 0ull;
+            const bool any_spread = sdrop != 0ull, any_wait = wdrop != 0ull;
             uint32_t spread = 0, q1 = 0;
             if (any_spread) {
 #pragma unroll
@@ -178,7 +185,7 @@ struct Fast {
                     prev = e;
                 }
             }
-            if (any_drop) {
+            if (lane_of(dmask)) {
                 const uint32_t drop = le0 ? spread : q1;                         // only listed slots can be set: unused ones hold NaN
                 const uint32_t keep = ((1u << n) - 1u) & ~drop;
                 // Compact the survivors in order, without a branch: vacate all slots, then every surviving member moves down to
@@ -216,7 +223,7 @@ struct Fast {
                 const int t = __ffsll((unsigned long long)todo) - 1;
                 todo &= todo - 1ull;
                 const uint64_t g = rl(gone, t);
-                if ((g >> lane) & 1ull) {                                        // this lane's agent was dropped by task t
+                if (lane_of(g)) {                                                // this lane's agent was dropped by task t
                     const uint32_t nth_ = r.ai >> 16;
                     r.ai += 1u << 16;
                     if (nth_ < (uint32_t)AB_CAP) r.ab[nth_] = (uint16_t)t;
@@ -236,9 +243,9 @@ struct Fast {
             r.ts = nts; r.tf = ntf;
             if (inT) { S.ts()[lt] = nts; S.tf()[lt] = ntf; }
             if constexpr (TRK) { dirty |= SimT::DIRTY_TIMES; dt_times |= bec; }
-            over_already = __ballot(becomes && inT && now >= ntf) != 0ull;
+            over_already = (bec & __ballot(now >= ntf)) != 0ull;
         }
-        const bool all_feasible = (__ballot(!(info & T_FEAS)) & tm) == 0ull;
+        const bool all_feasible = (__ballot((info & T_FEAS) == 0u) & tm) == 0ull;
         // (see Sim::task_update: a call can only change a task again at the same `now` if this one removed members or made a task
         //  feasible that is already over)
         calm = dmask == 0ull && !over_already;
@@ -281,11 +288,11 @@ struct Fast {
         }
         const uint32_t info = isD ? 0u : r.ti;
         const int status = (int)(int8_t)((info >> 8) & 0xFF);
-        const bool unfinished = !(info & T_FEAS) && status > 0;                  // :199
-        const uint64_t bm = __ballot(unfinished) & tm;
+        const uint64_t bm = __ballot((info & T_FEAS) == 0u) & __ballot(status > 0) & tm;   // unfinished :199
         if constexpr (OBS) {
-            // :193 per task; the depot's byte is False iff every task is masked (worker.py:58-61)
-            const bool zero = isD ? (bm == 0ull) : unfinished;
+            // :193 per task; the depot's byte is False iff every task is masked (worker.py:58-61): the depot lane's bit of bm is
+            // never set (T <= 63), it stands in for `every task is masked`
+            const bool zero = lane_of(bm | (bm == 0ull ? 1ull << DL : 0ull));
             const uint8_t mv = zero ? 0 : 1;
             const float g0 = (float)status, g1 = (float)(info & 0xFF), g2 = (float)r.dur;
             const float g3 = (float)(r.tx - lx), g4 = (float)(r.ty - ly);        // :185-188
@@ -341,9 +348,9 @@ struct Fast {
         if (policy == DCM_POLICY_NEAREST) {
             const double lx = rl(r.ax, leader), ly = rl(r.ay, leader);
             const double dd = dist2(lx, ly, r.tx, r.ty);
-            const bool open = (bm >> lane) & 1ull;
+            const bool open = lane_of(bm);
             const double m = wave_nanmin_n<CT>(open ? dd : __builtin_nan(""));
-            pick = __ballot(open && dd == m);
+            pick = bm & __ballot(dd == m);
         }
         const int action = __ffsll((unsigned long long)pick);                    // lowest set bit + 1 = the action; 0 = depot
         FPH(2);
@@ -366,11 +373,9 @@ struct Fast {
             const int vacancy = (int)(int8_t)(((uint32_t)__builtin_amdgcn_readlane((int)r.ti, tl) >> 8) & 0xFF);   // :327 (may be stale)
             const int nf = (vacancy > 1) ? ((vacancy - 1 < rlen) ? vacancy - 1 : rlen) : 0;   // :330-331
             uint64_t kk = k1;
-            for (int j = 0; j < nf; j++) {                                       // :331 choice without replacement
+            auto draw = [&](uint32_t rr) {
                 CNT(1);
                 FPM(22);
-                if ((j & 1) == 0) kk = (j == 0 && k2p) ? *k2p : mix64(kk + GAMMA);
-                const uint32_t rr = (j & 1) ? (uint32_t)kk : (uint32_t)(kk >> 32);
                 const int f = nth(rest, below(rr, rlen));
                 rest &= ~(1ull << f); rlen--;                                    // :332-333
                 mm |= 1ull << f;
@@ -379,6 +384,13 @@ struct Fast {
                 mypos = lane == f ? nm : mypos;
                 nm++;
                 FPM(23);
+            };
+            // :331 choice without replacement, two draws per trip: one key serves the draw from its high word and, if there is one,
+            // the draw from its low word
+            for (int j = 0; j < nf; j += 2) {
+                kk = (j == 0 && k2p) ? *k2p : mix64(kk + GAMMA);
+                draw((uint32_t)(kk >> 32));
+                if (j + 1 < nf) draw((uint32_t)kk);
             }
         }
         FPH(3);
@@ -389,7 +401,7 @@ struct Fast {
         double arrv = now + over_velocity(d);                                    // :315,:318
         asm volatile("" : "+v"(d), "+v"(arrv));
         FPH(4);
-        const bool mem = (mm >> lane) & 1ull;
+        const bool mem = lane_of(mm);
         uint64_t ids = 0ull; uint32_t kinfo = 0; int n = 0;
         int slot = 0;
         if (action) {
@@ -469,7 +481,7 @@ struct Fast {
         if (dm & (dm - 1ull)) {                                                  // more than one decider: all on one point?
             CNT(12);
             const double x0 = rl(r.ax, first), y0 = rl(r.ay, first);
-            same = __ballot(dec && !(r.ax == x0 && r.ay == y0)) == 0ull;
+            same = (dm & (__ballot(r.ax != x0) | __ballot(r.ay != y0))) == 0ull;   // (!= is true on NaN, like !(a == x && b == y))
         }
         if (same) {
             r.ai = (r.ai & ~A_GRP) | (dec ? (1u << 8) : 0u);
