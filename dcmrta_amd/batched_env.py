@@ -411,6 +411,40 @@ class BatchedTaskEnv:
         """(task[B,A,cap], arrival[B,A,cap], length[B,A]) recorded since the last reset."""
         return self._route
 
+    def enable_rollout_log(self, cap=64):
+        """Record every agent_step of the persistent launches (rollout / rollout_random, any policy; dcm_set_rollout_log) in buffers of
+        enable_route_log's layout.  They hold the LAST episode each env played: an env zeroes its lengths when it restarts an episode,
+        reset() zeroes all; after a budget stop in mid-episode they hold the prefix played and the next rollout() carries on.
+        step() never writes them, and rollout() never writes the enable_route_log ones.  cap = 0 / None disables."""
+        B, A, dev = self.B, self.A, self.device
+        if not cap:
+            check(self._lib.dcm_set_rollout_log(self._h, None, None, None, 0))
+            self._rollout_route = None
+        else:
+            bufs = (torch.full((B, A, cap), -2, dtype=torch.int16, device=dev),
+                    torch.zeros((B, A, cap), dtype=torch.float64, device=dev),
+                    torch.zeros((B, A), dtype=torch.int32, device=dev))
+            check(self._lib.dcm_set_rollout_log(self._h, *[_ptr(x) for x in bufs], int(cap)))
+            self._rollout_route = bufs
+        self.graph_epoch += 1
+        return self
+
+    def rollout_routes(self):
+        """(task[B,A,cap], arrival[B,A,cap], length[B,A]) of enable_rollout_log: the last episode each env played in rollout()."""
+        r = getattr(self, "_rollout_route", None)
+        if r is None:
+            raise DcmError("the rollout log is off: call enable_rollout_log(cap) first")
+        return r
+
+    def rollout_plan(self, b=None):
+        """The logged routes as the nested lists load_routes takes -- plan[b][a] = [action, ...] with 0 = depot, k = task k-1 -- for
+        every env, or for env b alone (plan[a]).  On a ragged batch the agents beyond an env's own size have empty lists.
+        ValueError, like route_lists, when a route is longer than the log's cap."""
+        from .trajectory import route_lists
+        task, arrival, length = (x.cpu().numpy() for x in self.rollout_routes())
+        one = lambda e: [[t + 1 for t in r] for r, _ in route_lists(task[e], arrival[e], length[e], "enable_rollout_log(cap)")]
+        return one(b) if b is not None else [one(e) for e in range(self.B)]
+
     # ------------------------------------------------------------------ route replay (env/task_env.py:562-599)
     def load_routes(self, routes, member_cap=8):
         """routes[b][a] = list of actions (0 = depot, k = task k-1) or None (pre_set_route stays None)."""

@@ -474,7 +474,7 @@ __device__ __forceinline__ void store_hdr(const HdrRegs& h, int lane) {
 
 // ---------------------------------------------------------------------------------- host side
 int fail(int code, const char* fmt, const char* a = "", const char* b = "");
-// the argument check of the route-log setters (dcm_set_route_log, dcm_set_replay_log): all three arrays and cap >= 1, or all NULL
+// the argument check of the route-log setters (dcm_set_route_log, dcm_set_replay_log, dcm_set_rollout_log): all three arrays and cap >= 1, or all NULL
 inline int make_route_log(const char* fn, int16_t* task, double* arrival, int32_t* len, int32_t cap, RouteLog* out) {
     const bool off = !task && !arrival && !len;
     if (!off && (!task || !arrival || !len || cap < 1))
@@ -538,6 +538,7 @@ struct dcm_env {
     int32_t replay_placement = 0;    // dcm_set_replay_placement: 0 auto, 1 replay scratch in LDS, 2 in HBM
     int32_t vis[4] = {20, 20, 10, 100};  // dynamic-arrival schedule: initial, batch, period, cap (env/task_env.py:567,:221)
     dcm::RouteLog log{nullptr, nullptr, nullptr, 0};   // dcm_set_route_log
+    dcm::RouteLog rollout_log{nullptr, nullptr, nullptr, 0};   // dcm_set_rollout_log: the persistent launches' log (len set = the logging kernel forms)
     // dcm_set_replay_log: route part (cap 0 = the replay log is off), final member lists [B][T][rlog_member_cols] and
     // feasible_assignment [B][T] (both nullable)
     dcm::RouteLog rlog{nullptr, nullptr, nullptr, 0};

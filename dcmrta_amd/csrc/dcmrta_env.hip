@@ -36,17 +36,22 @@ using namespace dcm;
 // A third unit (-DDCM_TU_P) holds the greedy-policy forms of the persistent kernels alone (k_hp_* / k_hprn_*, dcm_rollout_policy), with
 // the main unit's options: the main unit reaches them through dcm::launch_rollout_policy, and every kernel that existed before them
 // compiles from the text, and to the code, it had without them.
-#if defined(DCM_TU_G) || defined(DCM_TU_P)
+// A fourth unit (-DDCM_TU_L) holds the logging forms alone (k_lg_* / k_lgrn_*, dcm_set_rollout_log) in the same way: the main unit
+// reaches them through dcm::launch_rollout_log.
+#if defined(DCM_TU_G) || defined(DCM_TU_P) || defined(DCM_TU_L)
 #define DCM_DEVICE_ONLY_TU 1
 #endif
-#if defined(DCM_TU_G) || (!defined(DCM_SPLIT_G) && !defined(DCM_TU_P))
+#if defined(DCM_TU_G) || (!defined(DCM_SPLIT_G) && !defined(DCM_TU_P) && !defined(DCM_TU_L))
 #define DCM_HAVE_FAST_G 1     // this unit holds k_rollout_fast_g and its launcher
 #endif
-#if defined(DCM_TU_P) || (!defined(DCM_SPLIT_G) && !defined(DCM_TU_G))
+#if defined(DCM_TU_P) || (!defined(DCM_SPLIT_G) && !defined(DCM_TU_G) && !defined(DCM_TU_L))
 #define DCM_HAVE_POLICY 1     // this unit holds the greedy-policy forms and their launcher
 #endif
+#if defined(DCM_TU_L) || (!defined(DCM_SPLIT_G) && !defined(DCM_TU_G) && !defined(DCM_TU_P))
+#define DCM_HAVE_LOG 1        // this unit holds the logging forms and their launcher
+#endif
 namespace dcm {
-#if !defined(DCM_TU_G) && !defined(DCM_TU_P)
+#if !defined(DCM_TU_G) && !defined(DCM_TU_P) && !defined(DCM_TU_L)
 thread_local char g_err[512] = "";
 int fail(int code, const char* fmt, const char* a, const char* b) {
     snprintf(g_err, sizeof(g_err), fmt, a, b);
@@ -67,6 +72,7 @@ struct RolloutArgs {
     Renew rn;            // last argument of the renewing forms (k_rn_*, k_rs_*)
     plan::RenewForm form;  // which form the launch takes (plan::renew_form)
     int policy = DCM_POLICY_RANDOM;   // last argument of the greedy-policy forms (k_hp_*, k_hprn_*)
+    RouteLog lg{nullptr, nullptr, nullptr, 0};   // last argument of the logging forms (k_lg_*, k_lgrn_*), behind `policy`
 };
 // k_rollout_fast_g<NAC, NTC, OBS> / k_rn_rollout_fast_g / k_rs_rollout_fast_g (rollout_fast_g.hpp, its own translation unit)
 void launch_rollout_fast_g(int nac, int ntc, bool obs, unsigned grid, Lay L, hipStream_t stream, const RolloutArgs& a);
@@ -74,6 +80,10 @@ void launch_rollout_fast_g(int nac, int ntc, bool obs, unsigned grid, Lay L, hip
 // translation unit).  fast: plan::policy_rollout_kind said Fast; a.policy: DCM_POLICY_FIRST or DCM_POLICY_NEAREST; a.form: Plain or Instance
 int launch_rollout_policy(plan::SimKind kind, bool fast, bool obs, unsigned grid, Lay L, hipStream_t stream, const RolloutArgs& a);
 void allow_lds_policy(int lds);
+// the logging forms k_lg_rollout_fast / k_lg_rollout_random and their renewing forms k_lgrn_* (rollout_log.hpp, their own translation
+// unit).  fast: plan::log_rollout_kind said Fast; a.policy: any of the three; a.lg: the handle's rollout log; a.form: Plain or Instance
+int launch_rollout_log(plan::SimKind kind, bool fast, bool obs, unsigned grid, Lay L, hipStream_t stream, const RolloutArgs& a);
+void allow_lds_log(int lds);
 }  // namespace dcm
 
 namespace {
@@ -1539,6 +1549,15 @@ __device__ __forceinline__ int rollout_budget(int e, int64_t budget_all, const i
     return uni((int)((bud < 0 || bud >= NO_BUDGET) ? NO_BUDGET : bud));
 }
 
+// The budget of a greedy launch.  With max_waiting_time <= 0 a greedy episode does not end in general (plan::policy_needs_budget), so
+// there "no limit" (a negative entry of max_decisions_in; the host refuses a negative scalar) counts as 0: the env takes no decision
+// in this launch instead of spinning at a constant clock.  (Only the general form runs on such a handle.)
+__device__ __forceinline__ int rollout_budget_policy(int e, int64_t budget_all, const int64_t* budget_in, const KP& P) {
+    const int64_t bud = budget_in ? budget_in[e] : budget_all;
+    const int left = rollout_budget(e, budget_all, budget_in);
+    return uni((!(P.mwt > 0.0) && bud < 0) ? 0 : left);
+}
+
 // dynamic LDS of a k_rollout_random launch: the record image, or record + scratch for the layouts that keep the scratch in LDS
 template <int CA, int CT, bool RS>
 constexpr uint32_t rollout_random_lds_bytes(Lay L) {
@@ -1570,6 +1589,9 @@ constexpr uint32_t rollout_random_lds_bytes(Lay L) {
 #endif
 #ifdef DCM_HAVE_POLICY
 #include "rollout_policy.hpp"
+#endif
+#ifdef DCM_HAVE_LOG
+#include "rollout_log.hpp"
 #endif
 
 __global__ __launch_bounds__(WAVE) void k_env_status(int PA, int PT, int PC, const unsigned char* state, int B, uint32_t* flags_out,
@@ -1828,6 +1850,66 @@ void dcm::allow_lds_policy(int lds) {
 }
 #endif
 
+#ifdef DCM_HAVE_LOG
+namespace {
+// the logging forms take `policy` and the log last (k_lg_*), behind the renewal argument in the renewing ones (k_lgrn_*)
+template <class K>
+void launch_rollout_lg(K kernel, dim3 grid, dim3 block, unsigned lds_bytes, hipStream_t stream, const RolloutArgs& a) {
+    hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, a.A, a.T, a.PA, a.PT, a.kp, a.state, a.episodes, a.agents_out, a.tasks_out,
+                       a.mask_out, a.steps_out, a.summary, a.ablog, a.sizes, a.budget_all, a.budget_in, a.gscr, a.retlog, a.retcap, a.policy,
+                       a.lg);
+}
+template <class K>
+void launch_rollout_lgrn(K kernel, dim3 grid, dim3 block, unsigned lds_bytes, hipStream_t stream, const RolloutArgs& a) {
+    hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, a.A, a.T, a.PA, a.PT, a.kp, a.state, a.episodes, a.agents_out, a.tasks_out,
+                       a.mask_out, a.steps_out, a.summary, a.ablog, a.sizes, a.budget_all, a.budget_in, a.gscr, a.retlog, a.retcap, a.rn,
+                       a.policy, a.lg);
+}
+template <class K>
+void allow_lds_lg(K kernel, int bytes) { (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes); }
+}  // namespace
+
+// Returns 0, or -1 when `kind` has no one-chunk kernel (the caller asked plan::log_rollout_kind, so it has)
+int dcm::launch_rollout_log(plan::SimKind kind, bool fast, bool obs, unsigned grid, Lay L, hipStream_t stream, const RolloutArgs& a) {
+    const bool renew = a.form == plan::RenewForm::Instance;
+    if (fast) {
+#define CALLF(CA, CT, RS, OBS)                                                                                                             \
+    do {                                                                                                                                   \
+        if (renew) launch_rollout_lgrn(k_lgrn_rollout_fast<CA, CT, RS, OBS>, dim3(grid), dim3(WAVE), rollout_fast_lds_bytes<CA, CT, RS>(L), stream, a); \
+        else launch_rollout_lg(k_lg_rollout_fast<CA, CT, RS, OBS>, dim3(grid), dim3(WAVE), rollout_fast_lds_bytes<CA, CT, RS>(L), stream, a);           \
+    } while (0)
+#define CALL(CA, CT, RS) do { if (obs) { CALLF(CA, CT, RS, true); } else { CALLF(CA, CT, RS, false); } } while (0)
+        switch (kind) { FOR_EACH_FAST(SIM_CASE) default: return -1; }
+#undef CALL
+#undef CALLF
+        return 0;
+    }
+#define CALL(CA, CT, RS, ...)                                                                                                              \
+    do {                                                                                                                                   \
+        if (renew) launch_rollout_lgrn(k_lgrn_rollout_random<CA, CT, RS, ##__VA_ARGS__>, dim3(grid), dim3(WAVE), rollout_random_lds_bytes<CA, CT, RS>(L), stream, a); \
+        else launch_rollout_lg(k_lg_rollout_random<CA, CT, RS, ##__VA_ARGS__>, dim3(grid), dim3(WAVE), rollout_random_lds_bytes<CA, CT, RS>(L), stream, a);           \
+    } while (0)
+    switch (kind) { FOR_EACH_INSTANCE(SIM_CASE) }
+#undef CALL
+    return 0;
+}
+// dcm_create: the logging forms' share of the dynamic-LDS limit (see there)
+void dcm::allow_lds_log(int lds) {
+#define SET_ATTR(KIND, CA, CT, RS, ...)                                  \
+    allow_lds_lg(k_lg_rollout_random<CA, CT, RS, ##__VA_ARGS__>, lds);   \
+    allow_lds_lg(k_lgrn_rollout_random<CA, CT, RS, ##__VA_ARGS__>, lds);
+    FOR_EACH_INSTANCE(SET_ATTR)
+#undef SET_ATTR
+#define SET_FAST(KIND, CA, CT, RS)                                       \
+    allow_lds_lg(k_lg_rollout_fast<CA, CT, RS, true>, lds);              \
+    allow_lds_lg(k_lg_rollout_fast<CA, CT, RS, false>, lds);             \
+    allow_lds_lg(k_lgrn_rollout_fast<CA, CT, RS, true>, lds);            \
+    allow_lds_lg(k_lgrn_rollout_fast<CA, CT, RS, false>, lds);
+    FOR_EACH_FAST(SET_FAST)
+#undef SET_FAST
+}
+#endif
+
 #ifndef DCM_DEVICE_ONLY_TU   // (tools/loop_insts.py compiles single kernel instantiations of this file without the host API)
 namespace {
 constexpr uint32_t CU_LDS_BYTES = 160u * 1024u;
@@ -2004,6 +2086,7 @@ int dcm_create(const dcm_params* params, dcm_env** out) {
     allow_lds(k_rn_rollout_fast_mc<50, 200, true>, lds);
     allow_lds(k_rn_rollout_fast_mc<50, 200, false>, lds);
     dcm::allow_lds_policy(lds);
+    dcm::allow_lds_log(lds);
     allow_lds(k_get_tasks<M>, lds);
     allow_lds(k_get_agents<M>, lds);
     allow_lds(k_get_tasks<MW>, lds);
@@ -2164,6 +2247,8 @@ int dcm_reset(dcm_env* env, const uint64_t* seeds, void* stream) {
     LAUNCH_OK();
     if (env->log.len)
         HIP_TRY(hipMemsetAsync(env->log.len, 0, (size_t)env->p.n_envs * env->A * sizeof(int32_t), (hipStream_t)stream));
+    if (env->rollout_log.len)
+        HIP_TRY(hipMemsetAsync(env->rollout_log.len, 0, (size_t)env->p.n_envs * env->A * sizeof(int32_t), (hipStream_t)stream));
     env->reset_done = true;
     // the restart image of the register-resident lockstep kernel (dcm_env::init, read by k_step_fast only): what this reset produced
     env->init_valid = false;
@@ -2307,11 +2392,47 @@ int dcm_step(dcm_env* env, const int32_t* actions, const int32_t* leader_in, con
     return DCM_OK;
 }
 
+int dcm_set_rollout_log(dcm_env* env, int16_t* route_task, double* route_arrival, int32_t* route_len, int32_t cap) {
+    CHECK_HANDLE(env);
+    // (the register-resident logging forms address an env's [A][cap] block of route_arrival by a 32-bit byte offset)
+    if (cap > 0 && (uint64_t)env->A * (uint64_t)cap * sizeof(double) > 0xFFFFFFFFull)
+        return fail(DCM_ERR_INVALID, "dcm_set_rollout_log: cap too large (n_agents x cap x 8 bytes must stay below 4 GiB per env)");
+    return make_route_log("dcm_set_rollout_log", route_task, route_arrival, route_len, cap, &env->rollout_log);
+}
+
+namespace {
+// dcm_rollout_random / dcm_rollout_policy while the rollout log is set (dcm_set_rollout_log): the logging kernel forms, under any of
+// the three policies.  The caller has validated its arguments; `fn` names it in the refusal.
+int rollout_logged(dcm_env* env, const char* fn, int32_t policy, int32_t episodes, int64_t max_decisions, const int64_t* max_decisions_in,
+                   float* agents_out, float* tasks_out, uint8_t* mask_out, int64_t* steps_out, void* stream) {
+    if (!plan::log_form_ok(launch_form(env)))
+        return fail(DCM_ERR_STATE, "%s: no rollout log while a ragged batch renews its sizes (DCM_PARAM_RENEW_SIZES with a stride set): "
+                                   "clear the stride with dcm_set_instance_renewal(env, 0), or clear the log with dcm_set_rollout_log(env, NULL, NULL, NULL, 0)", fn);
+    DCM_TRY(dcm::flush_pending(env, stream));
+    const plan::RenewForm form = renewing_launch(env, stream);
+    dcm::RolloutArgs ra{DIMS(env), env->kp, env->state, (int)episodes, agents_out, tasks_out, mask_out, steps_out, env->summary,
+                        env->ablog, (const int32_t*)env->sizes, max_decisions, max_decisions_in, env->gscratch, env->retlog,
+                        (int)env->retcap, renew_args(env), form};
+    ra.policy = policy;
+    ra.lg = env->rollout_log;
+    const bool all_obs = agents_out && tasks_out && mask_out, no_obs = !agents_out && !tasks_out && !mask_out;
+    const plan::Shape shape = shape_of(env);
+    const bool fast = plan::log_rollout_kind(shape, all_obs || no_obs) == plan::Rollout::Fast;
+    if (dcm::launch_rollout_log(plan::sim_kind(shape), fast, all_obs, (unsigned)env->p.n_envs, env->L, (hipStream_t)stream, ra) != 0)
+        return fail(DCM_ERR_STATE, "internal error: a one-chunk kernel on another layout");
+    LAUNCH_OK();
+    return DCM_OK;
+}
+}  // namespace
+
 int dcm_rollout_random(dcm_env* env, int32_t episodes, int64_t max_decisions, const int64_t* max_decisions_in,
                        float* agents_out, float* tasks_out, uint8_t* mask_out, int64_t* steps_out, void* stream) {
     CHECK_ENV(env);
     if (!env->reset_done) return fail(DCM_ERR_STATE, "dcm_rollout_random: call dcm_reset first");
     if (episodes < 1) return fail(DCM_ERR_INVALID, "dcm_rollout_random: episodes must be >= 1");
+    if (env->rollout_log.len)
+        return rollout_logged(env, "dcm_rollout_random", DCM_POLICY_RANDOM, episodes, max_decisions, max_decisions_in, agents_out, tasks_out,
+                              mask_out, steps_out, stream);
     DCM_TRY(dcm::flush_pending(env, stream));
     // the renewing (k_rn_*) or size-renewing (k_rs_*) form of whichever kernel serves the handle, while a stride is set (dcm_set_instance_renewal)
     const plan::RenewForm form = renewing_launch(env, stream);
@@ -2390,6 +2511,9 @@ int dcm_rollout_policy(dcm_env* env, int32_t policy, int32_t episodes, int64_t m
     if (plan::policy_needs_budget(shape_of(env)) && !max_decisions_in && max_decisions < 0)
         return fail(DCM_ERR_INVALID, "dcm_rollout_policy: with max_waiting_time <= 0 a greedy policy does not end its episodes (a dropped member takes "
                                      "the same task again at the same time): give a decision budget");
+    if (env->rollout_log.len)
+        return rollout_logged(env, "dcm_rollout_policy", policy, episodes, max_decisions, max_decisions_in, agents_out, tasks_out, mask_out,
+                              steps_out, stream);
     if (!plan::policy_form_ok(launch_form(env)))
         return fail(DCM_ERR_STATE, "dcm_rollout_policy: no greedy policy while a ragged batch renews its sizes (DCM_PARAM_RENEW_SIZES with a stride set): "
                                    "clear the stride with dcm_set_instance_renewal(env, 0), or use DCM_POLICY_RANDOM");

@@ -8,15 +8,34 @@
 // The greedy-policy forms (DCM_POLICY defined; dcm_rollout_policy with DCM_POLICY_FIRST / DCM_POLICY_NEAREST): k_hp_rollout_fast and its
 // renewing form k_hprn_rollout_fast, the same text with one more wave-uniform argument, `policy`, and the action taken from it instead of
 // protocol slot 1.  Compiled in a translation unit of their own; the forms above hold nothing of them.  No size-renewing form.
+// The logging forms (DCM_LOG defined; a launch of either entry point while dcm_set_rollout_log is set): k_lg_rollout_fast and its
+// renewing form k_lgrn_rollout_fast, the same text with two more arguments: `policy`, which here covers all three policies (wave-
+// uniform: DCM_POLICY_RANDOM takes protocol slot 1 as the plain form does), and the log, to which Fast<>::apply appends where it
+// commits the member lanes.  Lane a keeps agent a's running length in a register (FastLog): loaded once at the head, zeroed at a
+// restart, written back once at the end -- nothing is loaded in the decision loop on the log's behalf.  Compiled in a translation
+// unit of their own; no size-renewing form.
+#if defined(DCM_LOG) && DCM_RENEW == 2
+#error "no size-renewing logging form"
+#endif
 #ifdef DCM_POLICY
 #if DCM_RENEW == 2
 #error "no size-renewing greedy form"
 #endif
 #define KPOLICY_PARAM , int policy
+#elif defined(DCM_LOG)
+#define KPOLICY_PARAM , int policy, RouteLog lg
 #else
 #define KPOLICY_PARAM
 #endif
-#if defined(DCM_POLICY) && DCM_RENEW
+#if defined(DCM_LOG) && DCM_RENEW
+#define KNAME k_lgrn_rollout_fast
+#define KRENEW_PARAM , Renew rn
+#define KSIZES const int32_t* sizes
+#elif defined(DCM_LOG)
+#define KNAME k_lg_rollout_fast
+#define KRENEW_PARAM
+#define KSIZES const int32_t* sizes
+#elif defined(DCM_POLICY) && DCM_RENEW
 #define KNAME k_hprn_rollout_fast
 #define KRENEW_PARAM , Renew rn
 #define KSIZES const int32_t* sizes
@@ -62,6 +81,10 @@ __global__ __launch_bounds__(WAVE, 4) void KNAME(int A, int T, int PA, int PT, K
     // (the launch asks for 512 bytes of LDS behind everything the general code uses: the dummy slots)
     F f{S, (double*)(smem + (SimT::SCR_IN_LDS ? L.lds_bytes() : SimT::lds_image_bytes(L)))};
     f.init(lane);
+#ifdef DCM_LOG
+    // the env's rows of the log: wave-uniform bases, the lane's entry addressed by a 32-bit offset (dcm_set_rollout_log bounds A x cap)
+    FastLog fl{lg.task + (size_t)e * BA * lg.cap, lg.arrival + (size_t)e * BA * lg.cap, lg.cap, f.inA ? lg.len[(size_t)e * BA + f.la] : 0};
+#endif
     float* agrow = nullptr; float* tkrow = nullptr; uint8_t* mkp = nullptr;
     if constexpr (OBS) {
         float* ag = agents_out + (size_t)e * 6 * BA;
@@ -137,6 +160,9 @@ __global__ __launch_bounds__(WAVE, 4) void KNAME(int A, int T, int PA, int PT, K
 #if DCM_RENEW
                 f.load_consts(r);
 #endif
+#ifdef DCM_LOG
+                fl.len = 0;                                                       // the log is the new episode's
+#endif
                 need_adv = true;
             }
         }
@@ -156,7 +182,9 @@ __global__ __launch_bounds__(WAVE, 4) void KNAME(int A, int T, int PA, int PT, K
                 FPHK(f, 12);
                 CNT(0);
                 const uint64_t k1 = rl(kv, ki), k2 = rl(kv2, ki);
-#ifdef DCM_POLICY
+#ifdef DCM_LOG
+                const int rlen = f.decide_logged(r, h, P, lane, k1, agrow, tkrow, mkp, &k2, policy, fl);
+#elif defined(DCM_POLICY)
                 const int rlen = f.decide_policy(r, h, P, lane, k1, agrow, tkrow, mkp, &k2, policy);
 #else
                 const int rlen = f.decide(r, h, P, lane, k1, agrow, tkrow, mkp, &k2, use_prio ? &nv_last : nullptr);
@@ -189,6 +217,9 @@ __global__ __launch_bounds__(WAVE, 4) void KNAME(int A, int T, int PA, int PT, K
     PH_FLUSH(lane);
     FPHK(f, 13);
     FPH_FLUSH(f, lane);
+#ifdef DCM_LOG
+    if (f.inA) lg.len[(size_t)e * BA + f.la] = fl.len;
+#endif
     const int64_t steps = (int64_t)(left0 - left);
     if (lane == 0 && steps_out) steps_out[e] = steps;
     h.d = d0 + (uint64_t)steps;

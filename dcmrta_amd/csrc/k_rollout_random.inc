@@ -8,15 +8,32 @@
 // The greedy-policy forms (DCM_POLICY defined; dcm_rollout_policy with DCM_POLICY_FIRST / DCM_POLICY_NEAREST): k_hp_rollout_random and its
 // renewing form k_hprn_rollout_random, the same text with one more wave-uniform argument, `policy`, and the action taken from it instead of
 // protocol slot 1.  Compiled in a translation unit of their own; the forms above hold nothing of them.  No size-renewing form.
+// The logging forms (DCM_LOG defined; a launch of either entry point while dcm_set_rollout_log is set): k_lg_rollout_random and its
+// renewing form k_lgrn_rollout_random, the same text with two more arguments: `policy`, which here covers all three policies (wave-
+// uniform: DCM_POLICY_RANDOM takes protocol slot 1 as the plain form does), and the log, which apply_and_advance appends to and whose
+// lengths the env zeroes when it restarts an episode.  Compiled in a translation unit of their own; no size-renewing form.
+#if defined(DCM_LOG) && DCM_RENEW == 2
+#error "no size-renewing logging form"
+#endif
 #ifdef DCM_POLICY
 #if DCM_RENEW == 2
 #error "no size-renewing greedy form"
 #endif
 #define KPOLICY_PARAM , int policy
+#elif defined(DCM_LOG)
+#define KPOLICY_PARAM , int policy, RouteLog lg
 #else
 #define KPOLICY_PARAM
 #endif
-#if defined(DCM_POLICY) && DCM_RENEW
+#if defined(DCM_LOG) && DCM_RENEW
+#define KNAME k_lgrn_rollout_random
+#define KRENEW_PARAM , Renew rn
+#define KSIZES const int32_t* sizes
+#elif defined(DCM_LOG)
+#define KNAME k_lg_rollout_random
+#define KRENEW_PARAM
+#define KSIZES const int32_t* sizes
+#elif defined(DCM_POLICY) && DCM_RENEW
 #define KNAME k_hprn_rollout_random
 #define KRENEW_PARAM , Renew rn
 #define KSIZES const int32_t* sizes
@@ -71,6 +88,8 @@ __global__ __launch_bounds__(WAVE, 3) void KNAME(int A, int T, int PA, int PT, K
     double* row = summary + (size_t)e * 8;
 #ifdef DCM_POLICY
     const int left0 = rollout_budget_policy(e, budget_all, budget_in, P);
+#elif defined(DCM_LOG)
+    const int left0 = policy == DCM_POLICY_RANDOM ? rollout_budget(e, budget_all, budget_in) : rollout_budget_policy(e, budget_all, budget_in, P);
 #else
     const int left0 = rollout_budget(e, budget_all, budget_in);
 #endif
@@ -90,6 +109,9 @@ __global__ __launch_bounds__(WAVE, 3) void KNAME(int A, int T, int PA, int PT, K
 #elif DCM_RENEW
             wave_renew_instance_call(S, rec, rn, e, lane, xy);
 #endif
+#ifdef DCM_LOG
+            for (int a = lane; a < S.A(); a += WAVE) lg.len[(size_t)e * BA + a] = 0;   // the log is the new episode's (as k_step's restart)
+#endif
             S.reset_state(h, lane);
             S.advance(h, P, lane, row PH_PASS);
             PH_MARK(10);
@@ -108,11 +130,17 @@ __global__ __launch_bounds__(WAVE, 3) void KNAME(int A, int T, int PA, int PT, K
             PH_MARK(1);
 #ifdef DCM_POLICY
             const int action = S.pick_policy_action(lane, leader, policy, xy);
+#elif defined(DCM_LOG)
+            const int action = policy == DCM_POLICY_RANDOM ? S.pick_random_action(lane, k1) : S.pick_policy_action(lane, leader, policy, xy);
 #else
             const int action = S.pick_random_action(lane, k1);
 #endif
             PH_MARK(2);
+#ifdef DCM_LOG
+            S.template apply_and_advance<true>(h, P, lane, leader, gm, action, k1, -1, nullptr, row PH_PASS, lg, e * BA, false, 0, true, false, &xy);
+#else
             S.template apply_and_advance<true>(h, P, lane, leader, gm, action, k1, -1, nullptr, row PH_PASS, RouteLog{nullptr, nullptr, nullptr, 0}, 0, false, 0, true, false, &xy);
+#endif
             gd += GAMMA;
             left--;
         }

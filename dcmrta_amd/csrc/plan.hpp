@@ -96,6 +96,14 @@ inline bool policy_form_ok(RenewForm form) { return form != RenewForm::Sizes; }
 // at once (env/task_env.py:269), decides again at the same time and, the policy being a function of the state, takes the same task
 // again -- in the reference as here.  Such a launch must carry a decision budget (the scalar one, or per-env budgets).
 inline bool policy_needs_budget(const Shape& s) { return !s.quiet; }
+// A persistent launch with the rollout log set (dcm_set_rollout_log), under any of the three policies.  The logging kernel forms
+// (k_lg_* / k_lgrn_*) exist, like the greedy ones, for the one-chunk register-resident kernel and for the general one only: where
+// rollout_kind says FastMc or FastG a logging launch takes the general kernel.
+inline Rollout log_rollout_kind(const Shape& s, bool obs_all_or_none) {
+    return rollout_kind(s, obs_all_or_none) == Rollout::Fast ? Rollout::Fast : Rollout::General;
+}
+// ... and there is no size-renewing logging form: a launch that would take the k_rs_* form is refused while the log is set
+inline bool log_form_ok(RenewForm form) { return form != RenewForm::Sizes; }
 // k_rollout_fast_g<NAC, NTC>: lane chunks of agents (1..2) and of tasks (2..4) from the batch dims
 inline int fast_g_agent_chunks(int A) { return A > LANES ? 2 : 1; }
 inline int fast_g_task_chunks(int T) { return T > 3 * LANES ? 4 : (T > 2 * LANES ? 3 : 2); }

@@ -33,6 +33,16 @@
 #pragma once
 #include <type_traits>
 
+// The rollout log of the logging kernel forms (dcm_set_rollout_log; k_lg_rollout_fast / k_lgrn_rollout_fast): the env's rows of
+// route_task / route_arrival as wave-uniform bases, and agent a's running length in lane a's register.  Only Fast<>::apply<true> touches
+// it, which only those forms instantiate.
+struct FastLog {
+    int16_t* task;    // the env's [A][cap] block
+    double* arrival;
+    int32_t cap;
+    int32_t len;      // lane-owned: entries appended to this lane's agent in the env's current episode (may exceed cap)
+};
+
 // TRK (lockstep kernel): the fast path records which task sections of the record it has changed (Sim::DIRTY_* bits), so that
 // the write-back can skip the others
 template <int CA, int CT, bool RS, bool OBS, bool TRK = false>
@@ -356,9 +366,40 @@ struct Fast {
         FPH(2);
         return apply(r, h, P, lane, k1, gm, leader, action, k2p);
     }
+    // The same decision with the rollout log set (the k_lg_* kernel forms; `policy` wave-uniform, any of the three): the action is chosen
+    // first -- decide()'s draw or decide_policy()'s pick -- and ONE apply follows, the logging one (a branch between decide and
+    // decide_policy would inline apply twice into the loop).
+    __device__ __forceinline__ int decide_logged(R& r, HdrRegs& h, const KP& P, int lane, uint64_t k1, float* agrow, float* tkrow, uint8_t* mkp,
+                                                 const uint64_t* k2p, int policy, FastLog& lg) const {
+        uint64_t gm;
+        int leader = pick_leader(r, h, k1, gm);
+        if (leader < 0) { h.flags |= DCM_FLAG_BAD_LEADER | DCM_FLAG_DONE; leader = 0; gm = 1ull; }
+        FPH(0);
+        const uint64_t bm = observe(r, h.now, leader, agrow, tkrow, mkp);
+        FPH(1);
+        int action;
+        if (policy == DCM_POLICY_RANDOM) {
+            const int nv = __popcll(bm);
+            action = nv ? nth(bm, below((uint32_t)k1, nv)) + 1 : 0;
+        } else {
+            uint64_t pick = bm;
+            if (policy == DCM_POLICY_NEAREST) {
+                const double lx = rl(r.ax, leader), ly = rl(r.ay, leader);
+                const double dd = dist2(lx, ly, r.tx, r.ty);
+                const bool open = lane_of(bm);
+                const double m = wave_nanmin_n<CT>(open ? dd : __builtin_nan(""));
+                pick = bm & __ballot(dd == m);
+            }
+            action = __ffsll((unsigned long long)pick);
+        }
+        FPH(2);
+        return apply<true>(r, h, P, lane, k1, gm, leader, action, k2p, &lg);
+    }
     // TaskEnv.step :326-342 with the leader's (valid: unmasked task or depot) action, then task_update / agent_update
+    // LOG (the k_lg_* kernel forms alone): every member lane appends (task id, arrival) to its agent's row of the rollout log
+    template <bool LOG = false>
     __device__ __forceinline__ int apply(R& r, const HdrRegs& h, const KP& P, int lane, uint64_t k1, uint64_t gm, int leader, int action,
-                                         const uint64_t* k2p = nullptr) const {
+                                         const uint64_t* k2p = nullptr, FastLog* lg = nullptr) const {
         const double now = h.now;
         uint64_t rest = gm & ~(1ull << leader);                                  // :328
         int rlen = __popcll(gm) - 1;
@@ -439,6 +480,16 @@ struct Fast {
             r.cur = action - 1;                                                  // :314
             r.ai = (r.ai & ~(A_GRP | A_MEMBER)) | (action == 0 ? A_INDEPOT : A_MEMBER);
             if (action) S.marr()[slot * CT + tl] = arrv;
+            if constexpr (LOG) {
+                // route.append / arrival_time += (:314,:318): one 16-bit and one 64-bit store behind the env's wave-uniform bases, at
+                // the lane's 32-bit entry index; the length never leaves the lane's register
+                const uint32_t o = (uint32_t)(la * lg->cap + lg->len);
+                if (lg->len < lg->cap) {
+                    *(int16_t*)((unsigned char*)lg->task + (o << 1)) = (int16_t)(action - 1);
+                    *(double*)((unsigned char*)lg->arrival + (o << 3)) = arrv;
+                }
+                lg->len++;
+            }
         }
         // A QUIET join: the task still lacks members after it (status = requirement - len(members) > 0) and the previous
         // task_update call -- at this same `now` -- left every task at a fixed point.  task_update (:245-281) then changes

@@ -12,15 +12,6 @@
 // form of k_rollout_fast_mc / k_rollout_fast_g: their shapes take k_hp_rollout_random (plan::policy_rollout_kind).
 #pragma once
 
-// The budget of a greedy launch.  With max_waiting_time <= 0 a greedy episode does not end in general (plan::policy_needs_budget), so
-// there "no limit" (a negative entry of max_decisions_in; the host refuses a negative scalar) counts as 0: the env takes no decision
-// in this launch instead of spinning at a constant clock.  (Only the general form runs on such a handle.)
-__device__ __forceinline__ int rollout_budget_policy(int e, int64_t budget_all, const int64_t* budget_in, const KP& P) {
-    const int64_t bud = budget_in ? budget_in[e] : budget_all;
-    const int left = rollout_budget(e, budget_all, budget_in);
-    return uni((!(P.mwt > 0.0) && bud < 0) ? 0 : left);
-}
-
 #define DCM_POLICY 1
 #define DCM_RENEW 0
 #include "k_rollout_random.inc"

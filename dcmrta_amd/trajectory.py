@@ -28,12 +28,17 @@ def route_lists(task, arrival, length, what="enable_route_log(cap)"):
     return out
 
 
-def route_history(env, b=0):
-    return route_lists(*(x[b].cpu().numpy() for x in env.routes()))
+def route_history(env, b=0, log="step"):
+    """log: "step" = the lockstep log (enable_route_log), "rollout" = the persistent launches' (enable_rollout_log)."""
+    if log == "step":
+        return route_lists(*(x[b].cpu().numpy() for x in env.routes()))
+    if log == "rollout":
+        return route_lists(*(x[b].cpu().numpy() for x in env.rollout_routes()), what="enable_rollout_log(cap)")
+    raise ValueError('log must be "step" or "rollout"')
 
 
-def routes_to_yaml(env, path, b=0):
-    routes = {a: [t + 1 for t in r] for a, (r, _) in enumerate(route_history(env, b))}   # worker.py:246-248
+def routes_to_yaml(env, path, b=0, log="step"):
+    routes = {a: [t + 1 for t in r] for a, (r, _) in enumerate(route_history(env, b, log))}   # worker.py:246-248
     with open(path, "w") as f:
         yaml.dump(routes, f, sort_keys=False)
     return routes
@@ -121,14 +126,15 @@ def trajectories(routes, depot, task_xy, members, feasible, time_start, time_fin
     return out
 
 
-def generate_traj(env, b=0, dt=0.1):
-    """trajectories() of env b of a BatchedTaskEnv whose route log was enabled before the episode (enable_route_log)."""
+def generate_traj(env, b=0, dt=0.1, log="step"):
+    """trajectories() of env b of a BatchedTaskEnv whose route log was enabled before the episode (enable_route_log; log="rollout": an
+    episode played by rollout() with enable_rollout_log)."""
     ts = {k: v[b].cpu().numpy() for k, v in env.tasks_state().items()}
     mem = env.task_members()[b].cpu().numpy()
     members = [[int(x) for x in row if x >= 0] for row in mem]
     d, xy, _, _ = env._instances
     st = env.status()
-    return trajectories(route_history(env, b), d[b].cpu().numpy(), xy[b].cpu().numpy(), members, ts["feasible"].astype(bool),
+    return trajectories(route_history(env, b, log), d[b].cpu().numpy(), xy[b].cpu().numpy(), members, ts["feasible"].astype(bool),
                         ts["time_start"], ts["time_finish"], float(st["now"][b]), env.max_waiting_time, dt)
 
 

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define DCM_ABI_VERSION 5 /* v3: dcm_build_id, dcm_set_visibility, dcm_load_instances validates req on the device; v4: dcm_set_replay_placement; v5: DCM_PARAM_WIDE_MEMBERS; still v5, additions only: dcm_generate_instances, dcm_get_instances, dcm_generator_draws, dcm_set_instance_renewal, dcm_instance_index, DCM_PARAM_RENEW_SIZES */
+#define DCM_ABI_VERSION 5 /* v3: dcm_build_id, dcm_set_visibility, dcm_load_instances validates req on the device; v4: dcm_set_replay_placement; v5: DCM_PARAM_WIDE_MEMBERS; still v5, additions only: dcm_generate_instances, dcm_get_instances, dcm_generator_draws, dcm_set_instance_renewal, dcm_instance_index, DCM_PARAM_RENEW_SIZES, dcm_set_rollout_log */
 
 typedef struct dcm_env dcm_env; /* opaque */
 
@@ -245,8 +245,32 @@ int dcm_step(dcm_env *env, const int32_t *actions, const int32_t *leader_in, con
  * executed by dcm_step appends (task id, -1 = depot; arrival time) to the agent's log:
  * route_task[B,A,cap] i16, route_arrival[B,A,cap] f64, route_len[B,A] i32 -- caller-owned device memory that must
  * outlive its use; all NULL disables.  dcm_reset zeroes route_len; entries beyond cap are counted but not stored.
- * (dcm_rollout_random does not log: use the lockstep API when trajectories are wanted.) */
+ * (The persistent launches, dcm_rollout_random / dcm_rollout_policy, never write this log: they have their own, dcm_set_rollout_log.) */
 int dcm_set_route_log(dcm_env *env, int16_t *route_task, double *route_arrival, int32_t *route_len, int32_t cap);
+
+/* The same history for the persistent launches: the routes of the episodes dcm_rollout_random / dcm_rollout_policy play.  Layout and
+ * argument check of dcm_set_route_log: route_task[B,A,cap] i16 (-1 = depot), route_arrival[B,A,cap] f64, route_len[B,A] i32 --
+ * caller-owned device memory that must outlive its use; all NULL disables.  A is the batch's agent dimension, also on a ragged batch,
+ * where an env writes the rows a < its own A.  In addition n_agents x cap x 8 bytes must stay below 4 GiB (DCM_ERR_INVALID otherwise).
+ *   What is logged: while set, every agent_step that dcm_rollout_random / dcm_rollout_policy execute appends (task id, arrival time)
+ *     to the acting agent's row -- the leader, its followers, and the whole group on a depot action.
+ *   Which episode: the log is that of the env's CURRENT episode.  The kernel zeroes the env's route_len row when it restarts an
+ *     episode (after the instance renewal, if there is one); dcm_reset zeroes all rows.
+ *   After a call the log holds the last episode the env played: complete if the env is DONE -- also for an env that stopped at an
+ *     episode boundary with its budget spent, which keeps the finished episode's log.  If the decision budget stopped the env in the
+ *     middle of an episode the log holds the prefix played so far, and a later persistent launch carries on appending from the
+ *     stored lengths.
+ *   Overflow: entries beyond cap are counted in route_len but not stored; only [0, min(len, cap)) of a row is defined.
+ *   Independence: dcm_step never writes this log, and the persistent launches still never write the dcm_set_route_log one; an
+ *     episode played partly by dcm_step is logged only for the part the persistent launches played.  The log is not part of
+ *     dcm_clone_state / dcm_restore_state.
+ *   Refusal: a launch that would take the size-renewing form (DCM_PARAM_RENEW_SIZES handle, ragged generated batch, stride set) while
+ *     the log is set returns DCM_ERR_STATE under every policy, nothing changes, and the message names the log.
+ *   Invariant: a launch with the log set returns exactly what the same launch returns without it -- steps_out, records, summaries,
+ *     the return log, the per-decision observation stores, the instance index, every policy's budget rule.  (It runs other kernels:
+ *     the logging forms of the one-chunk register-resident kernel and of the general one, under all three policies.)
+ * Host-side setter. */
+int dcm_set_rollout_log(dcm_env *env, int16_t *route_task, double *route_arrival, int32_t *route_len, int32_t cap);
 
 /* Optional history of route replay: what execute_by_route leaves for generate_traj / plot_animation (env/task_env.py:375-418,
  * 589-590) -- agent['route'] / ['arrival_time'], task['members'] and task['feasible_assignment'].  When set, dcm_execute_routes
