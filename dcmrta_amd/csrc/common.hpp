@@ -11,6 +11,7 @@
 
 #include "../../include/dcmrta_env.h"
 #include "plan.hpp"
+#include "removal_table.hpp"
 
 namespace dcm {
 
@@ -109,8 +110,9 @@ static_assert(Lay{20, 50}.rec_bytes() == 5824, "S(20,50) = 64 + 48A + 96T");
 static_assert(Lay{20, 50}.mids() == Lay{20, 50}.tb() + 56 * 50 && Lay{20, 50}.mut_bytes() == align16(Lay{20, 50}.tb() + 72 * 50), "5 member slots: the canonical record");
 constexpr int MW = DCM_MAX_MEMBERS_WIDE;
 // The removal path's dummy slots: LDS that a launch of a register-resident kernel (rollout_fast*.hpp, step_fast.hpp) asks for behind
-// everything the general code uses
+// everything the general code uses.  The one-chunk kernels (Fast<>) keep their compaction table in these bytes instead.
 constexpr uint32_t DUMMY_SLOT_BYTES = 512u;
+static_assert(DUMMY_SLOT_BYTES == RT_BYTES, "Fast<>'s removal table takes the place of the dummy slots");
 static_assert(MW <= 16, "member ids: one byte each of up to two 64-bit words");
 
 // Ordered member ids of one task: byte j of the word array = members[j] (the order matters: quirk Q1).  One word for the 5 slots

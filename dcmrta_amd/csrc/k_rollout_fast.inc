@@ -78,9 +78,10 @@ __global__ __launch_bounds__(WAVE, 4) void KNAME(int A, int T, int PA, int PT, K
     S.set_retlog(retlog, retcap, e, lane);
     WSYNC();
     HdrRegs h = load_hdr(smem);
-    // (the launch asks for 512 bytes of LDS behind everything the general code uses: the dummy slots)
-    F f{S, (double*)(smem + (SimT::SCR_IN_LDS ? L.lds_bytes() : SimT::lds_image_bytes(L)))};
+    // (the launch asks for 512 bytes of LDS behind everything the general code uses: the removal path's compaction table)
+    F f{S, (uint4*)(smem + (SimT::SCR_IN_LDS ? L.lds_bytes() : SimT::lds_image_bytes(L)))};
     f.init(lane);
+    f.build_removal_table(lane);
 #ifdef DCM_LOG
     // the env's rows of the log: wave-uniform bases, the lane's entry addressed by a 32-bit offset (dcm_set_rollout_log bounds A x cap)
     FastLog fl{lg.task + (size_t)e * BA * lg.cap, lg.arrival + (size_t)e * BA * lg.cap, lg.cap, f.inA ? lg.len[(size_t)e * BA + f.la] : 0};

@@ -44,8 +44,9 @@ __global__ __launch_bounds__(WAVE, DCM_STEP_WAVES) void KNAME(int A, int T, int 
     if (lane == 0) { *S.dirty() = 0; *S.dirty2() = 0; }
     WSYNC();
     HdrRegs h = load_hdr(smem);
-    F f{S, (double*)(smem + SimT::lds_image_bytes(L))};      // (512 bytes of LDS behind the image: the removal path's dummy slots)
+    F f{S, (uint4*)(smem + SimT::lds_image_bytes(L))};       // (512 bytes of LDS behind the image: the removal path's compaction table)
     f.init(lane);
+    f.build_removal_table(lane);
     typename F::R r;
     bool regs = false;       // the registers hold the env: agent arrays / member ids / abandonment counts of the LDS image are stale
     constexpr uint32_t ERR = DCM_FLAG_BAD_ACTION | DCM_FLAG_OVERFLOW | DCM_FLAG_BAD_LEADER | DCM_FLAG_BAD_INSTANCE;

@@ -54,7 +54,7 @@ struct Fast {
     static constexpr Lay L{CA, CT};
 
     SimT S;
-    double* dummy;                                     // 64 doubles of LDS nobody reads (the removal path's discarded writes)
+    uint4* rtab;                                       // the removal path's compaction table (removal_table.hpp): 32 x 16 bytes of LDS
     mutable uint32_t dirty = 0;                        // TRK only
     mutable uint64_t achg = ~0ull;                     // TRK only: the agents whose fields the step has changed (set by flush)
     mutable uint64_t dt_join = 0, dt_times = 0;        // TRK only: the tasks whose ids / arrival rows (a join) and time_start / time_finish
@@ -83,6 +83,16 @@ struct Fast {
         tm = (1ull << T_) - 1ull;
         inA = lane < A_; inT = lane < T_; isD = lane == DL;
         la = inA ? lane : 0; lt = inT ? lane : 0;
+    }
+    // Once per kernel, behind init: lanes 0..31 write one entry each of the compaction table (computed, not loaded).  A leaver's
+    // arrival goes to "slot 5" of its task, which is the task's own word of the id section behind the five arrival rows: the fast
+    // path keeps the ids in r.ids and nobody reads that word before flush() has rewritten it.
+    static_assert(M == RT_SLOTS && L.mids() == L.marr() + 8u * RT_SLOTS * CT && L.mids() + 8u * CT <= L.tinfo(),
+                  "slot 5 of task t is the id word of task t");
+    __device__ __forceinline__ void build_removal_table(int lane) const {
+        const RemovalEntry e = removal_entry((uint32_t)lane & (RT_ENTRIES - 1u), 8u * CT);
+        if (lane < (int)RT_ENTRIES) rtab[lane] = make_uint4(e.perm, e.off01, e.off23, e.off4_left);
+        WSYNC();
     }
 
     // ------------------------------------------------------------------------------ registers <-> LDS image
@@ -198,33 +208,38 @@ struct Fast {
             if (lane_of(dmask)) {
                 const uint32_t drop = le0 ? spread : q1;                         // only listed slots can be set: unused ones hold NaN
                 const uint32_t keep = ((1u << n) - 1u) & ~drop;
-                // Compact the survivors in order, without a branch: vacate all slots, then every surviving member moves down to
-                // its rank among the survivors (a target never lies above its source, so earlier writes are never clobbered);
-                // the leavers' writes go to a per-lane dummy slot.  At least one listed member leaves, so at most four survive:
-                // their ids fit the low word.  (Writing each slot straight to its final place -- survivors to their rank, leavers
-                // as NaN behind them: five writes instead of ten, no dummy slot -- was tried in round 6: +20 VALU for the target
-                // and value selects, not faster.)
+                // Compact the survivors in order, without a branch and without per-slot arithmetic: where every slot goes, the new
+                // id word and the new length are functions of `keep` alone and come from the workgroup's 32-entry table
+                // (removal_table.hpp) in one 128-bit LDS read, issued ahead of the writes that vacate the slots, which hide its
+                // latency.  Then all five arrivals are written: a survivor to its rank among the survivors (a target never lies
+                // above its source, and the values are in registers anyway), a leaver to "slot 5", the task's own word of the id
+                // section, which is stale on the fast path and rewritten by flush().  One v_perm_b32 makes the id word (at least
+                // one listed member leaves, so at most four survive: the low word).  The 512 bytes of the table are the former
+                // per-lane dummy slots of the leavers' writes: the launch's LDS is unchanged.  Measured (profiles/HISTORY.md, last
+                // section): the removal region of k_rollout_fast<20,50> 116 -> 78 static VALU (the per-slot rank / target / id /
+                // select arithmetic was ~70 of them, now five SDWA adds, a permute and the `gone` shifts), 285.0 -> 264.0 VALU per
+                // decision, product line +4.0 %.  (Writing each slot straight to its final place -- survivors to their rank,
+                // leavers as NaN behind them: five writes instead of ten -- was tried in round 6 with computed targets: +20 VALU
+                // for the target and value selects, not faster.)
+                const uint4 e = rtab[keep];
                 const uint32_t idl = (uint32_t)r.ids, idh = (uint32_t)(r.ids >> 32);
-                uint32_t nids = 0;
                 using gone_t = typename std::conditional<(CA <= 32), uint32_t, uint64_t>::type;   // agent ids below 32: one word
                 gone_t g = 0;
                 double* const row0 = S.marr() + lt;
-                double* const dump = dummy + lane;
 #pragma unroll
                 for (int j = 0; j < M; j++) row0[j * CT] = __builtin_nan("");
+                const uint32_t off[M] = {e.y & 0xFFFFu, e.y >> 16, e.z & 0xFFFFu, e.z >> 16, e.w & 0xFFFFu};
 #pragma unroll
                 for (int j = 0; j < M; j++) {
-                    const bool kp = (keep >> j) & 1u, lv = (drop >> j) & 1u;
-                    const int kj = __popc(keep & ((1u << j) - 1u));
                     const uint32_t id = (j < 4 ? (idl >> (8 * j)) : idh) & 0xFFu;
-                    nids |= kp ? (id << (8 * kj)) : 0u;
-                    g |= lv ? ((gone_t)1 << id) : (gone_t)0;
-                    *(kp ? row0 + kj * CT : dump) = av[j];
+                    g |= (gone_t)((drop >> j) & 1u) << id;
+                    *(double*)((unsigned char*)row0 + off[j]) = av[j];
                 }
                 gone = (uint64_t)g;
-                r.ids = (uint64_t)nids; r.lm &= ~gone;
-                r.nab += (uint32_t)__popc(drop);                                 // abandoned_agent.append :265/:271
-                nn = __popc(keep);
+                r.ids = (uint64_t)__builtin_amdgcn_perm(idh, idl, e.x);
+                r.lm &= ~gone;
+                nn = (int)(e.w >> 16);
+                r.nab += (uint32_t)(n - nn);                                     // abandoned_agent.append :265/:271
             }
             if constexpr (TRK) dirty |= SimT::DIRTY_ALL & ~SimT::DIRTY_TIMES;   // slots compacted: every arrival row, ids, counts
             uint64_t todo = dmask;
@@ -566,7 +581,7 @@ struct Fast {
 };
 
 // dynamic LDS of a k_rollout_fast launch: what the general code uses (the record image, + the scratch when it sits in LDS), then
-// the dummy slots
+// the removal path's compaction table (DUMMY_SLOT_BYTES: the bytes the leavers' dummy slots used to take)
 template <int CA, int CT, bool RS>
 constexpr uint32_t rollout_fast_lds_bytes(Lay L) {
     using SimT = Sim<CA, CT, RS, false>;

@@ -15,12 +15,12 @@
 #define DCM_STEP_WAVES 4       // minimum waves per SIMD asked of the compiler for k_step_fast
 #endif
 
-// The terminal metrics' scratch (calculate_waiting_time: 3.6 KB at 20A/50T) sits in LDS behind the dummy slots when 16 workgroups
+// The terminal metrics' scratch (calculate_waiting_time: 3.6 KB at 20A/50T) sits in LDS behind the removal table when 16 workgroups
 // per CU -- all that the kernel's VGPRs allow -- still fit: the env whose episode ends in a launch is that launch's slowest wave,
 // and with the scratch in HBM every write -> WSYNC -> read phase of the metrics is a global-memory round trip.
 template <int CA, int CT>
 constexpr bool step_scratch_in_lds() { return Lay{CA, CT}.lds_bytes() + DUMMY_SLOT_BYTES <= 10240u; }
-// dynamic LDS of a k_step_fast / k_terminal_flush launch: the record image, the dummy slots, the scratch when it sits in LDS
+// dynamic LDS of a k_step_fast / k_terminal_flush launch: the record image, the removal table (DUMMY_SLOT_BYTES), the scratch when it sits in LDS
 template <int CA, int CT, bool RS>
 constexpr uint32_t step_fast_lds_bytes(Lay L) {
     return Sim<CA, CT, RS, false>::lds_image_bytes(L) + DUMMY_SLOT_BYTES + (step_scratch_in_lds<CA, CT>() ? L.scratch_bytes() : 0u);
