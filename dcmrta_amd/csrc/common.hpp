@@ -280,6 +280,22 @@ __device__ __forceinline__ double nanmax2(double a, double b) {
     asm("v_max_f64 %0, %1, %2" : "=v"(r) : "v"(a), "v"(b));
     return r;
 }
+// The same over five values in ONE asm statement: behind every asm statement that writes a VGPR the compiler, which cannot read it,
+// pads for the longest forwarding hazard an instruction could have (s_nop 0 / 1 in front of the next reader), so a chain of four
+// nanmin2 costs three s_nop between its links; v_min_f64 / v_max_f64 themselves need none.  (early-clobber: the result is written
+// while c, d, e are still to be read)
+__device__ __forceinline__ double nanmin5(double a, double b, double c, double d, double e) {
+    double r;
+    asm("v_min_f64 %0, %1, %2\n\tv_min_f64 %0, %0, %3\n\tv_min_f64 %0, %0, %4\n\tv_min_f64 %0, %0, %5"
+        : "=&v"(r) : "v"(a), "v"(b), "v"(c), "v"(d), "v"(e));
+    return r;
+}
+__device__ __forceinline__ double nanmax5(double a, double b, double c, double d, double e) {
+    double r;
+    asm("v_max_f64 %0, %1, %2\n\tv_max_f64 %0, %0, %3\n\tv_max_f64 %0, %0, %4\n\tv_max_f64 %0, %0, %5"
+        : "=&v"(r) : "v"(a), "v"(b), "v"(c), "v"(d), "v"(e));
+    return r;
+}
 // NaN-ignoring minimum over the wave (np.nanmin), NaN when every lane is NaN.
 __device__ __forceinline__ double wave_nanmin(double v) {
     v = nanmin2(v, DPP_RED<0x111, 0xF>(v));  // row_shr:1

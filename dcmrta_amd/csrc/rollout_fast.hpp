@@ -150,9 +150,8 @@ struct Fast {
         // The latest arrival only matters for a task whose coalition is complete (status <= 0 :254): the spread test, time_start and
         // the spread rule's threshold (:255-265).  Such a task exists at the one call after the completing join (or while a stale
         // status lingers, Q3); every other call -- wave-uniform test -- skips the four v_max_f64 and the tests that need them.
-        double mn = av[0];
-#pragma unroll
-        for (int j = 1; j < M; j++) mn = nanmin2(mn, av[j]);
+        static_assert(M == 5, "nanmin5 / nanmax5");
+        const double mn = nanmin5(av[0], av[1], av[2], av[3], av[4]);
         const bool le0 = status <= 0;                                            // :254
         // The predicates live as wave-uniform masks (common.hpp, lane_of): every ballot is one direct compare, the combinations are
         // scalar.  The lanes that own no task hold a copy of task 0's words (lt is clamped): whatever decides anything passes through
@@ -163,9 +162,7 @@ struct Fast {
         double mx = 0.0, thr = 0.0;
         uint64_t okm = 0ull, sdrop = 0ull;
         if (open & le0m) {
-            mx = av[0];
-#pragma unroll
-            for (int j = 1; j < M; j++) mx = nanmax2(mx, av[j]);
+            mx = nanmax5(av[0], av[1], av[2], av[3], av[4]);
             okm = le0m & __ballot(mx - mn <= mwt);                               // :255
             thr = mx - mwt;                                                      // :262
             sdrop = open & le0m & ~okm & __ballot(mn <= thr);                    // the spread rule's leavers (none without such a task)
@@ -251,8 +248,15 @@ struct Fast {
                 if (lane_of(g)) {                                                // this lane's agent was dropped by task t
                     const uint32_t nth_ = r.ai >> 16;
                     r.ai += 1u << 16;
-                    if (nth_ < (uint32_t)AB_CAP) r.ab[nth_] = (uint16_t)t;
-                    else { const uint32_t ci = (uint32_t)(la * S.T() + t); atomicAdd((uint32_t*)S.abcnt() + (ci >> 1), 1u << (16 * (ci & 1))); }
+                    // (Both side tables live in HBM.  The LDS image keeps generic pointers to them, so the compiler emitted FLAT
+                    //  instructions, which count on lgkmcnt as well as vmcnt: the next lgkmcnt(0) also waited for this store.  With
+                    //  the cast to the global address space they are global_store_short / global_atomic_add.)
+                    if (nth_ < (uint32_t)AB_CAP) ((__attribute__((address_space(1))) uint16_t*)r.ab)[nth_] = (uint16_t)t;
+                    else {
+                        const uint32_t ci = (uint32_t)(la * S.T() + t);
+                        __hip_atomic_fetch_add((__attribute__((address_space(1))) uint32_t*)S.abcnt() + (ci >> 1), 1u << (16 * (ci & 1)),
+                                               __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+                    }
                     if (r.cur == t) r.ai &= ~A_MEMBER;                           // no longer `agent in current_task['members']` :230
                 }
             } while (todo);
@@ -421,8 +425,16 @@ struct Fast {
         uint64_t mm = 1ull << leader, mlist = (uint64_t)(uint32_t)leader;
         int nm = 1;
         int mypos = 0;                                                           // this lane's position in the step's member list
-        const int tl = action ? action - 1 : DL;                                 // lane that owns the target
-        if (action == 0) {                                                       // vacancy = len(group) :327 (Q9)
+        // `action - 1` pinned to the scalar unit: left alone the compiler fuses it with `action != 0` into ONE VALU subtract-with-borrow
+        // (r.cur wants the difference in a VGPR) and fetches every uniform use of the target lane back by v_readfirstlane
+        action = uni(action);                                                    // (the lockstep kernel's comes from a vector load; free here)
+        int task = action - 1;                                                   // route[-1] of the members (-1: the depot)
+        asm("" : "+s"(task));
+        int act_ = action;                                                       // (an opaque copy for the `action != 0` tests)
+        asm("" : "+s"(act_));
+        const bool go = act_ != 0;                                               // a task, not the depot
+        const int tl = go ? task : DL;                                           // lane that owns the target
+        if (!go) {                                                               // vacancy = len(group) :327 (Q9)
             CNT(2);
             mm |= rest; nm += rlen; rlen = 0;
         } else if (rlen != 0) {
@@ -460,7 +472,7 @@ struct Fast {
         const bool mem = lane_of(mm);
         uint64_t ids = 0ull; uint32_t kinfo = 0; int n = 0;
         int slot = 0;
-        if (action) {
+        if (go) {
             // :321-322 members.append unless already listed (Q4: a re-joining agent keeps its slot, its arrival is overwritten)
             kinfo = (uint32_t)__builtin_amdgcn_readlane((int)r.ti, tl);
             ids = rl(r.ids, tl);
@@ -492,28 +504,30 @@ struct Fast {
             r.td += d;                                                           // :317
             r.arr = arrv;
             r.ax = tx_; r.ay = ty_;                                              // :320
-            r.cur = action - 1;                                                  // :314
-            r.ai = (r.ai & ~(A_GRP | A_MEMBER)) | (action == 0 ? A_INDEPOT : A_MEMBER);
-            if (action) S.marr()[slot * CT + tl] = arrv;
+            r.cur = task;                                                        // :314
+            r.ai = (r.ai & ~(A_GRP | A_MEMBER)) | (go ? A_MEMBER : A_INDEPOT);
             if constexpr (LOG) {
                 // route.append / arrival_time += (:314,:318): one 16-bit and one 64-bit store behind the env's wave-uniform bases, at
                 // the lane's 32-bit entry index; the length never leaves the lane's register
                 const uint32_t o = (uint32_t)(la * lg->cap + lg->len);
                 if (lg->len < lg->cap) {
-                    *(int16_t*)((unsigned char*)lg->task + (o << 1)) = (int16_t)(action - 1);
+                    *(int16_t*)((unsigned char*)lg->task + (o << 1)) = (int16_t)task;
                     *(double*)((unsigned char*)lg->arrival + (o << 3)) = arrv;
                 }
                 lg->len++;
             }
         }
+        // (the members' arrival slots, under a mask of its own: as a uniform `if (go)` inside the members' block the compiler inverts
+        //  the condition through a 0/1 VGPR)
+        if (lane_of(go ? mm : 0ull)) S.marr()[slot * CT + tl] = arrv;
         // A QUIET join: the task still lacks members after it (status = requirement - len(members) > 0) and the previous
         // task_update call -- at this same `now` -- left every task at a fixed point.  task_update (:245-281) then changes
         // nothing but this task's status: not enough members -> not feasible (:254); the joining members have not waited
         // (arrival >= now, :269); everybody else was evaluated at this `now` by the previous call.  The pass over the tasks is
         // skipped and the task's lane takes the new status itself.
         const int status_k = (int)(kinfo & 0xFFu) - n;
-        const bool quiet = action && calm && status_k > 0;
-        if (action && lane == tl) {
+        const bool quiet = go && calm && status_k > 0;
+        if (go && lane == tl) {
             r.ids = ids; r.lm |= mm;
             r.ti = quiet ? ((kinfo & (T_FEAS | T_FIN | 0xFFu)) | ((uint32_t)(status_k & 0xFF) << 8) | ((uint32_t)n << 16))
                          : ((kinfo & ~0x00FF0000u) | ((uint32_t)n << 16));
