@@ -21,6 +21,7 @@ import torch
 
 from . import _lib
 from ._lib import DcmError, DcmParams, check
+from .choice import explore_q32 as _choice_explore_q32
 
 SUMMARY_COLUMNS = ("reward", "n_finished", "success_rate", "makespan", "time_cost", "waiting_time", "travel_dist",
                    "efficiency")
@@ -302,15 +303,34 @@ class BatchedTaskEnv:
 
     POLICIES = {"random": _lib.POLICY_RANDOM, "first": _lib.POLICY_FIRST, "nearest": _lib.POLICY_NEAREST}
 
-    def rollout(self, policy="random", episodes=1, write_obs=True, max_decisions=-1):
+    def rollout(self, policy="random", episodes=1, write_obs=True, max_decisions=-1, *, explore=None, explore_q32=None):
         """`episodes` full episodes per env in one persistent launch under a device policy (dcm_rollout_policy): "random" (uniform
         over the unmasked tasks: the config-2 hot path), "first" (the lowest unmasked task) or "nearest" (the unmasked task closest
         to the deciding agent, ties to the lowest index).
         max_decisions: int (all envs) or int64[B] (numpy/torch) -- decision budget of this call (< 0 = unlimited); an env that
         runs out of budget stays at its pending decision, the obs buffers (obs()) hold what its last decision TAKEN saw.
+        explore (a float epsilon in [0, 1]) or explore_q32 (an int in [0, 2^32]; choice.explore_q32(epsilon)): epsilon-greedy over
+        "first" / "nearest" (dcm_rollout_explore) -- a decision takes the random policy's action with probability epsilon, decided by
+        the choice protocol's explore word (choice.explores), and the base policy's pick otherwise.  Give at most one of the two;
+        with neither the call is the plain one.
         Returns steps int64[B] (device tensor)."""
         if policy not in self.POLICIES:
             raise DcmError("policy must be one of %s" % ", ".join(repr(p) for p in self.POLICIES))
+        q32 = None
+        if explore is not None or explore_q32 is not None:
+            if explore is not None and explore_q32 is not None:
+                raise DcmError("give explore (epsilon) or explore_q32, not both")
+            if policy == "random":
+                raise DcmError("explore needs a greedy base policy: 'first' or 'nearest' ('random' explores at every decision already)")
+            if explore is not None:
+                try:
+                    q32 = _choice_explore_q32(explore)
+                except ValueError as e:
+                    raise DcmError(str(e))
+            else:
+                q32 = int(explore_q32)
+                if not 0 <= q32 <= 1 << 32:
+                    raise DcmError("explore_q32 must lie in [0, 2^32]")
         steps = torch.empty((self.B,), dtype=torch.int64, device=self.device)
         o = (self._agents, self._tasks, self._mask) if write_obs else (None, None, None)
         per_env = None
@@ -320,8 +340,12 @@ class BatchedTaskEnv:
                 raise DcmError("max_decisions must be an int or int64[B]")
             max_decisions = -1
         with torch.cuda.device(self.device):
-            check(self._lib.dcm_rollout_policy(self._h, self.POLICIES[policy], int(episodes), int(max_decisions), _ptr(per_env),
-                                               *[_ptr(x) for x in o], _ptr(steps), self._stream()))
+            if q32 is None:
+                check(self._lib.dcm_rollout_policy(self._h, self.POLICIES[policy], int(episodes), int(max_decisions), _ptr(per_env),
+                                                   *[_ptr(x) for x in o], _ptr(steps), self._stream()))
+            else:
+                check(self._lib.dcm_rollout_explore(self._h, self.POLICIES[policy], q32, int(episodes), int(max_decisions), _ptr(per_env),
+                                                    *[_ptr(x) for x in o], _ptr(steps), self._stream()))
         return steps
 
     def obs(self):

@@ -16,6 +16,10 @@ GPU, so parity is defined on a counter-based protocol instead:
     action    = valid[below(draw(s,d,1), len(valid))]    uniform-random policy only
     followers = k successive rest.pop(below(draw(s,d,2+j), len(rest)))
 
+    explore_word(s,d) = mix64(key_1(s,d) ^ EXPLORE_SALT) >> 32     epsilon-greedy launches (dcm_rollout_explore) only:
+                     decision d explores -- takes the random policy's action, slot 1 -- iff explore_word < explore_q32,
+                     explore_q32 = floor(eps * 2^32) in [0, 2^32]; every other decision takes the base policy's pick
+
 Every draw is a pure function of (seed, d, slot): observe() and step() recompute the same
 leader without carrying RNG state, and a policy that ignores slot 1 does not shift the others.
 One 64-bit mix serves leader + action of a decision; a second one is only needed when
@@ -48,6 +52,27 @@ def draw(seed_e: int, d: int, slot: int) -> int:
 
 def below(r: int, n: int) -> int:
     return (r * n) >> 32
+
+
+EXPLORE_SALT = 0xD6E8FEB86659FD93
+
+
+def explore_word(seed_e: int, d: int) -> int:
+    """The 32-bit explore word of decision d (dcm_rollout_explore)."""
+    return mix64(mix64(seed_e + GAMMA * (d + 1)) ^ EXPLORE_SALT) >> 32
+
+
+def explore_q32(eps: float) -> int:
+    """floor(eps * 2^32) for eps in [0, 1]; 1.0 gives 2^32 (every decision explores)."""
+    eps = float(eps)
+    if not 0.0 <= eps <= 1.0:
+        raise ValueError("explore: epsilon must lie in [0, 1]")
+    return int(eps * 4294967296.0)      # (a double times a power of two is exact; int() floors a non-negative value)
+
+
+def explores(seed_e: int, d: int, q32: int) -> bool:
+    """Does decision d of the env explore under explore_q32 = q32?"""
+    return explore_word(seed_e, d) < int(q32)
 
 
 def env_seeds(base: int, first: int, count: int) -> np.ndarray:

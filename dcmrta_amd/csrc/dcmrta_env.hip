@@ -38,20 +38,25 @@ using namespace dcm;
 // compiles from the text, and to the code, it had without them.
 // A fourth unit (-DDCM_TU_L) holds the logging forms alone (k_lg_* / k_lgrn_*, dcm_set_rollout_log) in the same way: the main unit
 // reaches them through dcm::launch_rollout_log.
-#if defined(DCM_TU_G) || defined(DCM_TU_P) || defined(DCM_TU_L)
+// A fifth unit (-DDCM_TU_E) holds the epsilon-greedy forms alone (k_ex_* / k_exrn_*, dcm_rollout_explore) in the same way: the main
+// unit reaches them through dcm::launch_rollout_explore.
+#if defined(DCM_TU_G) || defined(DCM_TU_P) || defined(DCM_TU_L) || defined(DCM_TU_E)
 #define DCM_DEVICE_ONLY_TU 1
 #endif
-#if defined(DCM_TU_G) || (!defined(DCM_SPLIT_G) && !defined(DCM_TU_P) && !defined(DCM_TU_L))
+#if defined(DCM_TU_G) || (!defined(DCM_SPLIT_G) && !defined(DCM_TU_P) && !defined(DCM_TU_L) && !defined(DCM_TU_E))
 #define DCM_HAVE_FAST_G 1     // this unit holds k_rollout_fast_g and its launcher
 #endif
-#if defined(DCM_TU_P) || (!defined(DCM_SPLIT_G) && !defined(DCM_TU_G) && !defined(DCM_TU_L))
+#if defined(DCM_TU_P) || (!defined(DCM_SPLIT_G) && !defined(DCM_TU_G) && !defined(DCM_TU_L) && !defined(DCM_TU_E))
 #define DCM_HAVE_POLICY 1     // this unit holds the greedy-policy forms and their launcher
 #endif
-#if defined(DCM_TU_L) || (!defined(DCM_SPLIT_G) && !defined(DCM_TU_G) && !defined(DCM_TU_P))
+#if defined(DCM_TU_L) || (!defined(DCM_SPLIT_G) && !defined(DCM_TU_G) && !defined(DCM_TU_P) && !defined(DCM_TU_E))
 #define DCM_HAVE_LOG 1        // this unit holds the logging forms and their launcher
 #endif
+#if defined(DCM_TU_E) || (!defined(DCM_SPLIT_G) && !defined(DCM_TU_G) && !defined(DCM_TU_P) && !defined(DCM_TU_L))
+#define DCM_HAVE_EXPLORE 1    // this unit holds the epsilon-greedy forms and their launcher
+#endif
 namespace dcm {
-#if !defined(DCM_TU_G) && !defined(DCM_TU_P) && !defined(DCM_TU_L)
+#if !defined(DCM_DEVICE_ONLY_TU)
 thread_local char g_err[512] = "";
 int fail(int code, const char* fmt, const char* a, const char* b) {
     snprintf(g_err, sizeof(g_err), fmt, a, b);
@@ -73,6 +78,7 @@ struct RolloutArgs {
     plan::RenewForm form;  // which form the launch takes (plan::renew_form)
     int policy = DCM_POLICY_RANDOM;   // last argument of the greedy-policy forms (k_hp_*, k_hprn_*)
     RouteLog lg{nullptr, nullptr, nullptr, 0};   // last argument of the logging forms (k_lg_*, k_lgrn_*), behind `policy`
+    uint64_t explore_q32 = 0;          // the epsilon-greedy forms (k_ex_*, k_exrn_*): between `policy` and the log
 };
 // k_rollout_fast_g<NAC, NTC, OBS> / k_rn_rollout_fast_g / k_rs_rollout_fast_g (rollout_fast_g.hpp, its own translation unit)
 void launch_rollout_fast_g(int nac, int ntc, bool obs, unsigned grid, Lay L, hipStream_t stream, const RolloutArgs& a);
@@ -84,6 +90,11 @@ void allow_lds_policy(int lds);
 // unit).  fast: plan::log_rollout_kind said Fast; a.policy: any of the three; a.lg: the handle's rollout log; a.form: Plain or Instance
 int launch_rollout_log(plan::SimKind kind, bool fast, bool obs, unsigned grid, Lay L, hipStream_t stream, const RolloutArgs& a);
 void allow_lds_log(int lds);
+// the epsilon-greedy forms k_ex_rollout_fast / k_ex_rollout_random and their renewing forms k_exrn_* (rollout_explore.hpp, their own
+// translation unit).  fast: plan::explore_rollout_kind said Fast; a.policy: DCM_POLICY_FIRST or DCM_POLICY_NEAREST; a.explore_q32 <= 2^32;
+// a.lg: the handle's rollout log, set or not; a.form: Plain or Instance
+int launch_rollout_explore(plan::SimKind kind, bool fast, bool obs, unsigned grid, Lay L, hipStream_t stream, const RolloutArgs& a);
+void allow_lds_explore(int lds);
 }  // namespace dcm
 
 namespace {
@@ -1593,6 +1604,9 @@ constexpr uint32_t rollout_random_lds_bytes(Lay L) {
 #ifdef DCM_HAVE_LOG
 #include "rollout_log.hpp"
 #endif
+#ifdef DCM_HAVE_EXPLORE
+#include "rollout_explore.hpp"
+#endif
 
 __global__ __launch_bounds__(WAVE) void k_env_status(int PA, int PT, int PC, const unsigned char* state, int B, uint32_t* flags_out,
                                                     int64_t* dec_out, double* now_out, int32_t* episodes_out) {
@@ -1910,6 +1924,66 @@ void dcm::allow_lds_log(int lds) {
 }
 #endif
 
+#ifdef DCM_HAVE_EXPLORE
+namespace {
+// the epsilon-greedy forms take `policy`, explore_q32 and the log last (k_ex_*), behind the renewal argument in the renewing ones (k_exrn_*)
+template <class K>
+void launch_rollout_ex(K kernel, dim3 grid, dim3 block, unsigned lds_bytes, hipStream_t stream, const RolloutArgs& a) {
+    hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, a.A, a.T, a.PA, a.PT, a.kp, a.state, a.episodes, a.agents_out, a.tasks_out,
+                       a.mask_out, a.steps_out, a.summary, a.ablog, a.sizes, a.budget_all, a.budget_in, a.gscr, a.retlog, a.retcap, a.policy,
+                       a.explore_q32, a.lg);
+}
+template <class K>
+void launch_rollout_exrn(K kernel, dim3 grid, dim3 block, unsigned lds_bytes, hipStream_t stream, const RolloutArgs& a) {
+    hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, a.A, a.T, a.PA, a.PT, a.kp, a.state, a.episodes, a.agents_out, a.tasks_out,
+                       a.mask_out, a.steps_out, a.summary, a.ablog, a.sizes, a.budget_all, a.budget_in, a.gscr, a.retlog, a.retcap, a.rn,
+                       a.policy, a.explore_q32, a.lg);
+}
+template <class K>
+void allow_lds_ex(K kernel, int bytes) { (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes); }
+}  // namespace
+
+// Returns 0, or -1 when `kind` has no one-chunk kernel (the caller asked plan::explore_rollout_kind, so it has)
+int dcm::launch_rollout_explore(plan::SimKind kind, bool fast, bool obs, unsigned grid, Lay L, hipStream_t stream, const RolloutArgs& a) {
+    const bool renew = a.form == plan::RenewForm::Instance;
+    if (fast) {
+#define CALLF(CA, CT, RS, OBS)                                                                                                             \
+    do {                                                                                                                                   \
+        if (renew) launch_rollout_exrn(k_exrn_rollout_fast<CA, CT, RS, OBS>, dim3(grid), dim3(WAVE), rollout_fast_lds_bytes<CA, CT, RS>(L), stream, a); \
+        else launch_rollout_ex(k_ex_rollout_fast<CA, CT, RS, OBS>, dim3(grid), dim3(WAVE), rollout_fast_lds_bytes<CA, CT, RS>(L), stream, a);           \
+    } while (0)
+#define CALL(CA, CT, RS) do { if (obs) { CALLF(CA, CT, RS, true); } else { CALLF(CA, CT, RS, false); } } while (0)
+        switch (kind) { FOR_EACH_FAST(SIM_CASE) default: return -1; }
+#undef CALL
+#undef CALLF
+        return 0;
+    }
+#define CALL(CA, CT, RS, ...)                                                                                                              \
+    do {                                                                                                                                   \
+        if (renew) launch_rollout_exrn(k_exrn_rollout_random<CA, CT, RS, ##__VA_ARGS__>, dim3(grid), dim3(WAVE), rollout_random_lds_bytes<CA, CT, RS>(L), stream, a); \
+        else launch_rollout_ex(k_ex_rollout_random<CA, CT, RS, ##__VA_ARGS__>, dim3(grid), dim3(WAVE), rollout_random_lds_bytes<CA, CT, RS>(L), stream, a);           \
+    } while (0)
+    switch (kind) { FOR_EACH_INSTANCE(SIM_CASE) }
+#undef CALL
+    return 0;
+}
+// dcm_create: the epsilon-greedy forms' share of the dynamic-LDS limit (see there)
+void dcm::allow_lds_explore(int lds) {
+#define SET_ATTR(KIND, CA, CT, RS, ...)                                  \
+    allow_lds_ex(k_ex_rollout_random<CA, CT, RS, ##__VA_ARGS__>, lds);   \
+    allow_lds_ex(k_exrn_rollout_random<CA, CT, RS, ##__VA_ARGS__>, lds);
+    FOR_EACH_INSTANCE(SET_ATTR)
+#undef SET_ATTR
+#define SET_FAST(KIND, CA, CT, RS)                                       \
+    allow_lds_ex(k_ex_rollout_fast<CA, CT, RS, true>, lds);              \
+    allow_lds_ex(k_ex_rollout_fast<CA, CT, RS, false>, lds);             \
+    allow_lds_ex(k_exrn_rollout_fast<CA, CT, RS, true>, lds);            \
+    allow_lds_ex(k_exrn_rollout_fast<CA, CT, RS, false>, lds);
+    FOR_EACH_FAST(SET_FAST)
+#undef SET_FAST
+}
+#endif
+
 #ifndef DCM_DEVICE_ONLY_TU   // (tools/loop_insts.py compiles single kernel instantiations of this file without the host API)
 namespace {
 constexpr uint32_t CU_LDS_BYTES = 160u * 1024u;
@@ -2087,6 +2161,7 @@ int dcm_create(const dcm_params* params, dcm_env** out) {
     allow_lds(k_rn_rollout_fast_mc<50, 200, false>, lds);
     dcm::allow_lds_policy(lds);
     dcm::allow_lds_log(lds);
+    dcm::allow_lds_explore(lds);
     allow_lds(k_get_tasks<M>, lds);
     allow_lds(k_get_agents<M>, lds);
     allow_lds(k_get_tasks<MW>, lds);
@@ -2527,6 +2602,38 @@ int dcm_rollout_policy(dcm_env* env, int32_t policy, int32_t episodes, int64_t m
     const plan::Shape shape = shape_of(env);
     const bool fast = plan::policy_rollout_kind(shape, all_obs || no_obs) == plan::Rollout::Fast;
     if (dcm::launch_rollout_policy(plan::sim_kind(shape), fast, all_obs, (unsigned)env->p.n_envs, env->L, (hipStream_t)stream, ra) != 0)
+        return fail(DCM_ERR_STATE, "internal error: a one-chunk kernel on another layout");
+    LAUNCH_OK();
+    return DCM_OK;
+}
+
+int dcm_rollout_explore(dcm_env* env, int32_t policy, uint64_t explore_q32, int32_t episodes, int64_t max_decisions,
+                        const int64_t* max_decisions_in, float* agents_out, float* tasks_out, uint8_t* mask_out, int64_t* steps_out,
+                        void* stream) {
+    CHECK_ENV(env);
+    if (policy != DCM_POLICY_FIRST && policy != DCM_POLICY_NEAREST)
+        return fail(DCM_ERR_INVALID, "dcm_rollout_explore: the base policy must be DCM_POLICY_FIRST or DCM_POLICY_NEAREST");
+    if (explore_q32 > (1ull << 32)) return fail(DCM_ERR_INVALID, "dcm_rollout_explore: explore_q32 must be <= 2^32");
+    if (!env->reset_done) return fail(DCM_ERR_STATE, "dcm_rollout_explore: call dcm_reset first");
+    if (episodes < 1) return fail(DCM_ERR_INVALID, "dcm_rollout_explore: episodes must be >= 1");
+    if (plan::policy_needs_budget(shape_of(env)) && !max_decisions_in && max_decisions < 0)
+        return fail(DCM_ERR_INVALID, "dcm_rollout_explore: with max_waiting_time <= 0 a greedy policy does not end its episodes (a dropped member takes "
+                                     "the same task again at the same time): give a decision budget");
+    if (!plan::explore_form_ok(launch_form(env)))
+        return fail(DCM_ERR_STATE, "dcm_rollout_explore: no epsilon-greedy policy while a ragged batch renews its sizes (DCM_PARAM_RENEW_SIZES with a stride "
+                                   "set): clear the stride with dcm_set_instance_renewal(env, 0), or use dcm_rollout_random");
+    DCM_TRY(dcm::flush_pending(env, stream));
+    const plan::RenewForm form = renewing_launch(env, stream);
+    dcm::RolloutArgs ra{DIMS(env), env->kp, env->state, (int)episodes, agents_out, tasks_out, mask_out, steps_out, env->summary,
+                        env->ablog, (const int32_t*)env->sizes, max_decisions, max_decisions_in, env->gscratch, env->retlog,
+                        (int)env->retcap, renew_args(env), form};
+    ra.policy = policy;
+    ra.explore_q32 = explore_q32;      // (0 and 2^32 run the same kernels as every other value: no shortcut to the greedy / random forms)
+    ra.lg = env->rollout_log;          // set or not: one set of forms
+    const bool all_obs = agents_out && tasks_out && mask_out, no_obs = !agents_out && !tasks_out && !mask_out;
+    const plan::Shape shape = shape_of(env);
+    const bool fast = plan::explore_rollout_kind(shape, all_obs || no_obs) == plan::Rollout::Fast;
+    if (dcm::launch_rollout_explore(plan::sim_kind(shape), fast, all_obs, (unsigned)env->p.n_envs, env->L, (hipStream_t)stream, ra) != 0)
         return fail(DCM_ERR_STATE, "internal error: a one-chunk kernel on another layout");
     LAUNCH_OK();
     return DCM_OK;

@@ -14,7 +14,13 @@
 // commits the member lanes.  Lane a keeps agent a's running length in a register (FastLog): loaded once at the head, zeroed at a
 // restart, written back once at the end -- nothing is loaded in the decision loop on the log's behalf.  Compiled in a translation
 // unit of their own; no size-renewing form.
-#if defined(DCM_LOG) && DCM_RENEW == 2
+// The epsilon-greedy forms (DCM_EXPLORE defined; dcm_rollout_explore): k_ex_rollout_fast and its renewing form k_exrn_rollout_fast, the
+// logging form's text with one more argument, explore_q32.  The explore words of 64 decisions are computed one per lane at the key
+// refill (a third lane vector beside kv and kv2: one mix64, the high word kept); per decision one v_readlane, one scalar compare
+// against the argument and a wave-uniform choice between DCM_POLICY_RANDOM and the base policy in front of decide_logged's ONE apply.
+// The log may be unset there (lg.len null: cap 0, nothing stored, no length loaded or written back).  Compiled in a translation unit
+// of their own; no size-renewing form.
+#if (defined(DCM_LOG) || defined(DCM_EXPLORE)) && DCM_RENEW == 2
 #error "no size-renewing logging form"
 #endif
 #ifdef DCM_POLICY
@@ -22,12 +28,22 @@
 #error "no size-renewing greedy form"
 #endif
 #define KPOLICY_PARAM , int policy
+#elif defined(DCM_EXPLORE)
+#define KPOLICY_PARAM , int policy, uint64_t explore_q32, RouteLog lg
 #elif defined(DCM_LOG)
 #define KPOLICY_PARAM , int policy, RouteLog lg
 #else
 #define KPOLICY_PARAM
 #endif
-#if defined(DCM_LOG) && DCM_RENEW
+#if defined(DCM_EXPLORE) && DCM_RENEW
+#define KNAME k_exrn_rollout_fast
+#define KRENEW_PARAM , Renew rn
+#define KSIZES const int32_t* sizes
+#elif defined(DCM_EXPLORE)
+#define KNAME k_ex_rollout_fast
+#define KRENEW_PARAM
+#define KSIZES const int32_t* sizes
+#elif defined(DCM_LOG) && DCM_RENEW
 #define KNAME k_lgrn_rollout_fast
 #define KRENEW_PARAM , Renew rn
 #define KSIZES const int32_t* sizes
@@ -82,7 +98,15 @@ __global__ __launch_bounds__(WAVE, 4) void KNAME(int A, int T, int PA, int PT, K
     F f{S, (uint4*)(smem + (SimT::SCR_IN_LDS ? L.lds_bytes() : SimT::lds_image_bytes(L)))};
     f.init(lane);
     f.build_removal_table(lane);
-#ifdef DCM_LOG
+#ifdef DCM_EXPLORE
+    // the env's rows of the log as in the logging form, or -- no log set -- a log of cap 0, to which apply<true> stores nothing
+    const bool logged = lg.len != nullptr;
+    FastLog fl{lg.task + (size_t)e * BA * lg.cap, lg.arrival + (size_t)e * BA * lg.cap, logged ? lg.cap : 0,
+               (logged && f.inA) ? lg.len[(size_t)e * BA + f.la] : 0};
+    // explore_q32 in [0, 2^32] against a 32-bit word: `always` (2^32) or an unsigned 32-bit compare, both on the scalar unit
+    const bool x_all = (explore_q32 >> 32) != 0ull;
+    const uint32_t x_q = (uint32_t)explore_q32;
+#elif defined(DCM_LOG)
     // the env's rows of the log: wave-uniform bases, the lane's entry addressed by a 32-bit offset (dcm_set_rollout_log bounds A x cap)
     FastLog fl{lg.task + (size_t)e * BA * lg.cap, lg.arrival + (size_t)e * BA * lg.cap, lg.cap, f.inA ? lg.len[(size_t)e * BA + f.la] : 0};
 #endif
@@ -104,6 +128,9 @@ __global__ __launch_bounds__(WAVE, 4) void KNAME(int A, int T, int PA, int PT, K
     // chain of 20 scalar ones at the head of every decision); ki = the lane that holds the current decision's key
     uint64_t kv = mix64(gd + GAMMA * (uint64_t)lane);
     uint64_t kv2 = mix64(kv + GAMMA);                  // ... and their second keys (follower draws 0 and 1)
+#ifdef DCM_EXPLORE
+    uint32_t xv = (uint32_t)(mix64(kv ^ EXPLORE_SALT) >> 32);   // ... and their explore words
+#endif
     int ki = 0;
     const uint64_t d0 = h.d;
     typename F::R r;
@@ -161,7 +188,7 @@ __global__ __launch_bounds__(WAVE, 4) void KNAME(int A, int T, int PA, int PT, K
 #if DCM_RENEW
                 f.load_consts(r);
 #endif
-#ifdef DCM_LOG
+#if defined(DCM_LOG) || defined(DCM_EXPLORE)
                 fl.len = 0;                                                       // the log is the new episode's
 #endif
                 need_adv = true;
@@ -183,7 +210,11 @@ __global__ __launch_bounds__(WAVE, 4) void KNAME(int A, int T, int PA, int PT, K
                 FPHK(f, 12);
                 CNT(0);
                 const uint64_t k1 = rl(kv, ki), k2 = rl(kv2, ki);
-#ifdef DCM_LOG
+#ifdef DCM_EXPLORE
+                // the decision explores iff its explore word < explore_q32: then the random policy's action (protocol slot 1), else the base pick
+                const bool explores = x_all || rl(xv, ki) < x_q;
+                const int rlen = f.decide_logged(r, h, P, lane, k1, agrow, tkrow, mkp, &k2, explores ? DCM_POLICY_RANDOM : policy, fl);
+#elif defined(DCM_LOG)
                 const int rlen = f.decide_logged(r, h, P, lane, k1, agrow, tkrow, mkp, &k2, policy, fl);
 #elif defined(DCM_POLICY)
                 const int rlen = f.decide_policy(r, h, P, lane, k1, agrow, tkrow, mkp, &k2, policy);
@@ -192,7 +223,11 @@ __global__ __launch_bounds__(WAVE, 4) void KNAME(int A, int T, int PA, int PT, K
 #endif
                 if (h.flags & DCM_FLAG_DONE) break;
                 gd += GAMMA;
+#ifdef DCM_EXPLORE
+                if (++ki == WAVE) { kv = mix64(gd + GAMMA * (uint64_t)lane); kv2 = mix64(kv + GAMMA); xv = (uint32_t)(mix64(kv ^ EXPLORE_SALT) >> 32); ki = 0; }
+#else
                 if (++ki == WAVE) { kv = mix64(gd + GAMMA * (uint64_t)lane); kv2 = mix64(kv + GAMMA); ki = 0; if constexpr (use_prio) set_prio(ep); }
+#endif
                 left--;
                 // worker.py:53 else same group, next leader.  The next-group step is an add, not a branch: as an arm of an
                 // if / else-if beside next_event() it shared a latch block with the event, whose task_update / agent_update results
@@ -218,7 +253,9 @@ __global__ __launch_bounds__(WAVE, 4) void KNAME(int A, int T, int PA, int PT, K
     PH_FLUSH(lane);
     FPHK(f, 13);
     FPH_FLUSH(f, lane);
-#ifdef DCM_LOG
+#ifdef DCM_EXPLORE
+    if (logged && f.inA) lg.len[(size_t)e * BA + f.la] = fl.len;
+#elif defined(DCM_LOG)
     if (f.inA) lg.len[(size_t)e * BA + f.la] = fl.len;
 #endif
     const int64_t steps = (int64_t)(left0 - left);

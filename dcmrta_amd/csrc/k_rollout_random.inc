@@ -12,7 +12,11 @@
 // renewing form k_lgrn_rollout_random, the same text with two more arguments: `policy`, which here covers all three policies (wave-
 // uniform: DCM_POLICY_RANDOM takes protocol slot 1 as the plain form does), and the log, which apply_and_advance appends to and whose
 // lengths the env zeroes when it restarts an episode.  Compiled in a translation unit of their own; no size-renewing form.
-#if defined(DCM_LOG) && DCM_RENEW == 2
+// The epsilon-greedy forms (DCM_EXPLORE defined; dcm_rollout_explore): k_ex_rollout_random and its renewing form k_exrn_rollout_random,
+// the logging form's text with one more argument, explore_q32: a decision whose explore word (mix64(key_1 ^ EXPLORE_SALT) >> 32) is
+// below it takes pick_random_action, every other one pick_policy_action of the base policy (FIRST / NEAREST).  The budget is the
+// greedy forms' (rollout_budget_policy); the log may be unset (lg.len null).  A translation unit of their own; no size-renewing form.
+#if (defined(DCM_LOG) || defined(DCM_EXPLORE)) && DCM_RENEW == 2
 #error "no size-renewing logging form"
 #endif
 #ifdef DCM_POLICY
@@ -20,12 +24,22 @@
 #error "no size-renewing greedy form"
 #endif
 #define KPOLICY_PARAM , int policy
+#elif defined(DCM_EXPLORE)
+#define KPOLICY_PARAM , int policy, uint64_t explore_q32, RouteLog lg
 #elif defined(DCM_LOG)
 #define KPOLICY_PARAM , int policy, RouteLog lg
 #else
 #define KPOLICY_PARAM
 #endif
-#if defined(DCM_LOG) && DCM_RENEW
+#if defined(DCM_EXPLORE) && DCM_RENEW
+#define KNAME k_exrn_rollout_random
+#define KRENEW_PARAM , Renew rn
+#define KSIZES const int32_t* sizes
+#elif defined(DCM_EXPLORE)
+#define KNAME k_ex_rollout_random
+#define KRENEW_PARAM
+#define KSIZES const int32_t* sizes
+#elif defined(DCM_LOG) && DCM_RENEW
 #define KNAME k_lgrn_rollout_random
 #define KRENEW_PARAM , Renew rn
 #define KSIZES const int32_t* sizes
@@ -86,7 +100,7 @@ __global__ __launch_bounds__(WAVE, 3) void KNAME(int A, int T, int PA, int PT, K
     // (wave-uniform branches otherwise, at every decision)
     const bool all_obs = agents_out && tasks_out && mask_out;
     double* row = summary + (size_t)e * 8;
-#ifdef DCM_POLICY
+#if defined(DCM_POLICY) || defined(DCM_EXPLORE)
     const int left0 = rollout_budget_policy(e, budget_all, budget_in, P);
 #elif defined(DCM_LOG)
     const int left0 = policy == DCM_POLICY_RANDOM ? rollout_budget(e, budget_all, budget_in) : rollout_budget_policy(e, budget_all, budget_in, P);
@@ -109,7 +123,9 @@ __global__ __launch_bounds__(WAVE, 3) void KNAME(int A, int T, int PA, int PT, K
 #elif DCM_RENEW
             wave_renew_instance_call(S, rec, rn, e, lane, xy);
 #endif
-#ifdef DCM_LOG
+#ifdef DCM_EXPLORE
+            if (lg.len) for (int a = lane; a < S.A(); a += WAVE) lg.len[(size_t)e * BA + a] = 0;   // the log, if set, is the new episode's
+#elif defined(DCM_LOG)
             for (int a = lane; a < S.A(); a += WAVE) lg.len[(size_t)e * BA + a] = 0;   // the log is the new episode's (as k_step's restart)
 #endif
             S.reset_state(h, lane);
@@ -128,7 +144,11 @@ __global__ __launch_bounds__(WAVE, 3) void KNAME(int A, int T, int PA, int PT, K
             if (all_obs) { __builtin_assume(ag != nullptr); __builtin_assume(tk != nullptr); __builtin_assume(mk != nullptr); S.observe(h, lane, leader, ag, tk, mk, xy); }
             else S.observe(h, lane, leader, ag, tk, mk, xy);
             PH_MARK(1);
-#ifdef DCM_POLICY
+#ifdef DCM_EXPLORE
+            // the decision explores iff its explore word < explore_q32 (wave-uniform): protocol slot 1 then, the base policy's pick otherwise
+            const bool explores = (uint64_t)(uint32_t)(mix64(k1 ^ EXPLORE_SALT) >> 32) < explore_q32;
+            const int action = explores ? S.pick_random_action(lane, k1) : S.pick_policy_action(lane, leader, policy, xy);
+#elif defined(DCM_POLICY)
             const int action = S.pick_policy_action(lane, leader, policy, xy);
 #elif defined(DCM_LOG)
             const int action = policy == DCM_POLICY_RANDOM ? S.pick_random_action(lane, k1) : S.pick_policy_action(lane, leader, policy, xy);
@@ -136,7 +156,7 @@ __global__ __launch_bounds__(WAVE, 3) void KNAME(int A, int T, int PA, int PT, K
             const int action = S.pick_random_action(lane, k1);
 #endif
             PH_MARK(2);
-#ifdef DCM_LOG
+#if defined(DCM_LOG) || defined(DCM_EXPLORE)
             S.template apply_and_advance<true>(h, P, lane, leader, gm, action, k1, -1, nullptr, row PH_PASS, lg, e * BA, false, 0, true, false, &xy);
 #else
             S.template apply_and_advance<true>(h, P, lane, leader, gm, action, k1, -1, nullptr, row PH_PASS, RouteLog{nullptr, nullptr, nullptr, 0}, 0, false, 0, true, false, &xy);

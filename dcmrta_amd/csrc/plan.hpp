@@ -104,6 +104,14 @@ inline Rollout log_rollout_kind(const Shape& s, bool obs_all_or_none) {
 }
 // ... and there is no size-renewing logging form: a launch that would take the k_rs_* form is refused while the log is set
 inline bool log_form_ok(RenewForm form) { return form != RenewForm::Sizes; }
+// dcm_rollout_explore (epsilon-greedy over DCM_POLICY_FIRST / DCM_POLICY_NEAREST).  The forms (k_ex_* / k_exrn_*) exist, like the
+// greedy ones, for the one-chunk register-resident kernel and for the general one only: Fast exactly where policy_rollout_kind says
+// Fast, the general kernel everywhere else.  The budget rule is the base policy's (policy_needs_budget).
+inline Rollout explore_rollout_kind(const Shape& s, bool obs_all_or_none) {
+    return rollout_kind(s, obs_all_or_none) == Rollout::Fast ? Rollout::Fast : Rollout::General;
+}
+// ... and there is no size-renewing form: a launch that would take the k_rs_* form is refused
+inline bool explore_form_ok(RenewForm form) { return form != RenewForm::Sizes; }
 // k_rollout_fast_g<NAC, NTC>: lane chunks of agents (1..2) and of tasks (2..4) from the batch dims
 inline int fast_g_agent_chunks(int A) { return A > LANES ? 2 : 1; }
 inline int fast_g_task_chunks(int T) { return T > 3 * LANES ? 4 : (T > 2 * LANES ? 3 : 2); }

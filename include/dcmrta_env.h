@@ -332,6 +332,25 @@ int dcm_rollout_policy(dcm_env *env, int32_t policy, int32_t episodes, int64_t m
                        const int64_t *max_decisions_in, float *agents_out, float *tasks_out,
                        uint8_t *mask_out, int64_t *steps_out, void *stream);
 
+/* The same persistent launch under an EPSILON-GREEDY policy: the sampling baseline (play a stochastic heuristic many times -- one
+ * instance replicated over the envs under different seeds -- and keep the best episode).  Every argument other than explore_q32
+ * means what it means in the greedy launch above; `policy` is the BASE policy, DCM_POLICY_FIRST or DCM_POLICY_NEAREST.
+ * Choice protocol (bit-exact everywhere): with key_1 = mix64(seed_e + GAMMA (d + 1)) of decision d, the decision's explore word is
+ *     mix64(key_1 XOR 0xD6E8FEB86659FD93) >> 32        (32 bits)
+ * and the decision EXPLORES iff explore word < explore_q32, a value in [0, 2^32] (epsilon = explore_q32 / 2^32).  An exploring
+ * decision takes exactly the random policy's action (protocol slot 1 over the unmasked tasks); every other decision takes the base
+ * policy's pick and does not consume slot 1.  The leader (slot 0), the followers (slots 2+j), the decision counter and the depot
+ * action when no task is unmasked are as always.  So explore_q32 = 0 is the greedy policy and explore_q32 = 2^32 the random one,
+ * bit for bit -- through this entry point's own kernels: there is no host-side shortcut for either value.
+ * The rollout log may be set (the best env's log is the plan) or not (return sampling on large batches).
+ * Refusals, nothing launched and nothing changed: a base policy other than FIRST / NEAREST (DCM_POLICY_RANDOM included) or
+ * explore_q32 > 2^32: DCM_ERR_INVALID.  A launch that would renew a ragged batch's SIZES: DCM_ERR_STATE.  On a handle with
+ * max_waiting_time <= 0 the base policy's rule holds: a decision budget must be given, else DCM_ERR_INVALID, and a negative entry
+ * of max_decisions_in counts as 0. */
+int dcm_rollout_explore(dcm_env *env, int32_t policy, uint64_t explore_q32, int32_t episodes, int64_t max_decisions,
+                        const int64_t *max_decisions_in, float *agents_out, float *tasks_out, uint8_t *mask_out,
+                        int64_t *steps_out, void *stream);
+
 /* Terminal results of the last finished episode (worker.py:87,103-108):
  * out[B,8] f64 = reward(-makespan), n_finished_tasks, success_rate, makespan, time_cost,
  *                waiting_time, travel_dist, efficiency. Rows of envs not yet done are NaN. */

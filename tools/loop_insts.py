@@ -2,6 +2,10 @@
 """Static instruction census of a persistent kernel's DECISION loop (developer tool, build container: needs only hipcc).
 
     python tools/loop_insts.py [-D...] [--kernel 'k_rollout_fast<20, 50, false, true, false>'] [--keep out.s] [--blocks]
+    python tools/loop_insts.py --kernel 'k_ex_rollout_fast<20, 50, false, true, false>' --extra-args 'int, uint64_t, RouteLog' -DDCM_TU_E
+
+--extra-args: the arguments a kernel form takes behind the common ones (k_hp_*: 'int'; k_lg_*: 'int, RouteLog'; k_ex_*: 'int, uint64_t,
+RouteLog'; the renewing forms: 'Renew' in front), together with the form's unit macro (-DDCM_TU_P / -DDCM_TU_L / -DDCM_TU_E).
 
 Compiles ONE explicit instantiation of the kernel (a scratch translation unit that includes dcmrta_env.hip with its host API
 compiled out: seconds instead of the minute the whole library takes), finds the decision loop -- the loop around decide()'s
@@ -62,6 +66,7 @@ def main():
     args = sys.argv[1:]
     kernel = "k_rollout_fast<20, 50, false, true, false>"
     keep, blocks, defs, dump, phases, weights = None, False, [], None, False, None
+    extra = ""
     i = 0
     while i < len(args):
         if args[i] == "--kernel":
@@ -70,6 +75,8 @@ def main():
             keep = args[i + 1]; i += 2
         elif args[i] == "--blocks":
             blocks = True; i += 1
+        elif args[i] == "--extra-args":
+            extra = ", " + args[i + 1]; i += 2
         elif args[i] == "--phases":                    # needs -DDCM_PHASE_MARKS: per-phase census between the FPHMARK comments
             phases = True; i += 1
         elif args[i] == "--weights":                   # --phases: JSON {"<phase>[ <sub-region>]": executions per decision}
@@ -82,10 +89,10 @@ def main():
     with tempfile.TemporaryDirectory() as td:
         tu = os.path.join(td, "one.hip")
         with open(tu, "w") as f:
-            f.write(f'#define DCM_DEVICE_ONLY_TU 1\n#include "{CSRC}/dcmrta_env.hip"\nnamespace {{ template __global__ void {kernel}{SIG}; }}\n')
+            f.write(f'#define DCM_DEVICE_ONLY_TU 1\n#include "{CSRC}/dcmrta_env.hip"\nnamespace {{ template __global__ void {kernel}{SIG[:-1] + extra + ")"}; }}\n')
         out = keep or os.path.join(td, "one.s")
         subprocess.check_call(["/opt/rocm/bin/hipcc", "--offload-arch=gfx950", "-O3", "-std=c++17", "-ffp-contract=off", "-fno-fast-math",
-                               "-S", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-mllvm", "-amdgpu-sched-strategy=max-ilp"] + ([] if "fast_g" in kernel else ["-mllvm", "-phi-elim-split-all-critical-edges=1", "-DDCM_SPLIT_G"]) + defs + [tu, "-o", out],
+                               "-S", "--cuda-device-only", "-Rpass-analysis=kernel-resource-usage", "-mllvm", "-amdgpu-sched-strategy=max-ilp"] + ([] if "fast_g" in kernel else ["-mllvm", "-phi-elim-split-all-critical-edges=1"] + ([] if any(d.startswith("-DDCM_TU_") for d in defs) else ["-DDCM_SPLIT_G"])) + defs + [tu, "-o", out],
                               stderr=open(os.path.join(td, "remarks.txt"), "w"))
         rem = open(os.path.join(td, "remarks.txt")).read()
         body = open(out).read().splitlines()
