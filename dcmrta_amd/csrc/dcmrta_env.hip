@@ -22,38 +22,41 @@
 #include <array>
 #include <cstdlib>
 #include <mutex>
+#include <tuple>
 
 #include "common.hpp"
 #include "np_stream.hpp"
 
 using namespace dcm;
 
-// Translation units (Makefile).  The library is built from this file twice: the main unit (-DDCM_SPLIT_G: every kernel but the
-// mid-size persistent one, which it reaches through dcm::launch_rollout_fast_g) with -mllvm -phi-elim-split-all-critical-edges=1,
-// and the unit of k_rollout_fast_g alone (-DDCM_TU_G) without that option -- it costs that kernel 4 % (8.19 -> 8.53 ms per 4096 x
-// 70A/130T launch) while it buys the one-chunk and the 50A/200T kernel 2.1 % / 1.3 %.  With neither macro (the developer tools'
+// Translation units (Makefile).  The library is built from this file five times; every unit but the main one holds device code and
+// its launchers only, and the main unit reaches them through the dcm::launch_rollout_* functions declared below.
+//   unit    macro          holds                                                          options
+//   env     -DDCM_SPLIT_G  the host API and every kernel that is not in a unit below      SPLIT SCHED
+//   env_g   -DDCM_TU_G     k_rollout_fast_g and its forms (rollout_fast_g.hpp)            SCHED
+//   env_p   -DDCM_TU_P     the greedy forms k_hp_* / k_hprn_* (rollout_policy.hpp)        SPLIT SCHED
+//   env_l   -DDCM_TU_L     the logging forms k_lg_* / k_lgrn_* (rollout_log.hpp)          SPLIT SCHED
+//   env_e   -DDCM_TU_E     the epsilon-greedy forms k_ex_* / k_exrn_* (rollout_explore.hpp)  SPLIT SCHED
+// SPLIT (-mllvm -phi-elim-split-all-critical-edges=1) costs k_rollout_fast_g 4 % (8.19 -> 8.53 ms per 4096 x 70A/130T launch) while it
+// buys the one-chunk and the 50A/200T kernel 2.1 % / 1.3 %: hence env_g.  The form units exist so that every kernel that was there
+// before them compiles from the text, and to the code, it had without them.  With none of the macros (the developer tools'
 // one-command builds) everything is in one unit.
-// A third unit (-DDCM_TU_P) holds the greedy-policy forms of the persistent kernels alone (k_hp_* / k_hprn_*, dcm_rollout_policy), with
-// the main unit's options: the main unit reaches them through dcm::launch_rollout_policy, and every kernel that existed before them
-// compiles from the text, and to the code, it had without them.
-// A fourth unit (-DDCM_TU_L) holds the logging forms alone (k_lg_* / k_lgrn_*, dcm_set_rollout_log) in the same way: the main unit
-// reaches them through dcm::launch_rollout_log.
-// A fifth unit (-DDCM_TU_E) holds the epsilon-greedy forms alone (k_ex_* / k_exrn_*, dcm_rollout_explore) in the same way: the main
-// unit reaches them through dcm::launch_rollout_explore.
 #if defined(DCM_TU_G) || defined(DCM_TU_P) || defined(DCM_TU_L) || defined(DCM_TU_E)
 #define DCM_DEVICE_ONLY_TU 1
+#elif !defined(DCM_SPLIT_G)
+#define DCM_ONE_UNIT 1
 #endif
-#if defined(DCM_TU_G) || (!defined(DCM_SPLIT_G) && !defined(DCM_TU_P) && !defined(DCM_TU_L) && !defined(DCM_TU_E))
+#if defined(DCM_TU_G) || defined(DCM_ONE_UNIT)
 #define DCM_HAVE_FAST_G 1     // this unit holds k_rollout_fast_g and its launcher
 #endif
-#if defined(DCM_TU_P) || (!defined(DCM_SPLIT_G) && !defined(DCM_TU_G) && !defined(DCM_TU_L) && !defined(DCM_TU_E))
-#define DCM_HAVE_POLICY 1     // this unit holds the greedy-policy forms and their launcher
+#if defined(DCM_TU_P) || defined(DCM_ONE_UNIT)
+#define DCM_HAVE_POLICY 1     // ... the greedy-policy forms and their launcher
 #endif
-#if defined(DCM_TU_L) || (!defined(DCM_SPLIT_G) && !defined(DCM_TU_G) && !defined(DCM_TU_P) && !defined(DCM_TU_E))
-#define DCM_HAVE_LOG 1        // this unit holds the logging forms and their launcher
+#if defined(DCM_TU_L) || defined(DCM_ONE_UNIT)
+#define DCM_HAVE_LOG 1        // ... the logging forms and their launcher
 #endif
-#if defined(DCM_TU_E) || (!defined(DCM_SPLIT_G) && !defined(DCM_TU_G) && !defined(DCM_TU_P) && !defined(DCM_TU_L))
-#define DCM_HAVE_EXPLORE 1    // this unit holds the epsilon-greedy forms and their launcher
+#if defined(DCM_TU_E) || defined(DCM_ONE_UNIT)
+#define DCM_HAVE_EXPLORE 1    // ... the epsilon-greedy forms and their launcher
 #endif
 namespace dcm {
 #if !defined(DCM_DEVICE_ONLY_TU)
@@ -82,18 +85,15 @@ struct RolloutArgs {
 };
 // k_rollout_fast_g<NAC, NTC, OBS> / k_rn_rollout_fast_g / k_rs_rollout_fast_g (rollout_fast_g.hpp, its own translation unit)
 void launch_rollout_fast_g(int nac, int ntc, bool obs, unsigned grid, Lay L, hipStream_t stream, const RolloutArgs& a);
-// the greedy-policy forms k_hp_rollout_fast / k_hp_rollout_random and their renewing forms k_hprn_* (rollout_policy.hpp, their own
-// translation unit).  fast: plan::policy_rollout_kind said Fast; a.policy: DCM_POLICY_FIRST or DCM_POLICY_NEAREST; a.form: Plain or Instance
-int launch_rollout_policy(plan::SimKind kind, bool fast, bool obs, unsigned grid, Lay L, hipStream_t stream, const RolloutArgs& a);
+// The greedy, logging and epsilon-greedy forms of k_rollout_fast / k_rollout_random (k_form.inc), each set in a translation unit of its
+// own.  fast: plan::form_rollout_kind said Fast; a.form: Plain or Instance; a.policy: DCM_POLICY_FIRST or DCM_POLICY_NEAREST, in the
+// logging forms any of the three; a.lg: the handle's rollout log, which the epsilon-greedy forms also take unset; a.explore_q32 <= 2^32.
+// Return 0, or -1 when `kind` has no one-chunk kernel (the caller asked plan::form_rollout_kind, so it has).
+// allow_lds_*: the form's share of dcm_create's dynamic-LDS limit (see there).
+using FormLauncher = int(plan::SimKind kind, bool fast, bool obs, unsigned grid, Lay L, hipStream_t stream, const RolloutArgs& a);
+FormLauncher launch_rollout_policy, launch_rollout_log, launch_rollout_explore;
 void allow_lds_policy(int lds);
-// the logging forms k_lg_rollout_fast / k_lg_rollout_random and their renewing forms k_lgrn_* (rollout_log.hpp, their own translation
-// unit).  fast: plan::log_rollout_kind said Fast; a.policy: any of the three; a.lg: the handle's rollout log; a.form: Plain or Instance
-int launch_rollout_log(plan::SimKind kind, bool fast, bool obs, unsigned grid, Lay L, hipStream_t stream, const RolloutArgs& a);
 void allow_lds_log(int lds);
-// the epsilon-greedy forms k_ex_rollout_fast / k_ex_rollout_random and their renewing forms k_exrn_* (rollout_explore.hpp, their own
-// translation unit).  fast: plan::explore_rollout_kind said Fast; a.policy: DCM_POLICY_FIRST or DCM_POLICY_NEAREST; a.explore_q32 <= 2^32;
-// a.lg: the handle's rollout log, set or not; a.form: Plain or Instance
-int launch_rollout_explore(plan::SimKind kind, bool fast, bool obs, unsigned grid, Lay L, hipStream_t stream, const RolloutArgs& a);
 void allow_lds_explore(int lds);
 }  // namespace dcm
 
@@ -1768,33 +1768,95 @@ struct DeviceGuard {
     ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
 };
 
-template <class K>
-void launch_rollout(K kernel, dim3 grid, dim3 block, unsigned lds_bytes, hipStream_t stream, const RolloutArgs& a) {
-    hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, a.A, a.T, a.PA, a.PT, a.kp, a.state, a.episodes, a.agents_out, a.tasks_out,
-                       a.mask_out, a.steps_out, a.summary, a.ablog, a.sizes, a.budget_all, a.budget_in, a.gscr, a.retlog, a.retcap);
+// Launch any form of a persistent rollout kernel: the 19 arguments they all start with (RolloutArgs), then the form's own -- `tail`:
+// a.rn in a renewing form, then what DCM_FORM_LAUNCHERS says.  A size-renewing form (k_rs_*) declares `sizes` writable: it writes the
+// drawn sizes to the handle's size table.
+template <class... P, class... Tail>
+void launch(void (*kernel)(P...), unsigned grid, unsigned lds_bytes, hipStream_t stream, const RolloutArgs& a, const Tail&... tail) {
+    using Sizes = std::tuple_element_t<13, std::tuple<P...>>;   // int32_t* in k_rs_*, const int32_t* everywhere else
+    hipLaunchKernelGGL(kernel, dim3(grid), dim3(WAVE), lds_bytes, stream, a.A, a.T, a.PA, a.PT, a.kp, a.state, a.episodes, a.agents_out,
+                       a.tasks_out, a.mask_out, a.steps_out, a.summary, a.ablog, const_cast<Sizes>(a.sizes), a.budget_all, a.budget_in,
+                       a.gscr, a.retlog, a.retcap, tail...);
 }
-// the same for the renewing form of a rollout kernel (k_rn_*)
 template <class K>
-void launch_rollout_rn(K kernel, dim3 grid, dim3 block, unsigned lds_bytes, hipStream_t stream, const RolloutArgs& a) {
-    hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, a.A, a.T, a.PA, a.PT, a.kp, a.state, a.episodes, a.agents_out, a.tasks_out,
-                       a.mask_out, a.steps_out, a.summary, a.ablog, a.sizes, a.budget_all, a.budget_in, a.gscr, a.retlog, a.retcap, a.rn);
+void allow_lds(K kernel, int bytes) { (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes); }
+
+// dcm::launch_rollout_<form> and dcm::allow_lds_<form> for a form F (DCM_FORM_LAUNCHERS): F names the form's four kernels and launches
+// the renewing or the plain one of a pair with the form's arguments.  (The renewing one is named first throughout: the kernels are
+// instantiated in the order they are named here, and a unit's assembly lists them in that order.)
+template <class F>
+int launch_rollout_form(plan::SimKind kind, bool fast, bool obs, unsigned grid, Lay L, hipStream_t stream, const RolloutArgs& a) {
+    if (fast) {
+#define CALLF(CA, CT, RS, OBS) \
+    F::go(F::template fast_rn<CA, CT, RS, OBS>(), F::template fast<CA, CT, RS, OBS>(), grid, rollout_fast_lds_bytes<CA, CT, RS>(L), stream, a)
+#define CALL(CA, CT, RS) do { if (obs) { CALLF(CA, CT, RS, true); } else { CALLF(CA, CT, RS, false); } } while (0)
+        switch (kind) { FOR_EACH_FAST(SIM_CASE) default: return -1; }
+#undef CALL
+#undef CALLF
+        return 0;
+    }
+#define CALL(CA, CT, RS, ...) \
+    F::go(F::template general_rn<CA, CT, RS, ##__VA_ARGS__>(), F::template general<CA, CT, RS, ##__VA_ARGS__>(), grid, rollout_random_lds_bytes<CA, CT, RS>(L), stream, a)
+    switch (kind) { FOR_EACH_INSTANCE(SIM_CASE) }
+#undef CALL
+    return 0;
 }
-// ... and for the size-renewing form (k_rs_*), which writes the drawn sizes to the handle's size table
-template <class K>
-void launch_rollout_rs(K kernel, dim3 grid, dim3 block, unsigned lds_bytes, hipStream_t stream, const RolloutArgs& a) {
-    hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, a.A, a.T, a.PA, a.PT, a.kp, a.state, a.episodes, a.agents_out, a.tasks_out,
-                       a.mask_out, a.steps_out, a.summary, a.ablog, const_cast<int32_t*>(a.sizes), a.budget_all, a.budget_in, a.gscr, a.retlog,
-                       a.retcap, a.rn);
+template <class F>
+void allow_lds_form(int lds) {
+#define SET_ATTR(KIND, CA, CT, RS, ...)                                   \
+    allow_lds(F::template general<CA, CT, RS, ##__VA_ARGS__>(), lds);     \
+    allow_lds(F::template general_rn<CA, CT, RS, ##__VA_ARGS__>(), lds);
+    FOR_EACH_INSTANCE(SET_ATTR)
+#undef SET_ATTR
+#define SET_FAST(KIND, CA, CT, RS)                                        \
+    allow_lds(F::template fast<CA, CT, RS, true>(), lds);                 \
+    allow_lds(F::template fast<CA, CT, RS, false>(), lds);                \
+    allow_lds(F::template fast_rn<CA, CT, RS, true>(), lds);              \
+    allow_lds(F::template fast_rn<CA, CT, RS, false>(), lds);
+    FOR_EACH_FAST(SET_FAST)
+#undef SET_FAST
 }
 }  // namespace
+
+// One form: its name, the prefix of its plain and of its renewing kernels, and the arguments it appends behind retcap (behind a.rn in
+// the renewing ones).  The form has no size-renewing kernels and no wave-priority (PRIO) instantiation.
+#define DCM_FORM_LAUNCHERS(FORM, plain, renewing, ...)                                                                              \
+    namespace {                                                                                                                      \
+    struct FORM##_form {                                                                                                             \
+        template <int CA, int CT, bool RS, bool OBS> static auto fast() { return plain##rollout_fast<CA, CT, RS, OBS>; }             \
+        template <int CA, int CT, bool RS, bool OBS> static auto fast_rn() { return renewing##rollout_fast<CA, CT, RS, OBS>; }       \
+        template <int CA, int CT, bool RS, int MC = M> static auto general() { return plain##rollout_random<CA, CT, RS, MC>; }       \
+        template <int CA, int CT, bool RS, int MC = M> static auto general_rn() { return renewing##rollout_random<CA, CT, RS, MC>; } \
+        template <class KRN, class K>                                                                                                \
+        static void go(KRN k_rn, K k, unsigned grid, unsigned lds_bytes, hipStream_t stream, const RolloutArgs& a) {                 \
+            if (a.form == plan::RenewForm::Instance) launch(k_rn, grid, lds_bytes, stream, a, a.rn, __VA_ARGS__);                    \
+            else launch(k, grid, lds_bytes, stream, a, __VA_ARGS__);                                                                 \
+        }                                                                                                                            \
+    };                                                                                                                               \
+    }                                                                                                                                \
+    int dcm::launch_rollout_##FORM(plan::SimKind kind, bool fast, bool obs, unsigned grid, Lay L, hipStream_t stream, const RolloutArgs& a) { \
+        return launch_rollout_form<FORM##_form>(kind, fast, obs, grid, L, stream, a);                                                \
+    }                                                                                                                                \
+    void dcm::allow_lds_##FORM(int lds) { allow_lds_form<FORM##_form>(lds); }
+// Each pair inside its unit's guard: a device-only unit learns from here which kernels to instantiate
+#ifdef DCM_HAVE_POLICY
+DCM_FORM_LAUNCHERS(policy, k_hp_, k_hprn_, a.policy)
+#endif
+#ifdef DCM_HAVE_LOG
+DCM_FORM_LAUNCHERS(log, k_lg_, k_lgrn_, a.policy, a.lg)
+#endif
+#ifdef DCM_HAVE_EXPLORE
+DCM_FORM_LAUNCHERS(explore, k_ex_, k_exrn_, a.policy, a.explore_q32, a.lg)
+#endif
+#undef DCM_FORM_LAUNCHERS
 
 #ifdef DCM_HAVE_FAST_G
 void dcm::launch_rollout_fast_g(int nac, int ntc, bool obs, unsigned grid, Lay L, hipStream_t stream, const RolloutArgs& a) {
 #define CALLG(NAC, NTC, OBS)                                                                                                          \
     do {                                                                                                                              \
-        if (a.form == plan::RenewForm::Sizes) launch_rollout_rs(k_rs_rollout_fast_g<NAC, NTC, OBS>, dim3(grid), dim3(WAVE), rollout_fast_g_lds_bytes(L), stream, a); \
-        else if (a.form == plan::RenewForm::Instance) launch_rollout_rn(k_rn_rollout_fast_g<NAC, NTC, OBS>, dim3(grid), dim3(WAVE), rollout_fast_g_lds_bytes(L), stream, a); \
-        else launch_rollout(k_rollout_fast_g<NAC, NTC, OBS>, dim3(grid), dim3(WAVE), rollout_fast_g_lds_bytes(L), stream, a);        \
+        if (a.form == plan::RenewForm::Sizes) launch(k_rs_rollout_fast_g<NAC, NTC, OBS>, grid, rollout_fast_g_lds_bytes(L), stream, a, a.rn); \
+        else if (a.form == plan::RenewForm::Instance) launch(k_rn_rollout_fast_g<NAC, NTC, OBS>, grid, rollout_fast_g_lds_bytes(L), stream, a, a.rn); \
+        else launch(k_rollout_fast_g<NAC, NTC, OBS>, grid, rollout_fast_g_lds_bytes(L), stream, a);                                  \
     } while (0)
 #define CALLT(NAC, OBS) do { if (ntc > 3) { CALLG(NAC, 4, OBS); } else if (ntc > 2) { CALLG(NAC, 3, OBS); } else { CALLG(NAC, 2, OBS); } } while (0)
 #define CALLA(OBS) do { if (nac > 1) { CALLT(2, OBS); } else { CALLT(1, OBS); } } while (0)
@@ -1802,185 +1864,6 @@ void dcm::launch_rollout_fast_g(int nac, int ntc, bool obs, unsigned grid, Lay L
 #undef CALLA
 #undef CALLT
 #undef CALLG
-}
-#endif
-
-#ifdef DCM_HAVE_POLICY
-namespace {
-// the greedy-policy forms take `policy` last (k_hp_*), behind the renewal argument in the renewing ones (k_hprn_*)
-template <class K>
-void launch_rollout_hp(K kernel, dim3 grid, dim3 block, unsigned lds_bytes, hipStream_t stream, const RolloutArgs& a) {
-    hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, a.A, a.T, a.PA, a.PT, a.kp, a.state, a.episodes, a.agents_out, a.tasks_out,
-                       a.mask_out, a.steps_out, a.summary, a.ablog, a.sizes, a.budget_all, a.budget_in, a.gscr, a.retlog, a.retcap, a.policy);
-}
-template <class K>
-void launch_rollout_hprn(K kernel, dim3 grid, dim3 block, unsigned lds_bytes, hipStream_t stream, const RolloutArgs& a) {
-    hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, a.A, a.T, a.PA, a.PT, a.kp, a.state, a.episodes, a.agents_out, a.tasks_out,
-                       a.mask_out, a.steps_out, a.summary, a.ablog, a.sizes, a.budget_all, a.budget_in, a.gscr, a.retlog, a.retcap, a.rn,
-                       a.policy);
-}
-template <class K>
-void allow_lds_hp(K kernel, int bytes) { (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes); }
-}  // namespace
-
-// Returns 0, or -1 when `kind` has no one-chunk kernel (the caller asked plan::policy_rollout_kind, so it has)
-int dcm::launch_rollout_policy(plan::SimKind kind, bool fast, bool obs, unsigned grid, Lay L, hipStream_t stream, const RolloutArgs& a) {
-    const bool renew = a.form == plan::RenewForm::Instance;
-    if (fast) {
-#define CALLF(CA, CT, RS, OBS)                                                                                                             \
-    do {                                                                                                                                   \
-        if (renew) launch_rollout_hprn(k_hprn_rollout_fast<CA, CT, RS, OBS>, dim3(grid), dim3(WAVE), rollout_fast_lds_bytes<CA, CT, RS>(L), stream, a); \
-        else launch_rollout_hp(k_hp_rollout_fast<CA, CT, RS, OBS>, dim3(grid), dim3(WAVE), rollout_fast_lds_bytes<CA, CT, RS>(L), stream, a);           \
-    } while (0)
-#define CALL(CA, CT, RS) do { if (obs) { CALLF(CA, CT, RS, true); } else { CALLF(CA, CT, RS, false); } } while (0)
-        switch (kind) { FOR_EACH_FAST(SIM_CASE) default: return -1; }
-#undef CALL
-#undef CALLF
-        return 0;
-    }
-#define CALL(CA, CT, RS, ...)                                                                                                              \
-    do {                                                                                                                                   \
-        if (renew) launch_rollout_hprn(k_hprn_rollout_random<CA, CT, RS, ##__VA_ARGS__>, dim3(grid), dim3(WAVE), rollout_random_lds_bytes<CA, CT, RS>(L), stream, a); \
-        else launch_rollout_hp(k_hp_rollout_random<CA, CT, RS, ##__VA_ARGS__>, dim3(grid), dim3(WAVE), rollout_random_lds_bytes<CA, CT, RS>(L), stream, a);           \
-    } while (0)
-    switch (kind) { FOR_EACH_INSTANCE(SIM_CASE) }
-#undef CALL
-    return 0;
-}
-// dcm_create: the greedy forms' share of the dynamic-LDS limit (see there)
-void dcm::allow_lds_policy(int lds) {
-#define SET_ATTR(KIND, CA, CT, RS, ...)                                  \
-    allow_lds_hp(k_hp_rollout_random<CA, CT, RS, ##__VA_ARGS__>, lds);   \
-    allow_lds_hp(k_hprn_rollout_random<CA, CT, RS, ##__VA_ARGS__>, lds);
-    FOR_EACH_INSTANCE(SET_ATTR)
-#undef SET_ATTR
-#define SET_FAST(KIND, CA, CT, RS)                                       \
-    allow_lds_hp(k_hp_rollout_fast<CA, CT, RS, true>, lds);              \
-    allow_lds_hp(k_hp_rollout_fast<CA, CT, RS, false>, lds);             \
-    allow_lds_hp(k_hprn_rollout_fast<CA, CT, RS, true>, lds);            \
-    allow_lds_hp(k_hprn_rollout_fast<CA, CT, RS, false>, lds);
-    FOR_EACH_FAST(SET_FAST)
-#undef SET_FAST
-}
-#endif
-
-#ifdef DCM_HAVE_LOG
-namespace {
-// the logging forms take `policy` and the log last (k_lg_*), behind the renewal argument in the renewing ones (k_lgrn_*)
-template <class K>
-void launch_rollout_lg(K kernel, dim3 grid, dim3 block, unsigned lds_bytes, hipStream_t stream, const RolloutArgs& a) {
-    hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, a.A, a.T, a.PA, a.PT, a.kp, a.state, a.episodes, a.agents_out, a.tasks_out,
-                       a.mask_out, a.steps_out, a.summary, a.ablog, a.sizes, a.budget_all, a.budget_in, a.gscr, a.retlog, a.retcap, a.policy,
-                       a.lg);
-}
-template <class K>
-void launch_rollout_lgrn(K kernel, dim3 grid, dim3 block, unsigned lds_bytes, hipStream_t stream, const RolloutArgs& a) {
-    hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, a.A, a.T, a.PA, a.PT, a.kp, a.state, a.episodes, a.agents_out, a.tasks_out,
-                       a.mask_out, a.steps_out, a.summary, a.ablog, a.sizes, a.budget_all, a.budget_in, a.gscr, a.retlog, a.retcap, a.rn,
-                       a.policy, a.lg);
-}
-template <class K>
-void allow_lds_lg(K kernel, int bytes) { (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes); }
-}  // namespace
-
-// Returns 0, or -1 when `kind` has no one-chunk kernel (the caller asked plan::log_rollout_kind, so it has)
-int dcm::launch_rollout_log(plan::SimKind kind, bool fast, bool obs, unsigned grid, Lay L, hipStream_t stream, const RolloutArgs& a) {
-    const bool renew = a.form == plan::RenewForm::Instance;
-    if (fast) {
-#define CALLF(CA, CT, RS, OBS)                                                                                                             \
-    do {                                                                                                                                   \
-        if (renew) launch_rollout_lgrn(k_lgrn_rollout_fast<CA, CT, RS, OBS>, dim3(grid), dim3(WAVE), rollout_fast_lds_bytes<CA, CT, RS>(L), stream, a); \
-        else launch_rollout_lg(k_lg_rollout_fast<CA, CT, RS, OBS>, dim3(grid), dim3(WAVE), rollout_fast_lds_bytes<CA, CT, RS>(L), stream, a);           \
-    } while (0)
-#define CALL(CA, CT, RS) do { if (obs) { CALLF(CA, CT, RS, true); } else { CALLF(CA, CT, RS, false); } } while (0)
-        switch (kind) { FOR_EACH_FAST(SIM_CASE) default: return -1; }
-#undef CALL
-#undef CALLF
-        return 0;
-    }
-#define CALL(CA, CT, RS, ...)                                                                                                              \
-    do {                                                                                                                                   \
-        if (renew) launch_rollout_lgrn(k_lgrn_rollout_random<CA, CT, RS, ##__VA_ARGS__>, dim3(grid), dim3(WAVE), rollout_random_lds_bytes<CA, CT, RS>(L), stream, a); \
-        else launch_rollout_lg(k_lg_rollout_random<CA, CT, RS, ##__VA_ARGS__>, dim3(grid), dim3(WAVE), rollout_random_lds_bytes<CA, CT, RS>(L), stream, a);           \
-    } while (0)
-    switch (kind) { FOR_EACH_INSTANCE(SIM_CASE) }
-#undef CALL
-    return 0;
-}
-// dcm_create: the logging forms' share of the dynamic-LDS limit (see there)
-void dcm::allow_lds_log(int lds) {
-#define SET_ATTR(KIND, CA, CT, RS, ...)                                  \
-    allow_lds_lg(k_lg_rollout_random<CA, CT, RS, ##__VA_ARGS__>, lds);   \
-    allow_lds_lg(k_lgrn_rollout_random<CA, CT, RS, ##__VA_ARGS__>, lds);
-    FOR_EACH_INSTANCE(SET_ATTR)
-#undef SET_ATTR
-#define SET_FAST(KIND, CA, CT, RS)                                       \
-    allow_lds_lg(k_lg_rollout_fast<CA, CT, RS, true>, lds);              \
-    allow_lds_lg(k_lg_rollout_fast<CA, CT, RS, false>, lds);             \
-    allow_lds_lg(k_lgrn_rollout_fast<CA, CT, RS, true>, lds);            \
-    allow_lds_lg(k_lgrn_rollout_fast<CA, CT, RS, false>, lds);
-    FOR_EACH_FAST(SET_FAST)
-#undef SET_FAST
-}
-#endif
-
-#ifdef DCM_HAVE_EXPLORE
-namespace {
-// the epsilon-greedy forms take `policy`, explore_q32 and the log last (k_ex_*), behind the renewal argument in the renewing ones (k_exrn_*)
-template <class K>
-void launch_rollout_ex(K kernel, dim3 grid, dim3 block, unsigned lds_bytes, hipStream_t stream, const RolloutArgs& a) {
-    hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, a.A, a.T, a.PA, a.PT, a.kp, a.state, a.episodes, a.agents_out, a.tasks_out,
-                       a.mask_out, a.steps_out, a.summary, a.ablog, a.sizes, a.budget_all, a.budget_in, a.gscr, a.retlog, a.retcap, a.policy,
-                       a.explore_q32, a.lg);
-}
-template <class K>
-void launch_rollout_exrn(K kernel, dim3 grid, dim3 block, unsigned lds_bytes, hipStream_t stream, const RolloutArgs& a) {
-    hipLaunchKernelGGL(kernel, grid, block, lds_bytes, stream, a.A, a.T, a.PA, a.PT, a.kp, a.state, a.episodes, a.agents_out, a.tasks_out,
-                       a.mask_out, a.steps_out, a.summary, a.ablog, a.sizes, a.budget_all, a.budget_in, a.gscr, a.retlog, a.retcap, a.rn,
-                       a.policy, a.explore_q32, a.lg);
-}
-template <class K>
-void allow_lds_ex(K kernel, int bytes) { (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes); }
-}  // namespace
-
-// Returns 0, or -1 when `kind` has no one-chunk kernel (the caller asked plan::explore_rollout_kind, so it has)
-int dcm::launch_rollout_explore(plan::SimKind kind, bool fast, bool obs, unsigned grid, Lay L, hipStream_t stream, const RolloutArgs& a) {
-    const bool renew = a.form == plan::RenewForm::Instance;
-    if (fast) {
-#define CALLF(CA, CT, RS, OBS)                                                                                                             \
-    do {                                                                                                                                   \
-        if (renew) launch_rollout_exrn(k_exrn_rollout_fast<CA, CT, RS, OBS>, dim3(grid), dim3(WAVE), rollout_fast_lds_bytes<CA, CT, RS>(L), stream, a); \
-        else launch_rollout_ex(k_ex_rollout_fast<CA, CT, RS, OBS>, dim3(grid), dim3(WAVE), rollout_fast_lds_bytes<CA, CT, RS>(L), stream, a);           \
-    } while (0)
-#define CALL(CA, CT, RS) do { if (obs) { CALLF(CA, CT, RS, true); } else { CALLF(CA, CT, RS, false); } } while (0)
-        switch (kind) { FOR_EACH_FAST(SIM_CASE) default: return -1; }
-#undef CALL
-#undef CALLF
-        return 0;
-    }
-#define CALL(CA, CT, RS, ...)                                                                                                              \
-    do {                                                                                                                                   \
-        if (renew) launch_rollout_exrn(k_exrn_rollout_random<CA, CT, RS, ##__VA_ARGS__>, dim3(grid), dim3(WAVE), rollout_random_lds_bytes<CA, CT, RS>(L), stream, a); \
-        else launch_rollout_ex(k_ex_rollout_random<CA, CT, RS, ##__VA_ARGS__>, dim3(grid), dim3(WAVE), rollout_random_lds_bytes<CA, CT, RS>(L), stream, a);           \
-    } while (0)
-    switch (kind) { FOR_EACH_INSTANCE(SIM_CASE) }
-#undef CALL
-    return 0;
-}
-// dcm_create: the epsilon-greedy forms' share of the dynamic-LDS limit (see there)
-void dcm::allow_lds_explore(int lds) {
-#define SET_ATTR(KIND, CA, CT, RS, ...)                                  \
-    allow_lds_ex(k_ex_rollout_random<CA, CT, RS, ##__VA_ARGS__>, lds);   \
-    allow_lds_ex(k_exrn_rollout_random<CA, CT, RS, ##__VA_ARGS__>, lds);
-    FOR_EACH_INSTANCE(SET_ATTR)
-#undef SET_ATTR
-#define SET_FAST(KIND, CA, CT, RS)                                       \
-    allow_lds_ex(k_ex_rollout_fast<CA, CT, RS, true>, lds);              \
-    allow_lds_ex(k_ex_rollout_fast<CA, CT, RS, false>, lds);             \
-    allow_lds_ex(k_exrn_rollout_fast<CA, CT, RS, true>, lds);            \
-    allow_lds_ex(k_exrn_rollout_fast<CA, CT, RS, false>, lds);
-    FOR_EACH_FAST(SET_FAST)
-#undef SET_FAST
 }
 #endif
 
@@ -1996,9 +1879,6 @@ int largest_lds_request(Lay L) {
     if (lds + DUMMY_SLOT_BYTES <= CU_LDS_BYTES) lds += DUMMY_SLOT_BYTES;
     return (int)lds;
 }
-template <class K>
-void allow_lds(K kernel, int bytes) { (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes); }
-
 // ADVICE.md item 2 is to be fixed here: an error from hipStreamIsCapturing counts as "capturing"
 bool stream_capturing(void* stream) {
     hipStreamCaptureStatus cs = hipStreamCaptureStatusNone;
@@ -2055,6 +1935,56 @@ std::array<Section, 4> state_sections(const dcm_env* env) {
     const bool with_sizes = env->sizes && renew_sizes_opted_in(env);
     return {{{env->state, B * env->L.rec_bytes()}, {env->summary, B * 8 * sizeof(double)},
              {env->ablog, side_bytes(env->p.n_envs, env->A, env->T)}, {env->sizes, with_sizes ? B * 2 * sizeof(int32_t) : 0}}};
+}
+
+// the arguments every persistent rollout kernel starts with, from the handle and the call
+dcm::RolloutArgs rollout_args(const dcm_env* env, plan::RenewForm form, int32_t episodes, int64_t max_decisions, const int64_t* max_decisions_in,
+                              float* agents_out, float* tasks_out, uint8_t* mask_out, int64_t* steps_out) {
+    return {DIMS(env), env->kp, env->state, (int)episodes, agents_out, tasks_out, mask_out, steps_out, env->summary,
+            env->ablog, (const int32_t*)env->sizes, max_decisions, max_decisions_in, env->gscratch, env->retlog,
+            (int)env->retcap, renew_args(env), form};
+}
+
+// A greedy, logging or epsilon-greedy form to the host: its launcher, and what `fn` says when a size-renewing launch asks for it
+struct RolloutForm { dcm::FormLauncher* launch; const char* no_sizes_form; };
+const RolloutForm FORM_POLICY{dcm::launch_rollout_policy,
+    "%s: no greedy policy while a ragged batch renews its sizes (DCM_PARAM_RENEW_SIZES with a stride set): "
+    "clear the stride with dcm_set_instance_renewal(env, 0), or use DCM_POLICY_RANDOM"};
+const RolloutForm FORM_LOG{dcm::launch_rollout_log,
+    "%s: no rollout log while a ragged batch renews its sizes (DCM_PARAM_RENEW_SIZES with a stride set): "
+    "clear the stride with dcm_set_instance_renewal(env, 0), or clear the log with dcm_set_rollout_log(env, NULL, NULL, NULL, 0)"};
+const RolloutForm FORM_EXPLORE{dcm::launch_rollout_explore,
+    "%s: no epsilon-greedy policy while a ragged batch renews its sizes (DCM_PARAM_RENEW_SIZES with a stride "
+    "set): clear the stride with dcm_set_instance_renewal(env, 0), or use dcm_rollout_random"};
+
+// The common tail of the entry points that launch such a form: dcm_rollout_policy, dcm_rollout_explore, and dcm_rollout_random /
+// dcm_rollout_policy while the rollout log is set (FORM_LOG, under any of the three policies).  The caller `fn` has validated its
+// arguments.  explore_q32: 0 and 2^32 run the same kernels as every other value, no shortcut to the greedy / random forms.
+int rollout_form(dcm_env* env, const char* fn, const RolloutForm& form, int32_t policy, uint64_t explore_q32, int32_t episodes,
+                 int64_t max_decisions, const int64_t* max_decisions_in, float* agents_out, float* tasks_out, uint8_t* mask_out,
+                 int64_t* steps_out, void* stream) {
+    if (!plan::form_ok(launch_form(env))) return fail(DCM_ERR_STATE, form.no_sizes_form, fn);
+    DCM_TRY(dcm::flush_pending(env, stream));
+    dcm::RolloutArgs ra = rollout_args(env, renewing_launch(env, stream), episodes, max_decisions, max_decisions_in, agents_out, tasks_out,
+                                       mask_out, steps_out);
+    ra.policy = policy;
+    ra.explore_q32 = explore_q32;
+    ra.lg = env->rollout_log;          // (the epsilon-greedy forms take it set or not: one set of forms)
+    const bool all_obs = agents_out && tasks_out && mask_out, no_obs = !agents_out && !tasks_out && !mask_out;
+    const plan::Shape shape = shape_of(env);
+    const bool fast = plan::form_rollout_kind(shape, all_obs || no_obs) == plan::Rollout::Fast;
+    if (form.launch(plan::sim_kind(shape), fast, all_obs, (unsigned)env->p.n_envs, env->L, (hipStream_t)stream, ra) != 0)
+        return fail(DCM_ERR_STATE, "internal error: a one-chunk kernel on another layout");
+    LAUNCH_OK();
+    return DCM_OK;
+}
+
+// plan::policy_needs_budget: `fn` refuses an unlimited greedy launch there
+int need_budget(const dcm_env* env, const char* fn, int64_t max_decisions, const int64_t* max_decisions_in) {
+    if (plan::policy_needs_budget(shape_of(env)) && !max_decisions_in && max_decisions < 0)
+        return fail(DCM_ERR_INVALID, "%s: with max_waiting_time <= 0 a greedy policy does not end its episodes (a dropped member takes "
+                                     "the same task again at the same time): give a decision budget", fn);
+    return DCM_OK;
 }
 }  // namespace
 
@@ -2475,46 +2405,21 @@ int dcm_set_rollout_log(dcm_env* env, int16_t* route_task, double* route_arrival
     return make_route_log("dcm_set_rollout_log", route_task, route_arrival, route_len, cap, &env->rollout_log);
 }
 
-namespace {
-// dcm_rollout_random / dcm_rollout_policy while the rollout log is set (dcm_set_rollout_log): the logging kernel forms, under any of
-// the three policies.  The caller has validated its arguments; `fn` names it in the refusal.
-int rollout_logged(dcm_env* env, const char* fn, int32_t policy, int32_t episodes, int64_t max_decisions, const int64_t* max_decisions_in,
-                   float* agents_out, float* tasks_out, uint8_t* mask_out, int64_t* steps_out, void* stream) {
-    if (!plan::log_form_ok(launch_form(env)))
-        return fail(DCM_ERR_STATE, "%s: no rollout log while a ragged batch renews its sizes (DCM_PARAM_RENEW_SIZES with a stride set): "
-                                   "clear the stride with dcm_set_instance_renewal(env, 0), or clear the log with dcm_set_rollout_log(env, NULL, NULL, NULL, 0)", fn);
-    DCM_TRY(dcm::flush_pending(env, stream));
-    const plan::RenewForm form = renewing_launch(env, stream);
-    dcm::RolloutArgs ra{DIMS(env), env->kp, env->state, (int)episodes, agents_out, tasks_out, mask_out, steps_out, env->summary,
-                        env->ablog, (const int32_t*)env->sizes, max_decisions, max_decisions_in, env->gscratch, env->retlog,
-                        (int)env->retcap, renew_args(env), form};
-    ra.policy = policy;
-    ra.lg = env->rollout_log;
-    const bool all_obs = agents_out && tasks_out && mask_out, no_obs = !agents_out && !tasks_out && !mask_out;
-    const plan::Shape shape = shape_of(env);
-    const bool fast = plan::log_rollout_kind(shape, all_obs || no_obs) == plan::Rollout::Fast;
-    if (dcm::launch_rollout_log(plan::sim_kind(shape), fast, all_obs, (unsigned)env->p.n_envs, env->L, (hipStream_t)stream, ra) != 0)
-        return fail(DCM_ERR_STATE, "internal error: a one-chunk kernel on another layout");
-    LAUNCH_OK();
-    return DCM_OK;
-}
-}  // namespace
-
 int dcm_rollout_random(dcm_env* env, int32_t episodes, int64_t max_decisions, const int64_t* max_decisions_in,
                        float* agents_out, float* tasks_out, uint8_t* mask_out, int64_t* steps_out, void* stream) {
     CHECK_ENV(env);
     if (!env->reset_done) return fail(DCM_ERR_STATE, "dcm_rollout_random: call dcm_reset first");
     if (episodes < 1) return fail(DCM_ERR_INVALID, "dcm_rollout_random: episodes must be >= 1");
     if (env->rollout_log.len)
-        return rollout_logged(env, "dcm_rollout_random", DCM_POLICY_RANDOM, episodes, max_decisions, max_decisions_in, agents_out, tasks_out,
-                              mask_out, steps_out, stream);
+        return rollout_form(env, "dcm_rollout_random", FORM_LOG, DCM_POLICY_RANDOM, 0, episodes, max_decisions, max_decisions_in, agents_out,
+                            tasks_out, mask_out, steps_out, stream);
     DCM_TRY(dcm::flush_pending(env, stream));
     // the renewing (k_rn_*) or size-renewing (k_rs_*) form of whichever kernel serves the handle, while a stride is set (dcm_set_instance_renewal)
     const plan::RenewForm form = renewing_launch(env, stream);
     const bool renew = form == plan::RenewForm::Instance, renew_sizes = form == plan::RenewForm::Sizes;
-    const dcm::RolloutArgs ra{DIMS(env), env->kp, env->state, (int)episodes, agents_out, tasks_out, mask_out, steps_out, env->summary,
-                              env->ablog, (const int32_t*)env->sizes, max_decisions, max_decisions_in, env->gscratch, env->retlog,
-                              (int)env->retcap, renew_args(env), form};
+    const dcm::RolloutArgs ra = rollout_args(env, form, episodes, max_decisions, max_decisions_in, agents_out, tasks_out, mask_out, steps_out);
+    const unsigned grid = (unsigned)env->p.n_envs;
+    const hipStream_t hs = (hipStream_t)stream;
     // The register-resident kernels have the same contract and the same results as the general one (tests/test_gpu_rollout.py runs both)
     const bool all_obs = agents_out && tasks_out && mask_out, no_obs = !agents_out && !tasks_out && !mask_out;
     switch (plan::rollout_kind(shape_of(env), all_obs || no_obs)) {
@@ -2524,15 +2429,14 @@ int dcm_rollout_random(dcm_env* env, int32_t episodes, int64_t max_decisions, co
 #define CALL(CA, CT, RS) do { if (prio) { if (all_obs) { CALLF(CA, CT, RS, true, true); } else { CALLF(CA, CT, RS, false, true); } }   \
                               else { if (all_obs) { CALLF(CA, CT, RS, true, false); } else { CALLF(CA, CT, RS, false, false); } } } while (0)
         if (renew_sizes) {
-#define CALLF(CA, CT, RS, OBS, PRIO) \
-    launch_rollout_rs(k_rs_rollout_fast<CA, CT, RS, OBS, PRIO>, GRID(env), rollout_fast_lds_bytes<CA, CT, RS>(env->L), (hipStream_t)stream, ra)
+#define CALLF(CA, CT, RS, OBS, PRIO) launch(k_rs_rollout_fast<CA, CT, RS, OBS, PRIO>, grid, rollout_fast_lds_bytes<CA, CT, RS>(env->L), hs, ra, ra.rn)
             DISPATCH_ONE_CHUNK_RAGGED(env);
 #undef CALLF
         } else {
-#define CALLF(CA, CT, RS, OBS, PRIO)                                                                                                          \
-    do {                                                                                                                                          \
-        if (renew) launch_rollout_rn(k_rn_rollout_fast<CA, CT, RS, OBS, PRIO>, GRID(env), rollout_fast_lds_bytes<CA, CT, RS>(env->L), (hipStream_t)stream, ra); \
-        else launch_rollout(k_rollout_fast<CA, CT, RS, OBS, PRIO>, GRID(env), rollout_fast_lds_bytes<CA, CT, RS>(env->L), (hipStream_t)stream, ra);  \
+#define CALLF(CA, CT, RS, OBS, PRIO)                                                                                                  \
+    do {                                                                                                                              \
+        if (renew) launch(k_rn_rollout_fast<CA, CT, RS, OBS, PRIO>, grid, rollout_fast_lds_bytes<CA, CT, RS>(env->L), hs, ra, ra.rn); \
+        else launch(k_rollout_fast<CA, CT, RS, OBS, PRIO>, grid, rollout_fast_lds_bytes<CA, CT, RS>(env->L), hs, ra);                 \
     } while (0)
             DISPATCH_ONE_CHUNK(env);
 #undef CALLF
@@ -2541,29 +2445,27 @@ int dcm_rollout_random(dcm_env* env, int32_t episodes, int64_t max_decisions, co
         break;
     }
     case plan::Rollout::FastMc:                                                 // (exact shape, never ragged: no size-renewing form)
-#define CALLM(OBS)                                                                                                                      \
-    do {                                                                                                                                \
-        if (renew) launch_rollout_rn(k_rn_rollout_fast_mc<50, 200, OBS>, GRID(env), FastM<50, 200, OBS>::LDS_BYTES, (hipStream_t)stream, ra); \
-        else launch_rollout(k_rollout_fast_mc<50, 200, OBS>, GRID(env), FastM<50, 200, OBS>::LDS_BYTES, (hipStream_t)stream, ra);       \
+#define CALLM(OBS)                                                                                                \
+    do {                                                                                                          \
+        if (renew) launch(k_rn_rollout_fast_mc<50, 200, OBS>, grid, FastM<50, 200, OBS>::LDS_BYTES, hs, ra, ra.rn); \
+        else launch(k_rollout_fast_mc<50, 200, OBS>, grid, FastM<50, 200, OBS>::LDS_BYTES, hs, ra);               \
     } while (0)
         if (all_obs) { CALLM(true); } else { CALLM(false); }
 #undef CALLM
         break;
     case plan::Rollout::FastG:
-        dcm::launch_rollout_fast_g(plan::fast_g_agent_chunks(env->A), plan::fast_g_task_chunks(env->T), all_obs, (unsigned)env->p.n_envs,
-                                   env->L, (hipStream_t)stream, ra);
+        dcm::launch_rollout_fast_g(plan::fast_g_agent_chunks(env->A), plan::fast_g_task_chunks(env->T), all_obs, grid, env->L, hs, ra);
         break;
     case plan::Rollout::General:
         if (renew_sizes) {
-#define CALL(CA, CT, RS, ...) \
-    launch_rollout_rs(k_rs_rollout_random<CA, CT, RS, ##__VA_ARGS__>, GRID(env), rollout_random_lds_bytes<CA, CT, RS>(env->L), (hipStream_t)stream, ra)
+#define CALL(CA, CT, RS, ...) launch(k_rs_rollout_random<CA, CT, RS, ##__VA_ARGS__>, grid, rollout_random_lds_bytes<CA, CT, RS>(env->L), hs, ra, ra.rn)
             DISPATCH_RAGGED(env);
 #undef CALL
         } else {
 #define CALL(CA, CT, RS, ...)                                                                                                                    \
     do {                                                                                                                                         \
-        if (renew) launch_rollout_rn(k_rn_rollout_random<CA, CT, RS, ##__VA_ARGS__>, GRID(env), rollout_random_lds_bytes<CA, CT, RS>(env->L), (hipStream_t)stream, ra); \
-        else launch_rollout(k_rollout_random<CA, CT, RS, ##__VA_ARGS__>, GRID(env), rollout_random_lds_bytes<CA, CT, RS>(env->L), (hipStream_t)stream, ra); \
+        if (renew) launch(k_rn_rollout_random<CA, CT, RS, ##__VA_ARGS__>, grid, rollout_random_lds_bytes<CA, CT, RS>(env->L), hs, ra, ra.rn);    \
+        else launch(k_rollout_random<CA, CT, RS, ##__VA_ARGS__>, grid, rollout_random_lds_bytes<CA, CT, RS>(env->L), hs, ra);                    \
     } while (0)
             DISPATCH_ENV(env);
 #undef CALL
@@ -2583,28 +2485,9 @@ int dcm_rollout_policy(dcm_env* env, int32_t policy, int32_t episodes, int64_t m
         return fail(DCM_ERR_INVALID, "dcm_rollout_policy: unknown policy (DCM_POLICY_RANDOM, DCM_POLICY_FIRST, DCM_POLICY_NEAREST)");
     if (!env->reset_done) return fail(DCM_ERR_STATE, "dcm_rollout_policy: call dcm_reset first");
     if (episodes < 1) return fail(DCM_ERR_INVALID, "dcm_rollout_policy: episodes must be >= 1");
-    if (plan::policy_needs_budget(shape_of(env)) && !max_decisions_in && max_decisions < 0)
-        return fail(DCM_ERR_INVALID, "dcm_rollout_policy: with max_waiting_time <= 0 a greedy policy does not end its episodes (a dropped member takes "
-                                     "the same task again at the same time): give a decision budget");
-    if (env->rollout_log.len)
-        return rollout_logged(env, "dcm_rollout_policy", policy, episodes, max_decisions, max_decisions_in, agents_out, tasks_out, mask_out,
-                              steps_out, stream);
-    if (!plan::policy_form_ok(launch_form(env)))
-        return fail(DCM_ERR_STATE, "dcm_rollout_policy: no greedy policy while a ragged batch renews its sizes (DCM_PARAM_RENEW_SIZES with a stride set): "
-                                   "clear the stride with dcm_set_instance_renewal(env, 0), or use DCM_POLICY_RANDOM");
-    DCM_TRY(dcm::flush_pending(env, stream));
-    const plan::RenewForm form = renewing_launch(env, stream);
-    dcm::RolloutArgs ra{DIMS(env), env->kp, env->state, (int)episodes, agents_out, tasks_out, mask_out, steps_out, env->summary,
-                        env->ablog, (const int32_t*)env->sizes, max_decisions, max_decisions_in, env->gscratch, env->retlog,
-                        (int)env->retcap, renew_args(env), form};
-    ra.policy = policy;
-    const bool all_obs = agents_out && tasks_out && mask_out, no_obs = !agents_out && !tasks_out && !mask_out;
-    const plan::Shape shape = shape_of(env);
-    const bool fast = plan::policy_rollout_kind(shape, all_obs || no_obs) == plan::Rollout::Fast;
-    if (dcm::launch_rollout_policy(plan::sim_kind(shape), fast, all_obs, (unsigned)env->p.n_envs, env->L, (hipStream_t)stream, ra) != 0)
-        return fail(DCM_ERR_STATE, "internal error: a one-chunk kernel on another layout");
-    LAUNCH_OK();
-    return DCM_OK;
+    DCM_TRY(need_budget(env, "dcm_rollout_policy", max_decisions, max_decisions_in));
+    return rollout_form(env, "dcm_rollout_policy", env->rollout_log.len ? FORM_LOG : FORM_POLICY, policy, 0, episodes, max_decisions,
+                        max_decisions_in, agents_out, tasks_out, mask_out, steps_out, stream);
 }
 
 int dcm_rollout_explore(dcm_env* env, int32_t policy, uint64_t explore_q32, int32_t episodes, int64_t max_decisions,
@@ -2616,27 +2499,9 @@ int dcm_rollout_explore(dcm_env* env, int32_t policy, uint64_t explore_q32, int3
     if (explore_q32 > (1ull << 32)) return fail(DCM_ERR_INVALID, "dcm_rollout_explore: explore_q32 must be <= 2^32");
     if (!env->reset_done) return fail(DCM_ERR_STATE, "dcm_rollout_explore: call dcm_reset first");
     if (episodes < 1) return fail(DCM_ERR_INVALID, "dcm_rollout_explore: episodes must be >= 1");
-    if (plan::policy_needs_budget(shape_of(env)) && !max_decisions_in && max_decisions < 0)
-        return fail(DCM_ERR_INVALID, "dcm_rollout_explore: with max_waiting_time <= 0 a greedy policy does not end its episodes (a dropped member takes "
-                                     "the same task again at the same time): give a decision budget");
-    if (!plan::explore_form_ok(launch_form(env)))
-        return fail(DCM_ERR_STATE, "dcm_rollout_explore: no epsilon-greedy policy while a ragged batch renews its sizes (DCM_PARAM_RENEW_SIZES with a stride "
-                                   "set): clear the stride with dcm_set_instance_renewal(env, 0), or use dcm_rollout_random");
-    DCM_TRY(dcm::flush_pending(env, stream));
-    const plan::RenewForm form = renewing_launch(env, stream);
-    dcm::RolloutArgs ra{DIMS(env), env->kp, env->state, (int)episodes, agents_out, tasks_out, mask_out, steps_out, env->summary,
-                        env->ablog, (const int32_t*)env->sizes, max_decisions, max_decisions_in, env->gscratch, env->retlog,
-                        (int)env->retcap, renew_args(env), form};
-    ra.policy = policy;
-    ra.explore_q32 = explore_q32;      // (0 and 2^32 run the same kernels as every other value: no shortcut to the greedy / random forms)
-    ra.lg = env->rollout_log;          // set or not: one set of forms
-    const bool all_obs = agents_out && tasks_out && mask_out, no_obs = !agents_out && !tasks_out && !mask_out;
-    const plan::Shape shape = shape_of(env);
-    const bool fast = plan::explore_rollout_kind(shape, all_obs || no_obs) == plan::Rollout::Fast;
-    if (dcm::launch_rollout_explore(plan::sim_kind(shape), fast, all_obs, (unsigned)env->p.n_envs, env->L, (hipStream_t)stream, ra) != 0)
-        return fail(DCM_ERR_STATE, "internal error: a one-chunk kernel on another layout");
-    LAUNCH_OK();
-    return DCM_OK;
+    DCM_TRY(need_budget(env, "dcm_rollout_explore", max_decisions, max_decisions_in));
+    return rollout_form(env, "dcm_rollout_explore", FORM_EXPLORE, policy, explore_q32, episodes, max_decisions, max_decisions_in, agents_out,
+                        tasks_out, mask_out, steps_out, stream);
 }
 
 int dcm_summary(dcm_env* env, double* out, void* stream) {

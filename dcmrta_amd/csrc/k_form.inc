@@ -1,0 +1,78 @@
+// k_form.inc -- the forms of a kernel text: one text, compiled once per form, each time under another name and with that form's
+// arguments.  A text (k_step.inc, k_step_fast.inc, k_rollout_random.inc, k_rollout_fast.inc, k_rollout_fast_mc.inc,
+// k_rollout_fast_g.inc) says
+//     #define KBASE rollout_fast         its name without the prefix
+//     #define KPOLICY_FORMS 1            only if it has the forms of the second table
+//     #include "k_form.inc"
+// in front of its kernel, declares it as KNAME(..., KSIZES, ... int retcap KRENEW_PARAM KPOLICY_PARAM), and ends with
+// #include "k_form_end.inc".  Whoever includes the text sets DCM_RENEW and at most one of DCM_POLICY, DCM_LOG, DCM_EXPLORE.
+//
+//   DCM_RENEW   KNAME          launched                                            KRENEW_PARAM   KSIZES
+//   0           k_<base>       without a renewal stride                            --             const int32_t* sizes
+//   1           k_rn_<base>    with a stride (dcm_set_instance_renewal), uniform   , Renew rn     const int32_t* sizes
+//   2           k_rs_<base>    with a stride, ragged (DCM_PARAM_RENEW_SIZES)       , Renew rn     int32_t* sizes
+// k_rn_*: an env that restarts an episode first replaces its instance (wave_renew_instance, instgen.hpp).  k_rs_*, for the
+// instantiations that read per-env sizes: the restarting env draws its next SIZES with its next instance
+// (wave_renew_instance_sized), writes them to the handle's size table and carries on as an env of those sizes: everything the kernel
+// derived from the old ones at its head is derived again at the restart.
+//
+//   macro         KNAME (DCM_RENEW 0 / 1)        entry point                          KPOLICY_PARAM
+//   DCM_POLICY    k_hp_<base> / k_hprn_<base>    dcm_rollout_policy, FIRST / NEAREST  , int policy
+//   DCM_LOG       k_lg_<base> / k_lgrn_<base>    either, dcm_set_rollout_log set      , int policy, RouteLog lg
+//   DCM_EXPLORE   k_ex_<base> / k_exrn_<base>    dcm_rollout_explore                  , int policy, uint64_t explore_q32, RouteLog lg
+// Greedy: the action comes from `policy` (wave-uniform) instead of protocol slot 1.  Logging: `policy` covers all three policies
+// (DCM_POLICY_RANDOM takes slot 1 as the plain form does) and every agent_step is appended to the log.  Epsilon-greedy: the logging
+// form with explore_q32; the log may be unset there (lg.len null).  These forms exist for k_rollout_fast and k_rollout_random only,
+// each set in a translation unit of its own (rollout_policy.hpp, rollout_log.hpp, rollout_explore.hpp), and none of them has a
+// size-renewing form: the host refuses that launch (plan::form_ok).
+//
+// Two kernels from one text leave the first as it was: a form holds nothing of the others and compiles to the code it had before
+// they existed (DESIGN 4, 6).  A new form: one #elif here, its rollout_<form>.hpp, one DCM_FORM_LAUNCHERS line in dcmrta_env.hip.
+#ifndef KBASE
+#error "k_form.inc: the including text sets KBASE"
+#endif
+#if defined(DCM_POLICY) + defined(DCM_LOG) + defined(DCM_EXPLORE) > 1
+#error "at most one of DCM_POLICY, DCM_LOG, DCM_EXPLORE"
+#endif
+#if (defined(DCM_POLICY) || defined(DCM_LOG) || defined(DCM_EXPLORE)) && !defined(KPOLICY_FORMS)
+#error "this kernel text has no greedy, logging or epsilon-greedy form"
+#endif
+#if (defined(DCM_LOG) || defined(DCM_EXPLORE)) && DCM_RENEW == 2
+#error "no size-renewing logging form"
+#endif
+#if defined(DCM_POLICY) && DCM_RENEW == 2
+#error "no size-renewing greedy form"
+#endif
+
+#if DCM_RENEW
+#define KFORM_PICK(plain, renewing) renewing
+#define KRENEW_PARAM , Renew rn
+#else
+#define KFORM_PICK(plain, renewing) plain
+#define KRENEW_PARAM
+#endif
+#if DCM_RENEW == 2
+#define KSIZES int32_t* sizes
+#else
+#define KSIZES const int32_t* sizes
+#endif
+
+#if defined(DCM_POLICY)
+#define KPREFIX KFORM_PICK(k_hp_, k_hprn_)
+#define KPOLICY_PARAM , int policy
+#elif defined(DCM_LOG)
+#define KPREFIX KFORM_PICK(k_lg_, k_lgrn_)
+#define KPOLICY_PARAM , int policy, RouteLog lg
+#elif defined(DCM_EXPLORE)
+#define KPREFIX KFORM_PICK(k_ex_, k_exrn_)
+#define KPOLICY_PARAM , int policy, uint64_t explore_q32, RouteLog lg
+#elif DCM_RENEW == 2
+#define KPREFIX k_rs_
+#define KPOLICY_PARAM
+#else
+#define KPREFIX KFORM_PICK(k_, k_rn_)
+#define KPOLICY_PARAM
+#endif
+#define KFORM_PASTE_(prefix, base) prefix##base
+#define KFORM_PASTE(prefix, base) KFORM_PASTE_(prefix, base)
+#define KNAME KFORM_PASTE(KPREFIX, KBASE)

@@ -1,77 +1,15 @@
-// k_rollout_fast.inc -- the kernel k_rollout_fast, compiled twice by rollout_fast.hpp: as k_rollout_fast (DCM_RENEW 0) and as its renewing form k_rn_rollout_fast
-// (DCM_RENEW 1), which has one more argument, Renew rn, and is launched while dcm_set_instance_renewal has set a stride: an env that
-// restarts an episode first replaces its instance (wave_renew_instance, instgen.hpp).  Two kernels from one text: the plain
-// form holds nothing of the renewal and compiles to the code it had without it (DESIGN 6).
-// A third form, k_rs_rollout_fast (DCM_RENEW 2, DCM_PARAM_RENEW_SIZES), for the instantiations that read per-env sizes: on a ragged generated
-// batch the restarting env draws its next SIZES with its next instance (wave_renew_instance_sized) and carries on as an env of those
-// sizes: everything the kernel derived from the old ones at its head is derived again at the restart.  `sizes` is writable there.
-// The greedy-policy forms (DCM_POLICY defined; dcm_rollout_policy with DCM_POLICY_FIRST / DCM_POLICY_NEAREST): k_hp_rollout_fast and its
-// renewing form k_hprn_rollout_fast, the same text with one more wave-uniform argument, `policy`, and the action taken from it instead of
-// protocol slot 1.  Compiled in a translation unit of their own; the forms above hold nothing of them.  No size-renewing form.
-// The logging forms (DCM_LOG defined; a launch of either entry point while dcm_set_rollout_log is set): k_lg_rollout_fast and its
-// renewing form k_lgrn_rollout_fast, the same text with two more arguments: `policy`, which here covers all three policies (wave-
-// uniform: DCM_POLICY_RANDOM takes protocol slot 1 as the plain form does), and the log, to which Fast<>::apply appends where it
-// commits the member lanes.  Lane a keeps agent a's running length in a register (FastLog): loaded once at the head, zeroed at a
-// restart, written back once at the end -- nothing is loaded in the decision loop on the log's behalf.  Compiled in a translation
-// unit of their own; no size-renewing form.
-// The epsilon-greedy forms (DCM_EXPLORE defined; dcm_rollout_explore): k_ex_rollout_fast and its renewing form k_exrn_rollout_fast, the
-// logging form's text with one more argument, explore_q32.  The explore words of 64 decisions are computed one per lane at the key
-// refill (a third lane vector beside kv and kv2: one mix64, the high word kept); per decision one v_readlane, one scalar compare
-// against the argument and a wave-uniform choice between DCM_POLICY_RANDOM and the base policy in front of decide_logged's ONE apply.
-// The log may be unset there (lg.len null: cap 0, nothing stored, no length loaded or written back).  Compiled in a translation unit
-// of their own; no size-renewing form.
-#if (defined(DCM_LOG) || defined(DCM_EXPLORE)) && DCM_RENEW == 2
-#error "no size-renewing logging form"
-#endif
-#ifdef DCM_POLICY
-#if DCM_RENEW == 2
-#error "no size-renewing greedy form"
-#endif
-#define KPOLICY_PARAM , int policy
-#elif defined(DCM_EXPLORE)
-#define KPOLICY_PARAM , int policy, uint64_t explore_q32, RouteLog lg
-#elif defined(DCM_LOG)
-#define KPOLICY_PARAM , int policy, RouteLog lg
-#else
-#define KPOLICY_PARAM
-#endif
-#if defined(DCM_EXPLORE) && DCM_RENEW
-#define KNAME k_exrn_rollout_fast
-#define KRENEW_PARAM , Renew rn
-#define KSIZES const int32_t* sizes
-#elif defined(DCM_EXPLORE)
-#define KNAME k_ex_rollout_fast
-#define KRENEW_PARAM
-#define KSIZES const int32_t* sizes
-#elif defined(DCM_LOG) && DCM_RENEW
-#define KNAME k_lgrn_rollout_fast
-#define KRENEW_PARAM , Renew rn
-#define KSIZES const int32_t* sizes
-#elif defined(DCM_LOG)
-#define KNAME k_lg_rollout_fast
-#define KRENEW_PARAM
-#define KSIZES const int32_t* sizes
-#elif defined(DCM_POLICY) && DCM_RENEW
-#define KNAME k_hprn_rollout_fast
-#define KRENEW_PARAM , Renew rn
-#define KSIZES const int32_t* sizes
-#elif defined(DCM_POLICY)
-#define KNAME k_hp_rollout_fast
-#define KRENEW_PARAM
-#define KSIZES const int32_t* sizes
-#elif DCM_RENEW == 2
-#define KNAME k_rs_rollout_fast
-#define KRENEW_PARAM , Renew rn
-#define KSIZES int32_t* sizes
-#elif DCM_RENEW
-#define KNAME k_rn_rollout_fast
-#define KRENEW_PARAM , Renew rn
-#define KSIZES const int32_t* sizes
-#else
-#define KNAME k_rollout_fast
-#define KRENEW_PARAM
-#define KSIZES const int32_t* sizes
-#endif
+// k_rollout_fast.inc -- the kernel k_rollout_fast and all its forms (k_form.inc), compiled once per form: the plain, renewing and
+// size-renewing ones by rollout_fast.hpp, the others by rollout_policy.hpp, rollout_log.hpp and rollout_explore.hpp.
+// Logging forms: Fast<>::apply appends to the log where it commits the member lanes.  Lane a keeps agent a's running length in a
+// register (FastLog): loaded once at the head, zeroed at a restart, written back once at the end -- nothing is loaded in the decision
+// loop on the log's behalf.
+// Epsilon-greedy forms: the explore words of 64 decisions are computed one per lane at the key refill (a third lane vector beside kv
+// and kv2: one mix64, the high word kept); per decision one v_readlane, one scalar compare against explore_q32 and a wave-uniform
+// choice between DCM_POLICY_RANDOM and the base policy in front of decide_logged's ONE apply.  With the log unset: cap 0, nothing
+// stored, no length loaded or written back.
+#define KBASE rollout_fast
+#define KPOLICY_FORMS 1
+#include "k_form.inc"
 template <int CA, int CT, bool RS, bool OBS, bool PRIO = false>
 __global__ __launch_bounds__(WAVE, 4) void KNAME(int A, int T, int PA, int PT, KP P, unsigned char* state, int episodes,
                                                       float* agents_out, float* tasks_out, uint8_t* mask_out,
@@ -272,7 +210,4 @@ __global__ __launch_bounds__(WAVE, 4) void KNAME(int A, int T, int PA, int PT, K
     WSYNC();
     S.store_record(rec, lane);
 }
-#undef KNAME
-#undef KRENEW_PARAM
-#undef KSIZES
-#undef KPOLICY_PARAM
+#include "k_form_end.inc"

@@ -1,23 +1,7 @@
-// k_rollout_fast_g.inc -- the kernel k_rollout_fast_g, compiled twice by rollout_fast_g.hpp: as k_rollout_fast_g (DCM_RENEW 0) and as its renewing form k_rn_rollout_fast_g
-// (DCM_RENEW 1), which has one more argument, Renew rn, and is launched while dcm_set_instance_renewal has set a stride: an env that
-// restarts an episode first replaces its instance (wave_renew_instance, instgen.hpp).  Two kernels from one text: the plain
-// form holds nothing of the renewal and compiles to the code it had without it (DESIGN 6).
-// A third form, k_rs_rollout_fast_g (DCM_RENEW 2, DCM_PARAM_RENEW_SIZES), for the instantiations that read per-env sizes: on a ragged generated
-// batch the restarting env draws its next SIZES with its next instance (wave_renew_instance_sized) and carries on as an env of those
-// sizes: everything the kernel derived from the old ones at its head is derived again at the restart.  `sizes` is writable there.
-#if DCM_RENEW == 2
-#define KNAME k_rs_rollout_fast_g
-#define KRENEW_PARAM , Renew rn
-#define KSIZES int32_t* sizes
-#elif DCM_RENEW
-#define KNAME k_rn_rollout_fast_g
-#define KRENEW_PARAM , Renew rn
-#define KSIZES const int32_t* sizes
-#else
-#define KNAME k_rollout_fast_g
-#define KRENEW_PARAM
-#define KSIZES const int32_t* sizes
-#endif
+// k_rollout_fast_g.inc -- the kernel k_rollout_fast_g and its forms k_rn_rollout_fast_g and k_rs_rollout_fast_g (k_form.inc),
+// compiled once per form by rollout_fast_g.hpp
+#define KBASE rollout_fast_g
+#include "k_form.inc"
 template <int NAC, int NTC, bool OBS>
 __global__ __launch_bounds__(WAVE, DCM_G_WAVES) void KNAME(int A, int T, int PA, int PT, KP P, unsigned char* state, int episodes,
                                                         float* agents_out, float* tasks_out, uint8_t* mask_out,
@@ -126,6 +110,4 @@ __global__ __launch_bounds__(WAVE, DCM_G_WAVES) void KNAME(int A, int T, int PA,
     WSYNC();
     S.store_record(rec, lane);
 }
-#undef KNAME
-#undef KRENEW_PARAM
-#undef KSIZES
+#include "k_form_end.inc"

@@ -1,14 +1,7 @@
-// k_rollout_fast_mc.inc -- the kernel k_rollout_fast_mc, compiled twice by rollout_fast_mc.hpp: as k_rollout_fast_mc (DCM_RENEW 0) and as its renewing form k_rn_rollout_fast_mc
-// (DCM_RENEW 1), which has one more argument, Renew rn, and is launched while dcm_set_instance_renewal has set a stride: an env that
-// restarts an episode first replaces its instance (wave_renew_instance, instgen.hpp).  Two kernels from one text: the plain
-// form holds nothing of the renewal and compiles to the code it had without it (DESIGN 6).
-#if DCM_RENEW
-#define KNAME k_rn_rollout_fast_mc
-#define KRENEW_PARAM , Renew rn
-#else
-#define KNAME k_rollout_fast_mc
-#define KRENEW_PARAM
-#endif
+// k_rollout_fast_mc.inc -- the kernel k_rollout_fast_mc and its renewing form k_rn_rollout_fast_mc (k_form.inc), compiled once per
+// form by rollout_fast_mc.hpp.  An exact shape, never ragged: no size-renewing form.
+#define KBASE rollout_fast_mc
+#include "k_form.inc"
 template <int CA, int CT, bool OBS>
 __global__ __launch_bounds__(WAVE, DCM_MC_WAVES) void KNAME(int A, int T, int PA, int PT, KP P, unsigned char* state, int episodes,
                                                          float* agents_out, float* tasks_out, uint8_t* mask_out,
@@ -108,5 +101,4 @@ __global__ __launch_bounds__(WAVE, DCM_MC_WAVES) void KNAME(int A, int T, int PA
     WSYNC();
     S.store_record(rec, lane);
 }
-#undef KNAME
-#undef KRENEW_PARAM
+#include "k_form_end.inc"

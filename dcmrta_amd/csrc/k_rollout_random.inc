@@ -1,73 +1,12 @@
-// k_rollout_random.inc -- the kernel k_rollout_random, compiled twice by dcmrta_env.hip: as k_rollout_random (DCM_RENEW 0) and as its renewing form k_rn_rollout_random
-// (DCM_RENEW 1), which has one more argument, Renew rn, and is launched while dcm_set_instance_renewal has set a stride: an env that
-// restarts an episode first replaces its instance (wave_renew_instance, instgen.hpp).  Two kernels from one text: the plain
-// form holds nothing of the renewal and compiles to the code it had without it (DESIGN 6).
-// A third form, k_rs_rollout_random (DCM_RENEW 2, DCM_PARAM_RENEW_SIZES), for the instantiations that read per-env sizes: on a ragged generated
-// batch the restarting env draws its next SIZES with its next instance (wave_renew_instance_sized) and carries on as an env of those
-// sizes: everything the kernel derived from the old ones at its head is derived again at the restart.  `sizes` is writable there.
-// The greedy-policy forms (DCM_POLICY defined; dcm_rollout_policy with DCM_POLICY_FIRST / DCM_POLICY_NEAREST): k_hp_rollout_random and its
-// renewing form k_hprn_rollout_random, the same text with one more wave-uniform argument, `policy`, and the action taken from it instead of
-// protocol slot 1.  Compiled in a translation unit of their own; the forms above hold nothing of them.  No size-renewing form.
-// The logging forms (DCM_LOG defined; a launch of either entry point while dcm_set_rollout_log is set): k_lg_rollout_random and its
-// renewing form k_lgrn_rollout_random, the same text with two more arguments: `policy`, which here covers all three policies (wave-
-// uniform: DCM_POLICY_RANDOM takes protocol slot 1 as the plain form does), and the log, which apply_and_advance appends to and whose
-// lengths the env zeroes when it restarts an episode.  Compiled in a translation unit of their own; no size-renewing form.
-// The epsilon-greedy forms (DCM_EXPLORE defined; dcm_rollout_explore): k_ex_rollout_random and its renewing form k_exrn_rollout_random,
-// the logging form's text with one more argument, explore_q32: a decision whose explore word (mix64(key_1 ^ EXPLORE_SALT) >> 32) is
-// below it takes pick_random_action, every other one pick_policy_action of the base policy (FIRST / NEAREST).  The budget is the
-// greedy forms' (rollout_budget_policy); the log may be unset (lg.len null).  A translation unit of their own; no size-renewing form.
-#if (defined(DCM_LOG) || defined(DCM_EXPLORE)) && DCM_RENEW == 2
-#error "no size-renewing logging form"
-#endif
-#ifdef DCM_POLICY
-#if DCM_RENEW == 2
-#error "no size-renewing greedy form"
-#endif
-#define KPOLICY_PARAM , int policy
-#elif defined(DCM_EXPLORE)
-#define KPOLICY_PARAM , int policy, uint64_t explore_q32, RouteLog lg
-#elif defined(DCM_LOG)
-#define KPOLICY_PARAM , int policy, RouteLog lg
-#else
-#define KPOLICY_PARAM
-#endif
-#if defined(DCM_EXPLORE) && DCM_RENEW
-#define KNAME k_exrn_rollout_random
-#define KRENEW_PARAM , Renew rn
-#define KSIZES const int32_t* sizes
-#elif defined(DCM_EXPLORE)
-#define KNAME k_ex_rollout_random
-#define KRENEW_PARAM
-#define KSIZES const int32_t* sizes
-#elif defined(DCM_LOG) && DCM_RENEW
-#define KNAME k_lgrn_rollout_random
-#define KRENEW_PARAM , Renew rn
-#define KSIZES const int32_t* sizes
-#elif defined(DCM_LOG)
-#define KNAME k_lg_rollout_random
-#define KRENEW_PARAM
-#define KSIZES const int32_t* sizes
-#elif defined(DCM_POLICY) && DCM_RENEW
-#define KNAME k_hprn_rollout_random
-#define KRENEW_PARAM , Renew rn
-#define KSIZES const int32_t* sizes
-#elif defined(DCM_POLICY)
-#define KNAME k_hp_rollout_random
-#define KRENEW_PARAM
-#define KSIZES const int32_t* sizes
-#elif DCM_RENEW == 2
-#define KNAME k_rs_rollout_random
-#define KRENEW_PARAM , Renew rn
-#define KSIZES int32_t* sizes
-#elif DCM_RENEW
-#define KNAME k_rn_rollout_random
-#define KRENEW_PARAM , Renew rn
-#define KSIZES const int32_t* sizes
-#else
-#define KNAME k_rollout_random
-#define KRENEW_PARAM
-#define KSIZES const int32_t* sizes
-#endif
+// k_rollout_random.inc -- the kernel k_rollout_random and all its forms (k_form.inc), compiled once per form: the plain, renewing and
+// size-renewing ones by dcmrta_env.hip, the others by rollout_policy.hpp, rollout_log.hpp and rollout_explore.hpp.
+// Logging forms: apply_and_advance appends to the log, and the env zeroes its lengths when it restarts an episode.
+// Epsilon-greedy forms: a decision whose explore word (mix64(key_1 ^ EXPLORE_SALT) >> 32) is below explore_q32 takes
+// pick_random_action, every other one pick_policy_action of the base policy (FIRST / NEAREST).  The budget is the greedy forms'
+// (rollout_budget_policy).
+#define KBASE rollout_random
+#define KPOLICY_FORMS 1
+#include "k_form.inc"
 template <int CA, int CT, bool RS, int MC = M>
 __global__ __launch_bounds__(WAVE, 3) void KNAME(int A, int T, int PA, int PT, KP P, unsigned char* state, int episodes,
                                                         float* agents_out, float* tasks_out, uint8_t* mask_out,
@@ -183,7 +122,4 @@ __global__ __launch_bounds__(WAVE, 3) void KNAME(int A, int T, int PA, int PT, K
     WSYNC();
     S.store_record(rec, lane);
 }
-#undef KNAME
-#undef KRENEW_PARAM
-#undef KSIZES
-#undef KPOLICY_PARAM
+#include "k_form_end.inc"

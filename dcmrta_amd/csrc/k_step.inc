@@ -1,23 +1,6 @@
-// k_step.inc -- the kernel k_step, compiled twice by dcmrta_env.hip: as k_step (DCM_RENEW 0) and as its renewing form k_rn_step
-// (DCM_RENEW 1), which has one more argument, Renew rn, and is launched while dcm_set_instance_renewal has set a stride: an env that
-// restarts an episode first replaces its instance (wave_renew_instance, instgen.hpp).  Two kernels from one text: the plain
-// form holds nothing of the renewal and compiles to the code it had without it (DESIGN 6).
-// A third form, k_rs_step (DCM_RENEW 2, DCM_PARAM_RENEW_SIZES), for the instantiations that read per-env sizes: on a ragged generated
-// batch the restarting env draws its next SIZES with its next instance (wave_renew_instance_sized) and carries on as an env of those
-// sizes: everything the kernel derived from the old ones at its head is derived again at the restart.  `sizes` is writable there.
-#if DCM_RENEW == 2
-#define KNAME k_rs_step
-#define KRENEW_PARAM , Renew rn
-#define KSIZES int32_t* sizes
-#elif DCM_RENEW
-#define KNAME k_rn_step
-#define KRENEW_PARAM , Renew rn
-#define KSIZES const int32_t* sizes
-#else
-#define KNAME k_step
-#define KRENEW_PARAM
-#define KSIZES const int32_t* sizes
-#endif
+// k_step.inc -- the kernel k_step and its forms k_rn_step and k_rs_step (k_form.inc), compiled once per form by dcmrta_env.hip
+#define KBASE step
+#include "k_form.inc"
 template <int CA, int CT, bool RS, int MC = M>
 __global__ __launch_bounds__(WAVE) void KNAME(int A, int T, int PA, int PT, KP P, unsigned char* state, const int32_t* actions,
                                               const int32_t* leader_in, const int32_t* nfol_in, const int16_t* fol_in,
@@ -175,6 +158,4 @@ __global__ __launch_bounds__(WAVE) void KNAME(int A, int T, int PA, int PT, KP P
     }
     PHK_TOTAL(6);
 }
-#undef KNAME
-#undef KRENEW_PARAM
-#undef KSIZES
+#include "k_form_end.inc"

@@ -1,23 +1,7 @@
-// k_step_fast.inc -- the kernel k_step_fast, compiled twice by step_fast.hpp: as k_step_fast (DCM_RENEW 0) and as its renewing form k_rn_step_fast
-// (DCM_RENEW 1), which has one more argument, Renew rn, and is launched while dcm_set_instance_renewal has set a stride: an env that
-// restarts an episode first replaces its instance (wave_renew_instance, instgen.hpp).  Two kernels from one text: the plain
-// form holds nothing of the renewal and compiles to the code it had without it (DESIGN 6).
-// A third form, k_rs_step_fast (DCM_RENEW 2, DCM_PARAM_RENEW_SIZES), for the instantiations that read per-env sizes: on a ragged generated
-// batch the restarting env draws its next SIZES with its next instance (wave_renew_instance_sized) and carries on as an env of those
-// sizes: everything the kernel derived from the old ones at its head is derived again at the restart.  `sizes` is writable there.
-#if DCM_RENEW == 2
-#define KNAME k_rs_step_fast
-#define KRENEW_PARAM , Renew rn
-#define KSIZES int32_t* sizes
-#elif DCM_RENEW
-#define KNAME k_rn_step_fast
-#define KRENEW_PARAM , Renew rn
-#define KSIZES const int32_t* sizes
-#else
-#define KNAME k_step_fast
-#define KRENEW_PARAM
-#define KSIZES const int32_t* sizes
-#endif
+// k_step_fast.inc -- the kernel k_step_fast and its forms k_rn_step_fast and k_rs_step_fast (k_form.inc), compiled once per form by
+// step_fast.hpp
+#define KBASE step_fast
+#include "k_form.inc"
 template <int CA, int CT, bool RS>
 __global__ __launch_bounds__(WAVE, DCM_STEP_WAVES) void KNAME(int A, int T, int PA, int PT, KP P, unsigned char* state, const int32_t* actions,
                                                    float* agents_out, float* tasks_out, uint8_t* mask_out, int32_t* leader_out,
@@ -296,6 +280,4 @@ __global__ __launch_bounds__(WAVE, DCM_STEP_WAVES) void KNAME(int A, int T, int 
     }
     finish(regs);
 }
-#undef KNAME
-#undef KRENEW_PARAM
-#undef KSIZES
+#include "k_form_end.inc"

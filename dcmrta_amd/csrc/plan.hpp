@@ -84,34 +84,22 @@ inline Rollout rollout_kind(const Shape& s, bool obs_all_or_none) {
     if (s.A <= 2 * LANES && s.T <= 4 * LANES && !one_chunk_layout) return Rollout::FastG;  // the mid-size class: rollout_fast_g.hpp
     return Rollout::General;
 }
-// dcm_rollout_policy with a greedy policy (DCM_POLICY_FIRST / DCM_POLICY_NEAREST).  The greedy kernel forms exist for the one-chunk
-// register-resident kernel and for the general one only: where rollout_kind says FastMc or FastG (50A/200T, the mid sizes) a greedy
-// launch takes the general kernel.  DCM_POLICY_RANDOM is dcm_rollout_random and asks rollout_kind.
-inline Rollout policy_rollout_kind(const Shape& s, bool obs_all_or_none) {
+// The forms of the persistent kernels beside the plain and the renewing ones (k_form.inc): greedy (dcm_rollout_policy with
+// DCM_POLICY_FIRST / DCM_POLICY_NEAREST; DCM_POLICY_RANDOM is dcm_rollout_random and asks rollout_kind), logging (a launch of either
+// while dcm_set_rollout_log is set, under any of the three policies) and epsilon-greedy (dcm_rollout_explore).  They exist for the
+// one-chunk register-resident kernel and for the general one only: where rollout_kind says FastMc or FastG (50A/200T, the mid sizes)
+// such a launch takes the general kernel.
+inline Rollout form_rollout_kind(const Shape& s, bool obs_all_or_none) {
     return rollout_kind(s, obs_all_or_none) == Rollout::Fast ? Rollout::Fast : Rollout::General;
 }
-// ... and there is no size-renewing greedy form: a launch that would take the k_rs_* form is refused under a greedy policy
-inline bool policy_form_ok(RenewForm form) { return form != RenewForm::Sizes; }
+// ... and there is no size-renewing form of them: a launch that would take the k_rs_* form is refused under a greedy or an
+// epsilon-greedy policy and while the log is set
+inline bool form_ok(RenewForm form) { return form != RenewForm::Sizes; }
 // A greedy policy on a handle with max_waiting_time <= 0 does not end its episodes in general: a member that has waited 0 is dropped
 // at once (env/task_env.py:269), decides again at the same time and, the policy being a function of the state, takes the same task
-// again -- in the reference as here.  Such a launch must carry a decision budget (the scalar one, or per-env budgets).
+// again -- in the reference as here.  Such a launch must carry a decision budget (the scalar one, or per-env budgets); so must an
+// epsilon-greedy one, whose budget rule is the base policy's.
 inline bool policy_needs_budget(const Shape& s) { return !s.quiet; }
-// A persistent launch with the rollout log set (dcm_set_rollout_log), under any of the three policies.  The logging kernel forms
-// (k_lg_* / k_lgrn_*) exist, like the greedy ones, for the one-chunk register-resident kernel and for the general one only: where
-// rollout_kind says FastMc or FastG a logging launch takes the general kernel.
-inline Rollout log_rollout_kind(const Shape& s, bool obs_all_or_none) {
-    return rollout_kind(s, obs_all_or_none) == Rollout::Fast ? Rollout::Fast : Rollout::General;
-}
-// ... and there is no size-renewing logging form: a launch that would take the k_rs_* form is refused while the log is set
-inline bool log_form_ok(RenewForm form) { return form != RenewForm::Sizes; }
-// dcm_rollout_explore (epsilon-greedy over DCM_POLICY_FIRST / DCM_POLICY_NEAREST).  The forms (k_ex_* / k_exrn_*) exist, like the
-// greedy ones, for the one-chunk register-resident kernel and for the general one only: Fast exactly where policy_rollout_kind says
-// Fast, the general kernel everywhere else.  The budget rule is the base policy's (policy_needs_budget).
-inline Rollout explore_rollout_kind(const Shape& s, bool obs_all_or_none) {
-    return rollout_kind(s, obs_all_or_none) == Rollout::Fast ? Rollout::Fast : Rollout::General;
-}
-// ... and there is no size-renewing form: a launch that would take the k_rs_* form is refused
-inline bool explore_form_ok(RenewForm form) { return form != RenewForm::Sizes; }
 // k_rollout_fast_g<NAC, NTC>: lane chunks of agents (1..2) and of tasks (2..4) from the batch dims
 inline int fast_g_agent_chunks(int A) { return A > LANES ? 2 : 1; }
 inline int fast_g_task_chunks(int T) { return T > 3 * LANES ? 4 : (T > 2 * LANES ? 3 : 2); }

@@ -15,18 +15,11 @@
 // (return sampling on large batches; the log then has cap 0 and a null length array, which costs the decision loop one compare of
 // two registers and a skipped branch).  k_exrn_* renew a uniform generated batch's instances at episode restarts like k_rn_*; there is
 // no size-renewing form (the host refuses that launch), no wave-priority (PRIO) instantiation, and no form of k_rollout_fast_mc /
-// k_rollout_fast_g: their shapes take k_ex_rollout_random (plan::explore_rollout_kind).
+// k_rollout_fast_g: their shapes take k_ex_rollout_random (plan::form_rollout_kind).
 #pragma once
 
 constexpr uint64_t EXPLORE_SALT = 0xD6E8FEB86659FD93ULL;
 
 #define DCM_EXPLORE 1
-#define DCM_RENEW 0
-#include "k_rollout_random.inc"
-#include "k_rollout_fast.inc"
-#undef DCM_RENEW
-#define DCM_RENEW 1
-#include "k_rollout_random.inc"
-#include "k_rollout_fast.inc"
-#undef DCM_RENEW
+#include "k_rollout_forms.inc"
 #undef DCM_EXPLORE

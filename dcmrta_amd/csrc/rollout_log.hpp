@@ -9,16 +9,9 @@
 // with two more arguments: `policy`, wave-uniform and here covering DCM_POLICY_RANDOM as well, so that the random policy does not
 // double the kernel count, and the log.  k_lgrn_* renew a uniform generated batch's instances at episode restarts like k_rn_*; there
 // is no size-renewing form (the host refuses that launch), no wave-priority (PRIO) instantiation, and no logging form of
-// k_rollout_fast_mc / k_rollout_fast_g: their shapes take k_lg_rollout_random (plan::log_rollout_kind).
+// k_rollout_fast_mc / k_rollout_fast_g: their shapes take k_lg_rollout_random (plan::form_rollout_kind).
 #pragma once
 
 #define DCM_LOG 1
-#define DCM_RENEW 0
-#include "k_rollout_random.inc"
-#include "k_rollout_fast.inc"
-#undef DCM_RENEW
-#define DCM_RENEW 1
-#include "k_rollout_random.inc"
-#include "k_rollout_fast.inc"
-#undef DCM_RENEW
+#include "k_rollout_forms.inc"
 #undef DCM_LOG

@@ -9,16 +9,9 @@
 // distance chain and one wave minimum in front of the same ballot, and half as many kernels are compiled.  k_hprn_* renew a uniform
 // generated batch's instances at episode restarts like k_rn_*; there is no size-renewing form (the host refuses that launch), no
 // wave-priority (PRIO) instantiation -- its estimate of the work left is calibrated on the random policy's episodes -- and no greedy
-// form of k_rollout_fast_mc / k_rollout_fast_g: their shapes take k_hp_rollout_random (plan::policy_rollout_kind).
+// form of k_rollout_fast_mc / k_rollout_fast_g: their shapes take k_hp_rollout_random (plan::form_rollout_kind).
 #pragma once
 
 #define DCM_POLICY 1
-#define DCM_RENEW 0
-#include "k_rollout_random.inc"
-#include "k_rollout_fast.inc"
-#undef DCM_RENEW
-#define DCM_RENEW 1
-#include "k_rollout_random.inc"
-#include "k_rollout_fast.inc"
-#undef DCM_RENEW
+#include "k_rollout_forms.inc"
 #undef DCM_POLICY

@@ -86,9 +86,9 @@ def test_plan_sends_explore_launches_where_it_sends_greedy_ones(tmp_path):
 using namespace dcm::plan;
 static Shape shape(int A, int T, int ragged, int wide, int quiet) { return Shape{A, T, ragged != 0, wide != 0, quiet != 0}; }
 extern "C" {
-int p_explore(int A, int T, int ragged, int wide, int quiet, int obs) { return (int)explore_rollout_kind(shape(A, T, ragged, wide, quiet), obs != 0); }
-int p_policy(int A, int T, int ragged, int wide, int quiet, int obs) { return (int)policy_rollout_kind(shape(A, T, ragged, wide, quiet), obs != 0); }
-int p_form_ok(int form) { return explore_form_ok((RenewForm)form) ? 1 : 0; }
+int p_explore(int A, int T, int ragged, int wide, int quiet, int obs) { return (int)form_rollout_kind(shape(A, T, ragged, wide, quiet), obs != 0); }
+int p_policy(int A, int T, int ragged, int wide, int quiet, int obs) { return (int)form_rollout_kind(shape(A, T, ragged, wide, quiet), obs != 0); }
+int p_form_ok(int form) { return form_ok((RenewForm)form) ? 1 : 0; }
 }
 """)
     so = tmp_path / "plan_shim.so"

@@ -35,9 +35,9 @@ def test_plan_sends_greedy_launches_to_the_fast_or_the_general_form(tmp_path):
 using namespace dcm::plan;
 static Shape shape(int A, int T, int ragged, int wide, int quiet) { return Shape{A, T, ragged != 0, wide != 0, quiet != 0}; }
 extern "C" {
-int p_policy(int A, int T, int ragged, int wide, int quiet, int obs) { return (int)policy_rollout_kind(shape(A, T, ragged, wide, quiet), obs != 0); }
+int p_policy(int A, int T, int ragged, int wide, int quiet, int obs) { return (int)form_rollout_kind(shape(A, T, ragged, wide, quiet), obs != 0); }
 int p_rollout(int A, int T, int ragged, int wide, int quiet, int obs) { return (int)rollout_kind(shape(A, T, ragged, wide, quiet), obs != 0); }
-int p_form_ok(int form) { return policy_form_ok((RenewForm)form) ? 1 : 0; }
+int p_form_ok(int form) { return form_ok((RenewForm)form) ? 1 : 0; }
 int p_needs_budget(int A, int T, int ragged, int wide, int quiet) { return policy_needs_budget(shape(A, T, ragged, wide, quiet)) ? 1 : 0; }
 }
 """)

@@ -34,9 +34,9 @@ def test_plan_sends_logging_launches_to_the_fast_or_the_general_form(tmp_path):
 using namespace dcm::plan;
 static Shape shape(int A, int T, int ragged, int wide, int quiet) { return Shape{A, T, ragged != 0, wide != 0, quiet != 0}; }
 extern "C" {
-int p_log(int A, int T, int ragged, int wide, int quiet, int obs) { return (int)log_rollout_kind(shape(A, T, ragged, wide, quiet), obs != 0); }
+int p_log(int A, int T, int ragged, int wide, int quiet, int obs) { return (int)form_rollout_kind(shape(A, T, ragged, wide, quiet), obs != 0); }
 int p_rollout(int A, int T, int ragged, int wide, int quiet, int obs) { return (int)rollout_kind(shape(A, T, ragged, wide, quiet), obs != 0); }
-int p_form_ok(int form) { return log_form_ok((RenewForm)form) ? 1 : 0; }
+int p_form_ok(int form) { return form_ok((RenewForm)form) ? 1 : 0; }
 }
 """)
     so = tmp_path / "plan_shim.so"
