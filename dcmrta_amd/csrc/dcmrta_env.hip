@@ -23,6 +23,7 @@
 #include <cstdlib>
 #include <mutex>
 #include <tuple>
+#include <type_traits>
 
 #include "common.hpp"
 #include "np_stream.hpp"
@@ -75,8 +76,13 @@ struct RolloutArgs {
     int episodes;
     float* agents_out; float* tasks_out; uint8_t* mask_out;
     int64_t* steps_out; double* summary; uint16_t* ablog;
-    const int32_t* sizes; int64_t budget_all; const int64_t* budget_in;
+    int32_t* sizes;      // the handle's size table: a size-renewing form (k_rs_*) writes it, every other form takes it const
+    int64_t budget_all; const int64_t* budget_in;
     unsigned char* gscr; double* retlog; int retcap;
+    auto kernel_args() const {
+        return std::make_tuple(A, T, PA, PT, kp, state, episodes, agents_out, tasks_out, mask_out, steps_out, summary, ablog, sizes, budget_all,
+                               budget_in, gscr, retlog, retcap);
+    }
     Renew rn;            // last argument of the renewing forms (k_rn_*, k_rs_*)
     plan::RenewForm form;  // which form the launch takes (plan::renew_form)
     int policy = DCM_POLICY_RANDOM;   // last argument of the greedy-policy forms (k_hp_*, k_hprn_*)
@@ -1736,30 +1742,46 @@ __global__ void k_distance(const double* ax, const double* ay, const double* bx,
 
 // ---------------------------------------------------------------------------------- host side
 // Which Sim<> instantiation and which kernels serve a handle is decided in plan.hpp; here its answers become template arguments.
-// The instantiations by their plan::SimKind: first the one-chunk layouts, which also have the register-resident kernels of
-// rollout_fast.hpp / step_fast.hpp, then the rest
-#define FOR_EACH_FAST(X) X(S20x50, 20, 50, false) X(S20x50_RS, 20, 50, true) X(S64x64_RS, 64, 64, true)
-#define FOR_EACH_INSTANCE(X) FOR_EACH_FAST(X) X(S50x200, 50, 200, false) X(S100x500, 100, 500, false) X(S128x256_RS, 128, 256, true) \
-    X(Runtime, 0, 0, false) X(RuntimeWide, 0, 0, false, MW)
-// DISPATCH_ENV(env): the caller's macro CALL(CA, CT, RS[, MC]) for the handle's instantiation; DISPATCH_ONE_CHUNK(env): the same for
-// the kernels that exist for the one-chunk layouts only (their callers have asked plan::one_chunk_ok)
-#define SIM_CASE(KIND, ...) case plan::SimKind::KIND: CALL(__VA_ARGS__); break;
-#define DISPATCH_ENV(env) switch (plan::sim_kind(shape_of(env))) { FOR_EACH_INSTANCE(SIM_CASE) }
-#define DISPATCH_ONE_CHUNK(env) \
-    switch (plan::sim_kind(shape_of(env))) { FOR_EACH_FAST(SIM_CASE) default: return fail(DCM_ERR_STATE, "internal error: a one-chunk kernel on another layout"); }
-// The instantiations that read per-env sizes, i.e. what plan::sim_kind gives a ragged batch: the only ones the size-renewing kernel
-// forms (k_rs_*) exist for.  DISPATCH_RAGGED / DISPATCH_ONE_CHUNK_RAGGED: the same two switches over them.
-#define FOR_EACH_FAST_RAGGED(X) X(S20x50_RS, 20, 50, true) X(S64x64_RS, 64, 64, true)
-#define FOR_EACH_RAGGED(X) FOR_EACH_FAST_RAGGED(X) X(S128x256_RS, 128, 256, true) X(Runtime, 0, 0, false) X(RuntimeWide, 0, 0, false, MW)
-#define DISPATCH_RAGGED(env) \
-    switch (plan::sim_kind(shape_of(env))) { FOR_EACH_RAGGED(SIM_CASE) default: return fail(DCM_ERR_STATE, "internal error: a size-renewing kernel on an exact shape"); }
-#define DISPATCH_ONE_CHUNK_RAGGED(env) \
-    switch (plan::sim_kind(shape_of(env))) { FOR_EACH_FAST_RAGGED(SIM_CASE) default: return fail(DCM_ERR_STATE, "internal error: a size-renewing one-chunk kernel on another layout"); }
+// The instantiations by their plan::SimKind: the single list
+#define FOR_EACH_INSTANCE(X) X(S20x50, 20, 50, false) X(S20x50_RS, 20, 50, true) X(S64x64_RS, 64, 64, true) X(S50x200, 50, 200, false) \
+    X(S100x500, 100, 500, false) X(S128x256_RS, 128, 256, true) X(Runtime, 0, 0, false) X(RuntimeWide, 0, 0, false, MW)
+// One of them as a type, with the two facts that decide which kernels exist for it
+template <int CA_, int CT_, bool RS_, int MC_ = M>
+struct SimTag {
+    static constexpr int CA = CA_, CT = CT_, MC = MC_;
+    static constexpr bool RS = RS_;
+    // a one-chunk layout: the only ones that have the register-resident kernels of rollout_fast.hpp / step_fast.hpp
+    static constexpr bool one_chunk = CA != 0 && CA <= WAVE && CT <= WAVE;
+    // reads per-env sizes, i.e. what plan::sim_kind gives a ragged batch: the only ones the size-renewing forms (k_rs_*) exist for
+    static constexpr bool reads_sizes = RS || CA == 0;
+};
+#define SIM_ARGS(S) S::CA, S::CT, S::RS
+// The one dispatch: f(SimTag<...>{}) for the instantiation of `kind`; f returns 0, or -1 where it has no kernel for that one (a site
+// that serves a subset says so with `if constexpr` on the tag: a kernel that is named is compiled).  for_each_sim: f for every one.
+template <class F>
+int with_sim(plan::SimKind kind, F&& f) {
+    switch (kind) {
+#define SIM_CASE(KIND, ...) case plan::SimKind::KIND: return f(SimTag<__VA_ARGS__>{});
+    FOR_EACH_INSTANCE(SIM_CASE)
+#undef SIM_CASE
+    }
+    return -1;
+}
+template <class F>
+void for_each_sim(F&& f) {
+#define SIM_EACH(KIND, ...) f(SimTag<__VA_ARGS__>{});
+    FOR_EACH_INSTANCE(SIM_EACH)
+#undef SIM_EACH
+}
+// ... and a runtime flag as a type (std::true_type first)
+template <class F>
+auto with_bool(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_type{}); }
 // kernel arguments every env kernel starts with: batch dims, layout dims
 #define DIMS(env) (env)->A, (env)->T, (env)->L.A, (env)->L.T
 
 // what plan.hpp reads of a handle
 plan::Shape shape_of(const dcm_env* env) { return {env->A, env->T, env->sizes != nullptr, env->L.C > M, env->kp.mwt > 0.0}; }
+plan::SimKind sim_of(const dcm_env* env) { return plan::sim_kind(shape_of(env)); }
 
 // dcm_create / dcm_destroy run on the handle's device but leave the caller's current device as they found it
 struct DeviceGuard {
@@ -1768,53 +1790,75 @@ struct DeviceGuard {
     ~DeviceGuard() { if (prev >= 0) (void)hipSetDevice(prev); }
 };
 
-// Launch any form of a persistent rollout kernel: the 19 arguments they all start with (RolloutArgs), then the form's own -- `tail`:
-// a.rn in a renewing form, then what DCM_FORM_LAUNCHERS says.  A size-renewing form (k_rs_*) declares `sizes` writable: it writes the
-// drawn sizes to the handle's size table.
-template <class... P, class... Tail>
-void launch(void (*kernel)(P...), unsigned grid, unsigned lds_bytes, hipStream_t stream, const RolloutArgs& a, const Tail&... tail) {
-    using Sizes = std::tuple_element_t<13, std::tuple<P...>>;   // int32_t* in k_rs_*, const int32_t* everywhere else
-    hipLaunchKernelGGL(kernel, dim3(grid), dim3(WAVE), lds_bytes, stream, a.A, a.T, a.PA, a.PT, a.kp, a.state, a.episodes, a.agents_out,
-                       a.tasks_out, a.mask_out, a.steps_out, a.summary, a.ablog, const_cast<Sizes>(a.sizes), a.budget_all, a.budget_in,
-                       a.gscr, a.retlog, a.retcap, tail...);
+// Launch a kernel, one workgroup of one wave per env: `args` (a tuple: RolloutArgs::kernel_args, or what dcm_step packs), then `tail`.
+// Each argument converts to the parameter it is passed to, so the handle's size table arrives const everywhere but in a k_rs_* form.
+template <class K, class... Args, class... Tail>
+void launch(K kernel, unsigned grid, unsigned lds_bytes, hipStream_t stream, const std::tuple<Args...>& args, const Tail&... tail) {
+    std::apply([&](const Args&... a) { hipLaunchKernelGGL(kernel, dim3(grid), dim3(WAVE), lds_bytes, stream, a..., tail...); }, args);
 }
-template <class K>
-void allow_lds(K kernel, int bytes) { (void)hipFuncSetAttribute((const void*)kernel, hipFuncAttributeMaxDynamicSharedMemorySize, bytes); }
+template <class... K>
+void allow_lds(int bytes, K... kernels) { ((void)hipFuncSetAttribute((const void*)kernels, hipFuncAttributeMaxDynamicSharedMemorySize, bytes), ...); }
 
-// dcm::launch_rollout_<form> and dcm::allow_lds_<form> for a form F (DCM_FORM_LAUNCHERS): F names the form's four kernels and launches
-// the renewing or the plain one of a pair with the form's arguments.  (The renewing one is named first throughout: the kernels are
-// instantiated in the order they are named here, and a unit's assembly lists them in that order.)
+// A kernel family: the forms of one kernel text (k_form.inc) under one name each; <V...> are the kernel's template arguments, the
+// same in every form.  DCM_FAMILY(base) is the family of a text compiled with DCM_RENEW 0 / 1 / 2.  (Return types written out:
+// the kernel is then instantiated when the function that names the accessor is, in the order of the names, like one named directly.)
+#define DCM_FORM(NAME, KERNEL) template <auto... V> static decltype(&KERNEL<V...>) NAME() { return KERNEL<V...>; }
+#define DCM_FORMS(PLAIN, RENEWING) DCM_FORM(plain, PLAIN) DCM_FORM(renewing, RENEWING)
+#define DCM_FAMILY(base) struct base##_family { DCM_FORMS(k_##base, k_rn_##base) DCM_FORM(size_renewing, k_rs_##base) };
+DCM_FAMILY(step)
+DCM_FAMILY(step_fast)
+DCM_FAMILY(rollout_random)
+DCM_FAMILY(rollout_fast)
+struct rollout_fast_mc_family { DCM_FORMS(k_rollout_fast_mc, k_rn_rollout_fast_mc) };   // (exact shape, never ragged: no size-renewing form)
+#ifdef DCM_HAVE_FAST_G
+DCM_FAMILY(rollout_fast_g)
+#endif
+#undef DCM_FAMILY
+
+// Launch the member <V...> of a family in the form plan::renew_form chose, the one place that knows the rule: k_rs_* for Sizes, k_rn_*
+// for Instance, k_* otherwise, `rn` behind the common arguments of the renewing two, then the `tail` of a greedy, logging or epsilon-
+// greedy family.  HAS_RS: the member has a size-renewing form (SimTag::reads_sizes; all of k_rollout_fast_g); -1 for Sizes without.
+// (Kernels are instantiated in the order they are named and a unit's assembly lists them in that order: keep rs, rn, plain.)
+template <class Fam, bool HAS_RS, auto... V, class Args, class... Tail>
+int launch_family(plan::RenewForm form, unsigned grid, unsigned lds_bytes, hipStream_t stream, const Args& args, const Renew& rn,
+                  const Tail&... tail) {
+    if (form == plan::RenewForm::Sizes) {
+        if constexpr (HAS_RS) launch(Fam::template size_renewing<V...>(), grid, lds_bytes, stream, args, rn, tail...);
+        else return -1;
+    } else if (form == plan::RenewForm::Instance) launch(Fam::template renewing<V...>(), grid, lds_bytes, stream, args, rn, tail...);
+    else launch(Fam::template plain<V...>(), grid, lds_bytes, stream, args, tail...);
+    return 0;
+}
+
+// dcm::launch_rollout_<form> and dcm::allow_lds_<form> for a form F (DCM_FORM_LAUNCHERS), which names its two families and its tail
 template <class F>
 int launch_rollout_form(plan::SimKind kind, bool fast, bool obs, unsigned grid, Lay L, hipStream_t stream, const RolloutArgs& a) {
-    if (fast) {
-#define CALLF(CA, CT, RS, OBS) \
-    F::go(F::template fast_rn<CA, CT, RS, OBS>(), F::template fast<CA, CT, RS, OBS>(), grid, rollout_fast_lds_bytes<CA, CT, RS>(L), stream, a)
-#define CALL(CA, CT, RS) do { if (obs) { CALLF(CA, CT, RS, true); } else { CALLF(CA, CT, RS, false); } } while (0)
-        switch (kind) { FOR_EACH_FAST(SIM_CASE) default: return -1; }
-#undef CALL
-#undef CALLF
-        return 0;
-    }
-#define CALL(CA, CT, RS, ...) \
-    F::go(F::template general_rn<CA, CT, RS, ##__VA_ARGS__>(), F::template general<CA, CT, RS, ##__VA_ARGS__>(), grid, rollout_random_lds_bytes<CA, CT, RS>(L), stream, a)
-    switch (kind) { FOR_EACH_INSTANCE(SIM_CASE) }
-#undef CALL
-    return 0;
+    if (fast)
+        return with_sim(kind, [&](auto s) {
+            using S = decltype(s);
+            if constexpr (S::one_chunk)
+                return with_bool(obs, [&](auto obs_c) {
+                    return F::template go<typename F::fast, SIM_ARGS(S), decltype(obs_c)::value>(grid, rollout_fast_lds_bytes<SIM_ARGS(S)>(L), stream, a);
+                });
+            else return -1;
+        });
+    return with_sim(kind, [&](auto s) {
+        using S = decltype(s);
+        return F::template go<typename F::general, SIM_ARGS(S), S::MC>(grid, rollout_random_lds_bytes<SIM_ARGS(S)>(L), stream, a);
+    });
 }
 template <class F>
 void allow_lds_form(int lds) {
-#define SET_ATTR(KIND, CA, CT, RS, ...)                                   \
-    allow_lds(F::template general<CA, CT, RS, ##__VA_ARGS__>(), lds);     \
-    allow_lds(F::template general_rn<CA, CT, RS, ##__VA_ARGS__>(), lds);
-    FOR_EACH_INSTANCE(SET_ATTR)
-#undef SET_ATTR
-#define SET_FAST(KIND, CA, CT, RS)                                        \
-    allow_lds(F::template fast<CA, CT, RS, true>(), lds);                 \
-    allow_lds(F::template fast<CA, CT, RS, false>(), lds);                \
-    allow_lds(F::template fast_rn<CA, CT, RS, true>(), lds);              \
-    allow_lds(F::template fast_rn<CA, CT, RS, false>(), lds);
-    FOR_EACH_FAST(SET_FAST)
-#undef SET_FAST
+    for_each_sim([&](auto s) {
+        using S = decltype(s);
+        allow_lds(lds, F::general::template plain<SIM_ARGS(S), S::MC>(), F::general::template renewing<SIM_ARGS(S), S::MC>());
+    });
+    for_each_sim([&](auto s) {
+        using S = decltype(s);
+        if constexpr (S::one_chunk)
+            allow_lds(lds, F::fast::template plain<SIM_ARGS(S), true>(), F::fast::template plain<SIM_ARGS(S), false>(),
+                      F::fast::template renewing<SIM_ARGS(S), true>(), F::fast::template renewing<SIM_ARGS(S), false>());
+    });
 }
 }  // namespace
 
@@ -1823,14 +1867,11 @@ void allow_lds_form(int lds) {
 #define DCM_FORM_LAUNCHERS(FORM, plain, renewing, ...)                                                                              \
     namespace {                                                                                                                      \
     struct FORM##_form {                                                                                                             \
-        template <int CA, int CT, bool RS, bool OBS> static auto fast() { return plain##rollout_fast<CA, CT, RS, OBS>; }             \
-        template <int CA, int CT, bool RS, bool OBS> static auto fast_rn() { return renewing##rollout_fast<CA, CT, RS, OBS>; }       \
-        template <int CA, int CT, bool RS, int MC = M> static auto general() { return plain##rollout_random<CA, CT, RS, MC>; }       \
-        template <int CA, int CT, bool RS, int MC = M> static auto general_rn() { return renewing##rollout_random<CA, CT, RS, MC>; } \
-        template <class KRN, class K>                                                                                                \
-        static void go(KRN k_rn, K k, unsigned grid, unsigned lds_bytes, hipStream_t stream, const RolloutArgs& a) {                 \
-            if (a.form == plan::RenewForm::Instance) launch(k_rn, grid, lds_bytes, stream, a, a.rn, __VA_ARGS__);                    \
-            else launch(k, grid, lds_bytes, stream, a, __VA_ARGS__);                                                                 \
+        struct fast { DCM_FORMS(plain##rollout_fast, renewing##rollout_fast) };                                                      \
+        struct general { DCM_FORMS(plain##rollout_random, renewing##rollout_random) };                                               \
+        template <class Fam, auto... V>                                                                                              \
+        static int go(unsigned grid, unsigned lds_bytes, hipStream_t stream, const RolloutArgs& a) {                                 \
+            return launch_family<Fam, false, V...>(a.form, grid, lds_bytes, stream, a.kernel_args(), a.rn, __VA_ARGS__);             \
         }                                                                                                                            \
     };                                                                                                                               \
     }                                                                                                                                \
@@ -1849,27 +1890,34 @@ DCM_FORM_LAUNCHERS(log, k_lg_, k_lgrn_, a.policy, a.lg)
 DCM_FORM_LAUNCHERS(explore, k_ex_, k_exrn_, a.policy, a.explore_q32, a.lg)
 #endif
 #undef DCM_FORM_LAUNCHERS
+#undef DCM_FORMS
+#undef DCM_FORM
 
 #ifdef DCM_HAVE_FAST_G
 void dcm::launch_rollout_fast_g(int nac, int ntc, bool obs, unsigned grid, Lay L, hipStream_t stream, const RolloutArgs& a) {
-#define CALLG(NAC, NTC, OBS)                                                                                                          \
-    do {                                                                                                                              \
-        if (a.form == plan::RenewForm::Sizes) launch(k_rs_rollout_fast_g<NAC, NTC, OBS>, grid, rollout_fast_g_lds_bytes(L), stream, a, a.rn); \
-        else if (a.form == plan::RenewForm::Instance) launch(k_rn_rollout_fast_g<NAC, NTC, OBS>, grid, rollout_fast_g_lds_bytes(L), stream, a, a.rn); \
-        else launch(k_rollout_fast_g<NAC, NTC, OBS>, grid, rollout_fast_g_lds_bytes(L), stream, a);                                  \
-    } while (0)
-#define CALLT(NAC, OBS) do { if (ntc > 3) { CALLG(NAC, 4, OBS); } else if (ntc > 2) { CALLG(NAC, 3, OBS); } else { CALLG(NAC, 2, OBS); } } while (0)
-#define CALLA(OBS) do { if (nac > 1) { CALLT(2, OBS); } else { CALLT(1, OBS); } } while (0)
-    if (obs) { CALLA(true); } else { CALLA(false); }
-#undef CALLA
-#undef CALLT
-#undef CALLG
+    with_bool(obs, [&](auto obs_c) {
+        with_bool(nac > 1, [&](auto two_c) {
+            auto go = [&](auto ntc_c) {
+                launch_family<rollout_fast_g_family, true, decltype(two_c)::value ? 2 : 1, decltype(ntc_c)::value, decltype(obs_c)::value>(
+                    a.form, grid, rollout_fast_g_lds_bytes(L), stream, a.kernel_args(), a.rn);
+            };
+            if (ntc > 3) go(std::integral_constant<int, 4>{});
+            else if (ntc > 2) go(std::integral_constant<int, 3>{});
+            else go(std::integral_constant<int, 2>{});
+        });
+    });
 }
 #endif
 
 #ifndef DCM_DEVICE_ONLY_TU   // (tools/loop_insts.py compiles single kernel instantiations of this file without the host API)
 namespace {
 constexpr uint32_t CU_LDS_BYTES = 160u * 1024u;
+// the end of a launch: rc = -1 from with_sim / launch_family says that plan.hpp sent it to a kernel that does not exist
+int launched(int rc) {
+    if (rc != 0) return fail(DCM_ERR_STATE, "internal error: no such kernel for the handle's layout and renewal form");
+    LAUNCH_OK();
+    return DCM_OK;
+}
 
 // The most dynamic LDS any kernel of this file asks for on a layout: the general image with the wake-up times of the multi-chunk
 // layouts, or record + scratch where the persistent kernels keep the scratch in LDS (Sim::SCR_IN_LDS); then the dummy slots
@@ -1941,7 +1989,7 @@ std::array<Section, 4> state_sections(const dcm_env* env) {
 dcm::RolloutArgs rollout_args(const dcm_env* env, plan::RenewForm form, int32_t episodes, int64_t max_decisions, const int64_t* max_decisions_in,
                               float* agents_out, float* tasks_out, uint8_t* mask_out, int64_t* steps_out) {
     return {DIMS(env), env->kp, env->state, (int)episodes, agents_out, tasks_out, mask_out, steps_out, env->summary,
-            env->ablog, (const int32_t*)env->sizes, max_decisions, max_decisions_in, env->gscratch, env->retlog,
+            env->ablog, env->sizes, max_decisions, max_decisions_in, env->gscratch, env->retlog,
             (int)env->retcap, renew_args(env), form};
 }
 
@@ -1973,10 +2021,7 @@ int rollout_form(dcm_env* env, const char* fn, const RolloutForm& form, int32_t 
     const bool all_obs = agents_out && tasks_out && mask_out, no_obs = !agents_out && !tasks_out && !mask_out;
     const plan::Shape shape = shape_of(env);
     const bool fast = plan::form_rollout_kind(shape, all_obs || no_obs) == plan::Rollout::Fast;
-    if (form.launch(plan::sim_kind(shape), fast, all_obs, (unsigned)env->p.n_envs, env->L, (hipStream_t)stream, ra) != 0)
-        return fail(DCM_ERR_STATE, "internal error: a one-chunk kernel on another layout");
-    LAUNCH_OK();
-    return DCM_OK;
+    return launched(form.launch(plan::sim_kind(shape), fast, all_obs, (unsigned)env->p.n_envs, env->L, (hipStream_t)stream, ra));
 }
 
 // plan::policy_needs_budget: `fn` refuses an unlimited greedy launch there
@@ -2050,52 +2095,41 @@ int dcm_create(const dcm_params* params, dcm_env** out) {
     //  stream capture -- actors create handles for new batch shapes while others capture)
     if (lds <= lds_limit[dev_slot]) return DCM_OK;
     lds_limit[dev_slot] = lds;
-#define SET_ATTR(KIND, CA, CT, RS, ...)                        \
-    allow_lds(k_reset<CA, CT, RS, ##__VA_ARGS__>, lds);        \
-    allow_lds(k_observe<CA, CT, RS, ##__VA_ARGS__>, lds);      \
-    allow_lds(k_step<CA, CT, RS, ##__VA_ARGS__>, lds);         \
-    allow_lds(k_rollout_random<CA, CT, RS, ##__VA_ARGS__>, lds);  \
-    allow_lds(k_rn_step<CA, CT, RS, ##__VA_ARGS__>, lds);      \
-    allow_lds(k_rn_rollout_random<CA, CT, RS, ##__VA_ARGS__>, lds);
-    FOR_EACH_INSTANCE(SET_ATTR)
-#undef SET_ATTR
-#define SET_ATTR(KIND, CA, CT, RS, ...)                        \
-    allow_lds(k_rs_step<CA, CT, RS, ##__VA_ARGS__>, lds);      \
-    allow_lds(k_rs_rollout_random<CA, CT, RS, ##__VA_ARGS__>, lds);
-    FOR_EACH_RAGGED(SET_ATTR)
-#undef SET_ATTR
-#define SET_FAST(KIND, CA, CT, RS)                             \
-    allow_lds(k_rollout_fast<CA, CT, RS, true>, lds);          \
-    allow_lds(k_rollout_fast<CA, CT, RS, false>, lds);         \
-    allow_lds(k_rollout_fast<CA, CT, RS, true, true>, lds);    \
-    allow_lds(k_rollout_fast<CA, CT, RS, false, true>, lds);   \
-    allow_lds(k_step_fast<CA, CT, RS>, lds);                   \
-    allow_lds(k_rn_rollout_fast<CA, CT, RS, true>, lds);       \
-    allow_lds(k_rn_rollout_fast<CA, CT, RS, false>, lds);      \
-    allow_lds(k_rn_rollout_fast<CA, CT, RS, true, true>, lds); \
-    allow_lds(k_rn_rollout_fast<CA, CT, RS, false, true>, lds); \
-    allow_lds(k_rn_step_fast<CA, CT, RS>, lds);
-    FOR_EACH_FAST(SET_FAST)
-#undef SET_FAST
-#define SET_FAST(KIND, CA, CT, RS)                             \
-    allow_lds(k_rs_rollout_fast<CA, CT, RS, true>, lds);       \
-    allow_lds(k_rs_rollout_fast<CA, CT, RS, false>, lds);      \
-    allow_lds(k_rs_rollout_fast<CA, CT, RS, true, true>, lds); \
-    allow_lds(k_rs_rollout_fast<CA, CT, RS, false, true>, lds); \
-    allow_lds(k_rs_step_fast<CA, CT, RS>, lds);
-    FOR_EACH_FAST_RAGGED(SET_FAST)
-#undef SET_FAST
-    allow_lds(k_rollout_fast_mc<50, 200, true>, lds);
-    allow_lds(k_rollout_fast_mc<50, 200, false>, lds);
-    allow_lds(k_rn_rollout_fast_mc<50, 200, true>, lds);
-    allow_lds(k_rn_rollout_fast_mc<50, 200, false>, lds);
+    // every kernel that takes the record into LDS, from the tables the launches use (in the order the main unit's assembly has them)
+    for_each_sim([&](auto s) {
+        using S = decltype(s);
+        allow_lds(lds, k_reset<SIM_ARGS(S), S::MC>, k_observe<SIM_ARGS(S), S::MC>);
+        allow_lds(lds, step_family::plain<SIM_ARGS(S), S::MC>(), rollout_random_family::plain<SIM_ARGS(S), S::MC>(),
+                  step_family::renewing<SIM_ARGS(S), S::MC>(), rollout_random_family::renewing<SIM_ARGS(S), S::MC>());
+    });
+    for_each_sim([&](auto s) {
+        using S = decltype(s);
+        if constexpr (S::reads_sizes)
+            allow_lds(lds, step_family::size_renewing<SIM_ARGS(S), S::MC>(), rollout_random_family::size_renewing<SIM_ARGS(S), S::MC>());
+    });
+    using fast = rollout_fast_family;                    // <..., OBS, PRIO>: both OBS, without and with wave priorities
+    for_each_sim([&](auto s) {
+        using S = decltype(s);
+        if constexpr (S::one_chunk) {
+            allow_lds(lds, fast::plain<SIM_ARGS(S), true>(), fast::plain<SIM_ARGS(S), false>(), fast::plain<SIM_ARGS(S), true, true>(),
+                      fast::plain<SIM_ARGS(S), false, true>(), step_fast_family::plain<SIM_ARGS(S)>());
+            allow_lds(lds, fast::renewing<SIM_ARGS(S), true>(), fast::renewing<SIM_ARGS(S), false>(), fast::renewing<SIM_ARGS(S), true, true>(),
+                      fast::renewing<SIM_ARGS(S), false, true>(), step_fast_family::renewing<SIM_ARGS(S)>());
+        }
+    });
+    for_each_sim([&](auto s) {
+        using S = decltype(s);
+        if constexpr (S::one_chunk && S::reads_sizes)
+            allow_lds(lds, fast::size_renewing<SIM_ARGS(S), true>(), fast::size_renewing<SIM_ARGS(S), false>(),
+                      fast::size_renewing<SIM_ARGS(S), true, true>(), fast::size_renewing<SIM_ARGS(S), false, true>(),
+                      step_fast_family::size_renewing<SIM_ARGS(S)>());
+    });
+    using mc = rollout_fast_mc_family;
+    allow_lds(lds, mc::plain<50, 200, true>(), mc::plain<50, 200, false>(), mc::renewing<50, 200, true>(), mc::renewing<50, 200, false>());
     dcm::allow_lds_policy(lds);
     dcm::allow_lds_log(lds);
     dcm::allow_lds_explore(lds);
-    allow_lds(k_get_tasks<M>, lds);
-    allow_lds(k_get_agents<M>, lds);
-    allow_lds(k_get_tasks<MW>, lds);
-    allow_lds(k_get_agents<MW>, lds);
+    allow_lds(lds, k_get_tasks<M>, k_get_agents<M>, k_get_tasks<MW>, k_get_agents<MW>);
     return DCM_OK;
 }
 
@@ -2217,13 +2251,15 @@ int dcm_generator_draws(const uint64_t* seeds, int64_t n, int32_t n_doubles, uin
 namespace dcm {
 int flush_pending(dcm_env* env, void* stream) {
     if (!env->maybe_pending) return DCM_OK;
-#define CALL(CA, CT, RS)                                                                                             \
-    hipLaunchKernelGGL((k_terminal_flush<CA, CT, RS>), GRID(env), (step_fast_lds_bytes<CA, CT, RS>(env->L)),          \
-                       (hipStream_t)stream, DIMS(env), env->kp, (const unsigned char*)env->side, env->side_pitch, env->pendq,       \
-                       env->summary, (const int32_t*)env->sizes, env->gscratch)
-    DISPATCH_ONE_CHUNK(env);
-#undef CALL
-    LAUNCH_OK();
+    const auto args = std::make_tuple(DIMS(env), env->kp, env->side, env->side_pitch, env->pendq, env->summary, env->sizes, env->gscratch);
+    const int rc = with_sim(sim_of(env), [&](auto s) {
+        using S = decltype(s);
+        if constexpr (S::one_chunk) {
+            launch(k_terminal_flush<SIM_ARGS(S)>, (unsigned)env->p.n_envs, step_fast_lds_bytes<SIM_ARGS(S)>(env->L), (hipStream_t)stream, args);
+            return 0;
+        } else return -1;
+    });
+    DCM_TRY(launched(rc));
     env->maybe_pending = false;
     env->steps_since_flush = 0;
     return DCM_OK;
@@ -2244,12 +2280,12 @@ int dcm_reset(dcm_env* env, const uint64_t* seeds, void* stream) {
     DCM_TRY(dcm::drop_pending(env, stream));
     if (!env->loaded) return fail(DCM_ERR_STATE, "dcm_reset: call dcm_load_instances first");
     if (!seeds) return fail(DCM_ERR_INVALID, "dcm_reset: null seeds");
-#define CALL(CA, CT, RS, ...)                                                                                         \
-    hipLaunchKernelGGL((k_reset<CA, CT, RS, ##__VA_ARGS__>), GRID(env), (env_kernel_lds_bytes<CA, CT, RS>(env->L)), (hipStream_t)stream, DIMS(env), env->kp, \
-                       env->state, seeds, env->summary, env->ablog, env->p.flags, (const int32_t*)env->sizes, env->gscratch)
-    DISPATCH_ENV(env);
-#undef CALL
-    LAUNCH_OK();
+    const auto args = std::make_tuple(DIMS(env), env->kp, env->state, seeds, env->summary, env->ablog, env->p.flags, env->sizes, env->gscratch);
+    DCM_TRY(launched(with_sim(sim_of(env), [&](auto s) {
+        using S = decltype(s);
+        launch(k_reset<SIM_ARGS(S), S::MC>, (unsigned)env->p.n_envs, env_kernel_lds_bytes<SIM_ARGS(S)>(env->L), (hipStream_t)stream, args);
+        return 0;
+    })));
     if (env->log.len)
         HIP_TRY(hipMemsetAsync(env->log.len, 0, (size_t)env->p.n_envs * env->A * sizeof(int32_t), (hipStream_t)stream));
     if (env->rollout_log.len)
@@ -2291,14 +2327,13 @@ int dcm_observe(dcm_env* env, float* agents_out, float* tasks_out, uint8_t* mask
                 uint8_t* active_out, const int32_t* leader_in, void* stream) {
     CHECK_ENV(env);
     if (!env->reset_done) return fail(DCM_ERR_STATE, "dcm_observe: call dcm_reset first");
-#define CALL(CA, CT, RS, ...)                                                                                           \
-    hipLaunchKernelGGL((k_observe<CA, CT, RS, ##__VA_ARGS__>), GRID(env), (env_kernel_lds_bytes<CA, CT, RS>(env->L)), (hipStream_t)stream, DIMS(env),            \
-                       env->state, agents_out, tasks_out, mask_out, leader_out, active_out, leader_in,                  \
-                       (const int32_t*)env->sizes, env->p.flags)
-    DISPATCH_ENV(env);
-#undef CALL
-    LAUNCH_OK();
-    return DCM_OK;
+    const auto args = std::make_tuple(DIMS(env), env->state, agents_out, tasks_out, mask_out, leader_out, active_out, leader_in, env->sizes,
+                                      env->p.flags);
+    return launched(with_sim(sim_of(env), [&](auto s) {
+        using S = decltype(s);
+        launch(k_observe<SIM_ARGS(S), S::MC>, (unsigned)env->p.n_envs, env_kernel_lds_bytes<SIM_ARGS(S)>(env->L), (hipStream_t)stream, args);
+        return 0;
+    }));
 }
 
 int dcm_step(dcm_env* env, const int32_t* actions, const int32_t* leader_in, const int32_t* nfol_in,
@@ -2343,27 +2378,17 @@ int dcm_step(dcm_env* env, const int32_t* actions, const int32_t* leader_in, con
         if (form == plan::RenewForm::Sizes && !stream_capturing(stream)) DCM_TRY(dcm::flush_pending(env, stream));
         (void)renewing_launch(env, stream);
         const unsigned char* const image = plan::step_restart_image(env->init_valid, pendq != nullptr, renew) ? env->init : nullptr;
-        const Renew rn = renew_args(env);
-#define STEP_FAST_ARGS(SIZES) DIMS(env), env->kp, env->state, actions, agents_out, tasks_out, mask_out, leader_out, active_out, env->summary, env->ablog,  \
-                       env->p.flags, SIZES, env->gscratch, env->p.auto_reset_episodes, env->retlog, (int)env->retcap, \
-                       env->side, env->side_pitch, pendq, image
-        if (form == plan::RenewForm::Sizes) {
-#define CALL(CA, CT, RS) hipLaunchKernelGGL((k_rs_step_fast<CA, CT, RS>), GRID(env), (step_fast_lds_bytes<CA, CT, RS>(env->L)), (hipStream_t)stream, \
-                                            STEP_FAST_ARGS(env->sizes), rn)
-            DISPATCH_ONE_CHUNK_RAGGED(env);
-#undef CALL
-        } else {
-#define CALL(CA, CT, RS)                                                                             \
-    do {                                                                                             \
-        const unsigned lds = step_fast_lds_bytes<CA, CT, RS>(env->L);                                \
-        if (renew) hipLaunchKernelGGL((k_rn_step_fast<CA, CT, RS>), GRID(env), lds, (hipStream_t)stream, STEP_FAST_ARGS((const int32_t*)env->sizes), rn); \
-        else hipLaunchKernelGGL((k_step_fast<CA, CT, RS>), GRID(env), lds, (hipStream_t)stream, STEP_FAST_ARGS((const int32_t*)env->sizes)); \
-    } while (0)
-            DISPATCH_ONE_CHUNK(env);
-#undef CALL
-        }
-#undef STEP_FAST_ARGS
-        LAUNCH_OK();
+        const auto args = std::make_tuple(DIMS(env), env->kp, env->state, actions, agents_out, tasks_out, mask_out, leader_out, active_out,
+                                          env->summary, env->ablog, env->p.flags, env->sizes, env->gscratch, env->p.auto_reset_episodes,
+                                          env->retlog, (int)env->retcap, env->side, env->side_pitch, pendq, image);
+        const int rc = with_sim(sim_of(env), [&](auto s) {
+            using S = decltype(s);
+            if constexpr (S::one_chunk)
+                return launch_family<step_fast_family, S::reads_sizes, SIM_ARGS(S)>(form, (unsigned)env->p.n_envs, step_fast_lds_bytes<SIM_ARGS(S)>(env->L),
+                                                                                    (hipStream_t)stream, args, renew_args(env));
+            else return -1;
+        });
+        DCM_TRY(launched(rc));
         if (pendq) {
             env->maybe_pending = true;
             if (++env->steps_since_flush >= dcm_env::FLUSH_EVERY) return dcm::flush_pending(env, stream);
@@ -2372,29 +2397,15 @@ int dcm_step(dcm_env* env, const int32_t* actions, const int32_t* leader_in, con
     }
     DCM_TRY(dcm::flush_pending(env, stream));    // (the general kernel writes summary rows itself)
     const plan::RenewForm form = renewing_launch(env, stream);
-    const bool renew = form != plan::RenewForm::Plain;
-    const Renew rn = renew_args(env);
-#define STEP_ARGS(SIZES) DIMS(env), env->kp, env->state, actions, leader_in, nfol_in, followers_in, agents_out, tasks_out, mask_out, leader_out, \
-                  active_out, env->summary, env->log, env->ablog, env->p.flags, SIZES, env->gscratch, \
-                  env->p.auto_reset_episodes, env->retlog, (int)env->retcap
-    if (form == plan::RenewForm::Sizes) {
-#define CALL(CA, CT, RS, ...) hipLaunchKernelGGL((k_rs_step<CA, CT, RS, ##__VA_ARGS__>), GRID(env), (env_kernel_lds_bytes<CA, CT, RS>(env->L)), \
-                                                 (hipStream_t)stream, STEP_ARGS(env->sizes), rn)
-        DISPATCH_RAGGED(env);
-#undef CALL
-    } else {
-#define CALL(CA, CT, RS, ...)                                                                        \
-    do {                                                                                             \
-        const unsigned lds = env_kernel_lds_bytes<CA, CT, RS>(env->L);                               \
-        if (renew) hipLaunchKernelGGL((k_rn_step<CA, CT, RS, ##__VA_ARGS__>), GRID(env), lds, (hipStream_t)stream, STEP_ARGS((const int32_t*)env->sizes), rn); \
-        else hipLaunchKernelGGL((k_step<CA, CT, RS, ##__VA_ARGS__>), GRID(env), lds, (hipStream_t)stream, STEP_ARGS((const int32_t*)env->sizes)); \
-    } while (0)
-        DISPATCH_ENV(env);
-#undef CALL
-    }
-#undef STEP_ARGS
-    LAUNCH_OK();
-    return DCM_OK;
+    const auto args = std::make_tuple(DIMS(env), env->kp, env->state, actions, leader_in, nfol_in, followers_in, agents_out, tasks_out, mask_out,
+                                      leader_out, active_out, env->summary, env->log, env->ablog, env->p.flags, env->sizes, env->gscratch,
+                                      env->p.auto_reset_episodes, env->retlog, (int)env->retcap);
+    const int rc = with_sim(sim_of(env), [&](auto s) {
+        using S = decltype(s);
+        return launch_family<step_family, S::reads_sizes, SIM_ARGS(S), S::MC>(form, (unsigned)env->p.n_envs, env_kernel_lds_bytes<SIM_ARGS(S)>(env->L),
+                                                                              (hipStream_t)stream, args, renew_args(env));
+    });
+    return launched(rc);
 }
 
 int dcm_set_rollout_log(dcm_env* env, int16_t* route_task, double* route_arrival, int32_t* route_len, int32_t cap) {
@@ -2416,64 +2427,48 @@ int dcm_rollout_random(dcm_env* env, int32_t episodes, int64_t max_decisions, co
     DCM_TRY(dcm::flush_pending(env, stream));
     // the renewing (k_rn_*) or size-renewing (k_rs_*) form of whichever kernel serves the handle, while a stride is set (dcm_set_instance_renewal)
     const plan::RenewForm form = renewing_launch(env, stream);
-    const bool renew = form == plan::RenewForm::Instance, renew_sizes = form == plan::RenewForm::Sizes;
     const dcm::RolloutArgs ra = rollout_args(env, form, episodes, max_decisions, max_decisions_in, agents_out, tasks_out, mask_out, steps_out);
+    const auto args = ra.kernel_args();
     const unsigned grid = (unsigned)env->p.n_envs;
     const hipStream_t hs = (hipStream_t)stream;
     // The register-resident kernels have the same contract and the same results as the general one (tests/test_gpu_rollout.py runs both)
     const bool all_obs = agents_out && tasks_out && mask_out, no_obs = !agents_out && !tasks_out && !mask_out;
+    int rc = 0;
     switch (plan::rollout_kind(shape_of(env), all_obs || no_obs)) {
     case plan::Rollout::Fast: {
         // wave priorities (k_rollout_fast, PRIO) for a launch that fills the machine by itself: 16 workgroups x 256 CUs
         const bool prio = env->p.n_envs >= 4096;
-#define CALL(CA, CT, RS) do { if (prio) { if (all_obs) { CALLF(CA, CT, RS, true, true); } else { CALLF(CA, CT, RS, false, true); } }   \
-                              else { if (all_obs) { CALLF(CA, CT, RS, true, false); } else { CALLF(CA, CT, RS, false, false); } } } while (0)
-        if (renew_sizes) {
-#define CALLF(CA, CT, RS, OBS, PRIO) launch(k_rs_rollout_fast<CA, CT, RS, OBS, PRIO>, grid, rollout_fast_lds_bytes<CA, CT, RS>(env->L), hs, ra, ra.rn)
-            DISPATCH_ONE_CHUNK_RAGGED(env);
-#undef CALLF
-        } else {
-#define CALLF(CA, CT, RS, OBS, PRIO)                                                                                                  \
-    do {                                                                                                                              \
-        if (renew) launch(k_rn_rollout_fast<CA, CT, RS, OBS, PRIO>, grid, rollout_fast_lds_bytes<CA, CT, RS>(env->L), hs, ra, ra.rn); \
-        else launch(k_rollout_fast<CA, CT, RS, OBS, PRIO>, grid, rollout_fast_lds_bytes<CA, CT, RS>(env->L), hs, ra);                 \
-    } while (0)
-            DISPATCH_ONE_CHUNK(env);
-#undef CALLF
-        }
-#undef CALL
+        rc = with_sim(sim_of(env), [&](auto s) {
+            using S = decltype(s);
+            if constexpr (S::one_chunk)
+                return with_bool(prio, [&](auto prio_c) {
+                    return with_bool(all_obs, [&](auto obs_c) {
+                        return launch_family<rollout_fast_family, S::reads_sizes, SIM_ARGS(S), decltype(obs_c)::value, decltype(prio_c)::value>(
+                            form, grid, rollout_fast_lds_bytes<SIM_ARGS(S)>(env->L), hs, args, ra.rn);
+                    });
+                });
+            else return -1;
+        });
         break;
     }
-    case plan::Rollout::FastMc:                                                 // (exact shape, never ragged: no size-renewing form)
-#define CALLM(OBS)                                                                                                \
-    do {                                                                                                          \
-        if (renew) launch(k_rn_rollout_fast_mc<50, 200, OBS>, grid, FastM<50, 200, OBS>::LDS_BYTES, hs, ra, ra.rn); \
-        else launch(k_rollout_fast_mc<50, 200, OBS>, grid, FastM<50, 200, OBS>::LDS_BYTES, hs, ra);               \
-    } while (0)
-        if (all_obs) { CALLM(true); } else { CALLM(false); }
-#undef CALLM
+    case plan::Rollout::FastMc:
+        rc = with_bool(all_obs, [&](auto obs_c) {
+            constexpr bool OBS = decltype(obs_c)::value;
+            return launch_family<rollout_fast_mc_family, false, 50, 200, OBS>(form, grid, FastM<50, 200, OBS>::LDS_BYTES, hs, args, ra.rn);
+        });
         break;
     case plan::Rollout::FastG:
         dcm::launch_rollout_fast_g(plan::fast_g_agent_chunks(env->A), plan::fast_g_task_chunks(env->T), all_obs, grid, env->L, hs, ra);
         break;
     case plan::Rollout::General:
-        if (renew_sizes) {
-#define CALL(CA, CT, RS, ...) launch(k_rs_rollout_random<CA, CT, RS, ##__VA_ARGS__>, grid, rollout_random_lds_bytes<CA, CT, RS>(env->L), hs, ra, ra.rn)
-            DISPATCH_RAGGED(env);
-#undef CALL
-        } else {
-#define CALL(CA, CT, RS, ...)                                                                                                                    \
-    do {                                                                                                                                         \
-        if (renew) launch(k_rn_rollout_random<CA, CT, RS, ##__VA_ARGS__>, grid, rollout_random_lds_bytes<CA, CT, RS>(env->L), hs, ra, ra.rn);    \
-        else launch(k_rollout_random<CA, CT, RS, ##__VA_ARGS__>, grid, rollout_random_lds_bytes<CA, CT, RS>(env->L), hs, ra);                    \
-    } while (0)
-            DISPATCH_ENV(env);
-#undef CALL
-        }
+        rc = with_sim(sim_of(env), [&](auto s) {
+            using S = decltype(s);
+            return launch_family<rollout_random_family, S::reads_sizes, SIM_ARGS(S), S::MC>(form, grid, rollout_random_lds_bytes<SIM_ARGS(S)>(env->L),
+                                                                                            hs, args, ra.rn);
+        });
         break;
     }
-    LAUNCH_OK();
-    return DCM_OK;
+    return launched(rc);
 }
 
 int dcm_rollout_policy(dcm_env* env, int32_t policy, int32_t episodes, int64_t max_decisions, const int64_t* max_decisions_in,

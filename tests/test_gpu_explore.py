@@ -26,6 +26,9 @@ FORMS = {
     "F5": (66, 70, 4, {}, None, -1),                                            # general, the mid-size layout
     "F6": (10, 20, 4, dict(max_waiting_time=0.0), None, 60),                    # general, the literal rule; every launch under a budget
 }
+# ... and one whose launches need the raised dynamic-LDS limit (record_bytes > 64 KiB): the two ends only
+BIG_FORMS = {"F7-above-64KiB": (4, 700, 2, {}, None, -1)}
+ALL_FORMS = {**FORMS, **BIG_FORMS}
 
 
 def _shared():
@@ -37,7 +40,7 @@ def _shared():
 def _form_instances(form):
     from dcmrta_amd.choice import env_seeds
     from dcmrta_amd.instances import generate_batch, generate_batch_ranges
-    A, T, B, _, ranges, _ = FORMS[form]
+    A, T, B, _, ranges, _ = ALL_FORMS[form]
     inst = generate_batch(B, A, T, base_seed=6000 + 3 * A + T) if ranges is None else generate_batch_ranges(range(6100, 6100 + B), *ranges)
     return inst, env_seeds(41, 0, B)
 
@@ -46,7 +49,7 @@ def _form_instances(form):
 def _form_sims(form, policy, episodes):
     """The oracle's side of one launch of `episodes` episodes on a form under one of the three pinned policies: computed once, shared."""
     L = _shared()
-    A, T, B, kw, ranges, budget = FORMS[form]
+    A, T, B, kw, ranges, budget = ALL_FORMS[form]
     inst, seeds = _form_instances(form)
     sims, steps = [], []
     for b in range(B):
@@ -59,9 +62,10 @@ def _form_sims(form, policy, episodes):
 
 def _form_env(gpu_device, form, logged=True, ring=2):
     from dcmrta_amd.batched_env import BatchedTaskEnv
-    A, T, B, kw, _, _ = FORMS[form]
+    A, T, B, kw, _, _ = ALL_FORMS[form]
     inst, seeds = _form_instances(form)
     env = BatchedTaskEnv(B, A, T, device=gpu_device, **kw).load_instances(**inst)
+    assert (env.record_bytes() > 65536) == (form in BIG_FORMS)
     if logged:
         env.enable_rollout_log(CAP)
     env._ring = env.enable_return_log(ring)
@@ -90,12 +94,12 @@ def _assert_same(got, ref, tag):
 # ---------------------------------------------------------------------------------------------------- 1. + 2. the two ends
 @pytest.mark.parametrize("logged", [True, False], ids=["log", "nolog"])
 @pytest.mark.parametrize("base", BASES)
-@pytest.mark.parametrize("form", sorted(FORMS))
+@pytest.mark.parametrize("form", sorted(ALL_FORMS))
 def test_the_ends_are_the_greedy_and_the_random_policy(gpu_device, form, base, logged):
     """explore_q32 = 0 against rollout(base), explore_q32 = 2^32 against rollout("random"), each on a twin handle, two episodes: byte for
     byte; and the twin's launch is the oracle's (steps, the last episode's reward, the logged lists)."""
     L = _shared()
-    budget = FORMS[form][5]
+    budget = ALL_FORMS[form][5]
     for q32, pinned in ((0, base), (Q_ALL, "random")):
         tag = f"{form} {base} q={q32} {'log' if logged else 'nolog'}"
         twin, _ = _form_env(gpu_device, form, logged)

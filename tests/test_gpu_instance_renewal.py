@@ -112,6 +112,7 @@ ROLLOUT_CASES = [
     pytest.param(70, 130, 8, 5, 5, None, 8500, id="70A130T-fast-g"),
     pytest.param(100, 300, 4, 5, 5, None, 8600, id="100A300T-general"),
     pytest.param(20, 50, 16, 16, 9, None, 8700, id="20A50T-wide-9"),
+    pytest.param(4, 700, 2, 5, 5, None, 8800, id="4A700T-general-above-64KiB"),   # a launch that needs the raised dynamic-LDS limit
 ]
 
 
@@ -121,6 +122,8 @@ def test_persistent_rollout_plays_a_new_instance_every_episode(gpu_device, A, T,
     stride = B if stride is None else stride
     seeds = env_seeds(51, 0, B)
     env, ring = _make(gpu_device, B, A, T, base, stride, mcs, member_cap)
+    if T == 700:
+        assert env.record_bytes() > 65536
     env.reset(seeds, observe=False)
     steps = env.rollout_random(episodes=EPISODES).cpu().numpy()
     _assert_after_three(env, ring, _chains(A, T, B, base, stride, seeds, mcs), range(B), steps)
@@ -202,11 +205,14 @@ def _lockstep(env, seeds, read_summary_every=0, policy=None):
     pytest.param(20, 50, 96, 9100, 0, id="20A50T-summaries-read-at-the-end"),
     pytest.param(64, 63, 16, 9300, 40, id="64A63T"),
     pytest.param(50, 200, 8, 9400, 40, id="50A200T-general-k_step"),
+    pytest.param(4, 700, 2, 8800, 40, id="4A700T-general-k_step-above-64KiB"),
 ])
 def test_lockstep_auto_reset_renews(gpu_device, A, T, B, base, read_every):
     from dcmrta_amd.choice import env_seeds
     seeds = env_seeds(53, 0, B)
     env, ring = _make(gpu_device, B, A, T, base, B, auto_reset=True, auto_reset_episodes=EPISODES)
+    if T == 700:
+        assert env.record_bytes() > 65536
     dcount = _lockstep(env, seeds, read_every)
     _assert_after_three(env, ring, _chains(A, T, B, base, B, seeds), range(B), dcount)
     assert np.array_equal(env.status()["decisions"].cpu().numpy(), dcount)

@@ -142,6 +142,7 @@ ORACLE_CASES = [
     pytest.param(64, 64, 6, {}, None, id="64A64T-general-no-depot-lane"),
     pytest.param(70, 130, 6, {}, None, id="70A130T-general"),
     pytest.param(10, 20, 8, dict(member_cap=16), None, id="10A20T-wide-general"),
+    pytest.param(4, 700, 2, {}, None, id="4A700T-general-above-64KiB"),        # a launch that needs the raised dynamic-LDS limit
 ]
 
 
@@ -178,6 +179,8 @@ def test_three_episodes_and_a_random_stop_against_the_oracle(gpu_device, A, T, B
     inst = _case_instances(A, T, B, ranges)
     seeds, refs = _case_refs(A, T, B, ranges, policy, kw.get("max_waiting_time", 10.0))
     env = BatchedTaskEnv(B, A, T, device=gpu_device, **kw)
+    if T == 700:
+        assert env.record_bytes() > 65536
     if ranges is None:
         env.load_instances(**inst)
     else:                                                # per-env sizes drawn on the device; the oracle plays the host generator's batch
@@ -210,6 +213,23 @@ def test_three_episodes_and_a_random_stop_against_the_oracle(gpu_device, A, T, B
         for k in ("travel_dist", "returned", "agent_wait"):
             f[k] = f[k][:a]
         H.assert_final_matches(f, eps[-1], tag)
+
+
+@pytest.mark.parametrize("policy", POLICIES)
+def test_wide_handle_above_64KiB_against_the_oracle(gpu_device, policy):
+    """The same comparison on a wide handle (sixteen member slots) at the smallest T whose record no longer fits the default 64 KiB
+    of dynamic LDS; T comes from the sizes the library reports."""
+    from dcmrta_amd.batched_env import BatchedTaskEnv
+    A, B, kw = 4, 2, dict(member_cap=16)
+    size = lambda t: BatchedTaskEnv(B, A, t, device=gpu_device, **kw).record_bytes()
+    lo, hi = 1, 2                                        # size(lo) <= 65536 < size(hi)
+    while size(hi) <= 65536:
+        lo, hi = hi, 2 * hi
+    while hi - lo > 1:
+        mid = (lo + hi) // 2
+        lo, hi = (lo, mid) if size(mid) > 65536 else (mid, hi)
+    assert size(hi - 1) <= 65536 < size(hi)
+    test_three_episodes_and_a_random_stop_against_the_oracle(gpu_device, A, hi, B, kw, None, policy)
 
 
 @pytest.mark.parametrize("policy", POLICIES)

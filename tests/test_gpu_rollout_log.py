@@ -155,6 +155,8 @@ FORMS = {
     "10A20T-wide": (10, 20, 4, dict(member_cap=16), None, -1),
     "10A20T-mwt0": (10, 20, 4, dict(max_waiting_time=0.0), None, 60),           # the launch stops at 60 decisions: the prefix
 }
+# ... and one whose launches need the raised dynamic-LDS limit (record_bytes > 64 KiB): test 7 only
+BIG_FORMS = {"4A700T-general-above-64KiB": (4, 700, 2, {}, None, -1)}
 
 
 CAP = 64
@@ -164,7 +166,7 @@ CAP = 64
 def _form_instances(form):
     from dcmrta_amd.choice import env_seeds
     from dcmrta_amd.instances import generate_batch, generate_batch_ranges
-    A, T, B, _, ranges, _ = FORMS[form]
+    A, T, B, _, ranges, _ = {**FORMS, **BIG_FORMS}[form]
     inst = generate_batch(B, A, T, base_seed=4000 + 3 * A + T) if ranges is None else generate_batch_ranges(range(4100, 4100 + B), *ranges)
     return inst, env_seeds(37, 0, B)
 
@@ -186,9 +188,11 @@ def _form_sims(form, policy, episodes):
 
 def _form_env(gpu_device, form):
     from dcmrta_amd.batched_env import BatchedTaskEnv
-    A, T, B, kw, _, _ = FORMS[form]
+    A, T, B, kw, _, _ = {**FORMS, **BIG_FORMS}[form]
     inst, seeds = _form_instances(form)
-    return BatchedTaskEnv(B, A, T, device=gpu_device, **kw).load_instances(**inst), seeds
+    env = BatchedTaskEnv(B, A, T, device=gpu_device, **kw).load_instances(**inst)
+    assert (env.record_bytes() > 65536) == (form in BIG_FORMS)
+    return env, seeds
 
 
 @pytest.mark.parametrize("policy", POLICIES)
@@ -328,11 +332,11 @@ def test_a_size_renewing_launch_is_refused_while_the_log_is_set(gpu_device):
 
 # ---------------------------------------------------------------------------------------------------- 7. the log changes nothing else
 @pytest.mark.parametrize("policy", POLICIES)
-@pytest.mark.parametrize("form", sorted(FORMS))
+@pytest.mark.parametrize("form", sorted(FORMS) + sorted(BIG_FORMS))
 def test_a_launch_with_the_log_returns_what_it_returns_without(gpu_device, form, policy):
     """The same two-episode launch with and without the log: steps, records (clone_state), summary rows, the return log and the
     observation buffers byte for byte.  A lockstep log enabled beside the rollout log stays empty."""
-    budget = FORMS[form][5]
+    budget = {**FORMS, **BIG_FORMS}[form][5]
     out = []
     for logged in (False, True):
         env, seeds = _form_env(gpu_device, form)

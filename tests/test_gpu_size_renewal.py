@@ -130,6 +130,7 @@ ROLLOUT_CASES = [
     pytest.param(20, (5, 50), 16, 5, 5, None, 18800, id="tasks-range-only"),
     pytest.param((3, 20), 50, 16, 5, 5, None, 18900, id="agents-range-only"),
     pytest.param((3, 20), (5, 50), 16, 5, 5, WRAP_STRIDE, (1 << 63) + 77, id="20x50-layout-stride-wraps"),
+    pytest.param(4, (690, 700), 2, 5, 5, None, 19000, id="general-above-64KiB"),   # a launch that needs the raised dynamic-LDS limit
 ]
 
 
@@ -140,6 +141,8 @@ def test_persistent_rollout_plays_new_sizes_every_episode(gpu_device, ar, tr, B,
     _size_table(ar, tr, B, base, stride, mcs)
     seeds = env_seeds(61, 0, B)
     env, ring = _make(gpu_device, B, ar, tr, base, stride, mcs, member_cap)
+    if _dim(tr) == 700:
+        assert env.record_bytes() > 65536
     env.reset(seeds, observe=False)
     steps = env.rollout_random(episodes=EPISODES).cpu().numpy()
     _assert_after_three(env, ring, _chains(ar, tr, B, base, stride, seeds, mcs), steps)
@@ -248,12 +251,15 @@ def _lockstep(env, seeds, read_summary_every=0, policy=None):
     pytest.param((10, 20), (20, 50), 64, 19100, 0, id="reference-ranges-summaries-read-at-the-end"),
     pytest.param((10, 64), (20, 63), 16, 19300, 40, id="64x64-layout"),
     pytest.param((30, 70), (40, 160), 8, 19400, 40, id="general-k_step-128x256"),
+    pytest.param(4, (690, 700), 2, 19000, 40, id="general-k_step-above-64KiB"),
 ])
 def test_lockstep_auto_reset_renews_sizes(gpu_device, ar, tr, B, base, read_every):
     from dcmrta_amd.choice import env_seeds
     _size_table(ar, tr, B, base, B)
     seeds = env_seeds(63, 0, B)
     env, ring = _make(gpu_device, B, ar, tr, base, B, auto_reset=True, auto_reset_episodes=EPISODES)
+    if _dim(tr) == 700:
+        assert env.record_bytes() > 65536
     dcount = _lockstep(env, seeds, read_every)
     _assert_after_three(env, ring, _chains(ar, tr, B, base, B, seeds), dcount)
     assert np.array_equal(env.status()["decisions"].cpu().numpy(), dcount)
