@@ -451,6 +451,8 @@ class BatchedTaskEnv:
             check(self._lib.dcm_set_rollout_log(self._h, *[_ptr(x) for x in bufs], int(cap)))
             self._rollout_route = bufs
         self.graph_epoch += 1
+        if getattr(self, "_best", None) is not None:                        # the best log has the rollout log's cap: it follows
+            self.enable_best_log(bool(cap))
         return self
 
     def rollout_routes(self):
@@ -466,6 +468,60 @@ class BatchedTaskEnv:
         ValueError, like route_lists, when a route is longer than the log's cap."""
         from .trajectory import route_lists
         task, arrival, length = (x.cpu().numpy() for x in self.rollout_routes())
+        one = lambda e: [[t + 1 for t in r] for r, _ in route_lists(task[e], arrival[e], length[e], "enable_rollout_log(cap)")]
+        return one(b) if b is not None else [one(e) for e in range(self.B)]
+
+    def enable_best_log(self, on=True):
+        """Keep every env's best episode on the device (dcm_set_best_log): while on, rollout() under any policy keeps for each env the
+        best episode it has finished since reset() -- by the pair (finished tasks, reward); on a tie the earliest -- with its summary
+        row, its ordinal and its complete routes, across the episodes of a call and across calls: one call of B envs x E episodes
+        gives B x E samples and B plans (best_summary / best_episode / best_routes / best_plan).  Needs enable_rollout_log, whose cap
+        the buffers take (calling it again re-allocates them); reset() forgets the kept episodes.  rollout() refuses while instances
+        are renewed.  enable_best_log(False) disables."""
+        if not on:
+            if getattr(self, "_best", None) is not None:
+                check(self._lib.dcm_set_best_log(self._h, None, None, None, None, None))
+                self.graph_epoch += 1
+            self._best = None
+            return self
+        r = getattr(self, "_rollout_route", None)
+        if r is None:
+            raise DcmError("the best log copies the kept episode from the rollout log: call enable_rollout_log(cap) first")
+        B, A, dev, cap = self.B, self.A, self.device, r[0].shape[2]
+        bufs = (torch.full((B, A, cap), -2, dtype=torch.int16, device=dev),
+                torch.zeros((B, A, cap), dtype=torch.float64, device=dev),
+                torch.zeros((B, A), dtype=torch.int32, device=dev),
+                torch.full((B, 8), float("nan"), dtype=torch.float64, device=dev),
+                torch.full((B,), -1, dtype=torch.int32, device=dev))
+        check(self._lib.dcm_set_best_log(self._h, *[_ptr(x) for x in bufs]))
+        self._best = bufs
+        self.graph_epoch += 1
+        return self
+
+    def _best_log(self):
+        r = getattr(self, "_best", None)
+        if r is None:
+            raise DcmError("the best log is off: call enable_best_log() first")
+        return r
+
+    def best_routes(self):
+        """(task[B,A,cap], arrival[B,A,cap], length[B,A]) of enable_best_log: each env's kept episode, in rollout_routes' layout.  Only
+        [0, min(length, cap)) of a row is defined, and nothing for an env that keeps no episode (best_episode -1)."""
+        return self._best_log()[:3]
+
+    def best_summary(self):
+        """f64[B,8]: the summary row of each env's kept episode (summary's columns); NaN rows where none is kept."""
+        return self._best_log()[3]
+
+    def best_episode(self):
+        """int32[B]: the ordinal since reset() of each env's kept episode (its column of the return log), -1 = none kept."""
+        return self._best_log()[4]
+
+    def best_plan(self, b=None):
+        """rollout_plan over the kept episodes: plan[b][a] = [action, ...] with 0 = depot, k = task k-1, for every env or for env b
+        alone.  ValueError, like route_lists, when a kept route is longer than the log's cap."""
+        from .trajectory import route_lists
+        task, arrival, length = (x.cpu().numpy() for x in self.best_routes())
         one = lambda e: [[t + 1 for t in r] for r, _ in route_lists(task[e], arrival[e], length[e], "enable_rollout_log(cap)")]
         return one(b) if b is not None else [one(e) for e in range(self.B)]
 

@@ -173,6 +173,16 @@ struct RouteLog {
     int32_t cap;
 };
 
+// optional best log of the persistent launches (dcm_set_best_log): per env the best episode finished since dcm_reset.  task / arrival
+// / len have the layout (and the cap) of the rollout log that is set when a launch runs; episode -1 = none kept yet.
+struct BestLog {
+    int16_t* task;    // [B][A][cap]
+    double* arrival;  // [B][A][cap]
+    int32_t* len;     // [B][A]  (may exceed cap)
+    double* summary;  // [B][8]  the kept episode's summary row
+    int32_t* episode; // [B]     its ordinal since dcm_reset
+};
+
 extern __shared__ __attribute__((aligned(16))) unsigned char smem[];
 
 // One wavefront == one workgroup: LDS instructions of a wave execute in program order, so cross-lane
@@ -226,6 +236,7 @@ __device__ __forceinline__ HdrRegs load_hdr(const unsigned char* p) {
 // dcmrta_amd/choice.py: stream of 32-bit words hi(key_1), lo(key_1), hi(key_2), ...;
 // slot 0 leader, 1 action, 2+j follower j; below(r,n) = (r*n) >> 32.  All wave-uniform.
 constexpr uint64_t GAMMA = 0x9E3779B97F4A7C15ULL;
+constexpr uint64_t EXPLORE_SALT = 0xD6E8FEB86659FD93ULL;   // the explore word of a decision: mix64(key_1 ^ EXPLORE_SALT) >> 32 (rollout_explore.hpp)
 __device__ __forceinline__ uint64_t mix64(uint64_t z) {
     z = (z ^ (z >> 30)) * 0xBF58476D1CE4E5B9ULL;
     z = (z ^ (z >> 27)) * 0x94D049BB133111EBULL;
@@ -557,6 +568,7 @@ struct dcm_env {
     int32_t vis[4] = {20, 20, 10, 100};  // dynamic-arrival schedule: initial, batch, period, cap (env/task_env.py:567,:221)
     dcm::RouteLog log{nullptr, nullptr, nullptr, 0};   // dcm_set_route_log
     dcm::RouteLog rollout_log{nullptr, nullptr, nullptr, 0};   // dcm_set_rollout_log: the persistent launches' log (len set = the logging kernel forms)
+    dcm::BestLog best_log{nullptr, nullptr, nullptr, nullptr, nullptr};   // dcm_set_best_log (episode set = the best-keeping kernel form)
     // dcm_set_replay_log: route part (cap 0 = the replay log is off), final member lists [B][T][rlog_member_cols] and
     // feasible_assignment [B][T] (both nullable)
     dcm::RouteLog rlog{nullptr, nullptr, nullptr, 0};

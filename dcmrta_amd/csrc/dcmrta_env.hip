@@ -30,7 +30,7 @@
 
 using namespace dcm;
 
-// Translation units (Makefile).  The library is built from this file five times; every unit but the main one holds device code and
+// Translation units (Makefile).  The library is built from this file six times; every unit but the main one holds device code and
 // its launchers only, and the main unit reaches them through the dcm::launch_rollout_* functions declared below.
 //   unit    macro          holds                                                          options
 //   env     -DDCM_SPLIT_G  the host API and every kernel that is not in a unit below      SPLIT SCHED
@@ -38,11 +38,12 @@ using namespace dcm;
 //   env_p   -DDCM_TU_P     the greedy forms k_hp_* / k_hprn_* (rollout_policy.hpp)        SPLIT SCHED
 //   env_l   -DDCM_TU_L     the logging forms k_lg_* / k_lgrn_* (rollout_log.hpp)          SPLIT SCHED
 //   env_e   -DDCM_TU_E     the epsilon-greedy forms k_ex_* / k_exrn_* (rollout_explore.hpp)  SPLIT SCHED
+//   env_b   -DDCM_TU_B     the best-keeping form k_bs_* (rollout_best.hpp)                 SPLIT SCHED
 // SPLIT (-mllvm -phi-elim-split-all-critical-edges=1) costs k_rollout_fast_g 4 % (8.19 -> 8.53 ms per 4096 x 70A/130T launch) while it
 // buys the one-chunk and the 50A/200T kernel 2.1 % / 1.3 %: hence env_g.  The form units exist so that every kernel that was there
 // before them compiles from the text, and to the code, it had without them.  With none of the macros (the developer tools'
 // one-command builds) everything is in one unit.
-#if defined(DCM_TU_G) || defined(DCM_TU_P) || defined(DCM_TU_L) || defined(DCM_TU_E)
+#if defined(DCM_TU_G) || defined(DCM_TU_P) || defined(DCM_TU_L) || defined(DCM_TU_E) || defined(DCM_TU_B)
 #define DCM_DEVICE_ONLY_TU 1
 #elif !defined(DCM_SPLIT_G)
 #define DCM_ONE_UNIT 1
@@ -58,6 +59,9 @@ using namespace dcm;
 #endif
 #if defined(DCM_TU_E) || defined(DCM_ONE_UNIT)
 #define DCM_HAVE_EXPLORE 1    // ... the epsilon-greedy forms and their launcher
+#endif
+#if defined(DCM_TU_B) || defined(DCM_ONE_UNIT)
+#define DCM_HAVE_BEST 1       // ... the best-keeping form and its launcher
 #endif
 namespace dcm {
 #if !defined(DCM_DEVICE_ONLY_TU)
@@ -88,19 +92,23 @@ struct RolloutArgs {
     int policy = DCM_POLICY_RANDOM;   // last argument of the greedy-policy forms (k_hp_*, k_hprn_*)
     RouteLog lg{nullptr, nullptr, nullptr, 0};   // last argument of the logging forms (k_lg_*, k_lgrn_*), behind `policy`
     uint64_t explore_q32 = 0;          // the epsilon-greedy forms (k_ex_*, k_exrn_*): between `policy` and the log
+    BestLog best{nullptr, nullptr, nullptr, nullptr, nullptr};   // the best-keeping form (k_bs_*): behind the epsilon-greedy forms' arguments
 };
 // k_rollout_fast_g<NAC, NTC, OBS> / k_rn_rollout_fast_g / k_rs_rollout_fast_g (rollout_fast_g.hpp, its own translation unit)
 void launch_rollout_fast_g(int nac, int ntc, bool obs, unsigned grid, Lay L, hipStream_t stream, const RolloutArgs& a);
 // The greedy, logging and epsilon-greedy forms of k_rollout_fast / k_rollout_random (k_form.inc), each set in a translation unit of its
 // own.  fast: plan::form_rollout_kind said Fast; a.form: Plain or Instance; a.policy: DCM_POLICY_FIRST or DCM_POLICY_NEAREST, in the
 // logging forms any of the three; a.lg: the handle's rollout log, which the epsilon-greedy forms also take unset; a.explore_q32 <= 2^32.
+// The best-keeping form (k_bs_*) takes the epsilon-greedy forms' arguments and a.best; it has no renewing kernels (-1 for a.form other
+// than Plain: the host has refused that launch).
 // Return 0, or -1 when `kind` has no one-chunk kernel (the caller asked plan::form_rollout_kind, so it has).
 // allow_lds_*: the form's share of dcm_create's dynamic-LDS limit (see there).
 using FormLauncher = int(plan::SimKind kind, bool fast, bool obs, unsigned grid, Lay L, hipStream_t stream, const RolloutArgs& a);
-FormLauncher launch_rollout_policy, launch_rollout_log, launch_rollout_explore;
+FormLauncher launch_rollout_policy, launch_rollout_log, launch_rollout_explore, launch_rollout_best;
 void allow_lds_policy(int lds);
 void allow_lds_log(int lds);
 void allow_lds_explore(int lds);
+void allow_lds_best(int lds);
 }  // namespace dcm
 
 namespace {
@@ -1613,6 +1621,9 @@ constexpr uint32_t rollout_random_lds_bytes(Lay L) {
 #ifdef DCM_HAVE_EXPLORE
 #include "rollout_explore.hpp"
 #endif
+#ifdef DCM_HAVE_BEST
+#include "rollout_best.hpp"
+#endif
 
 __global__ __launch_bounds__(WAVE) void k_env_status(int PA, int PT, int PC, const unsigned char* state, int B, uint32_t* flags_out,
                                                     int64_t* dec_out, double* now_out, int32_t* episodes_out) {
@@ -1851,27 +1862,42 @@ template <class F>
 void allow_lds_form(int lds) {
     for_each_sim([&](auto s) {
         using S = decltype(s);
-        allow_lds(lds, F::general::template plain<SIM_ARGS(S), S::MC>(), F::general::template renewing<SIM_ARGS(S), S::MC>());
+        if constexpr (F::has_renewing)
+            allow_lds(lds, F::general::template plain<SIM_ARGS(S), S::MC>(), F::general::template renewing<SIM_ARGS(S), S::MC>());
+        else allow_lds(lds, F::general::template plain<SIM_ARGS(S), S::MC>());
     });
     for_each_sim([&](auto s) {
         using S = decltype(s);
-        if constexpr (S::one_chunk)
+        if constexpr (S::one_chunk && F::has_renewing)
             allow_lds(lds, F::fast::template plain<SIM_ARGS(S), true>(), F::fast::template plain<SIM_ARGS(S), false>(),
                       F::fast::template renewing<SIM_ARGS(S), true>(), F::fast::template renewing<SIM_ARGS(S), false>());
+        else if constexpr (S::one_chunk)
+            allow_lds(lds, F::fast::template plain<SIM_ARGS(S), true>(), F::fast::template plain<SIM_ARGS(S), false>());
     });
 }
 }  // namespace
 
 // One form: its name, the prefix of its plain and of its renewing kernels, and the arguments it appends behind retcap (behind a.rn in
 // the renewing ones).  The form has no size-renewing kernels and no wave-priority (PRIO) instantiation.
-#define DCM_FORM_LAUNCHERS(FORM, plain, renewing, ...)                                                                              \
+// DCM_PLAIN_FORM_LAUNCHERS: a form without renewing kernels either (HAS_RN false: its `renewing` accessors are never named, and a
+// launch in another form than Plain returns -1).
+#define DCM_FORM_LAUNCHERS(FORM, plain, renewing, ...) DCM_FORM_LAUNCHERS_(FORM, true, plain, renewing, __VA_ARGS__)
+#define DCM_PLAIN_FORM_LAUNCHERS(FORM, plain, ...) DCM_FORM_LAUNCHERS_(FORM, false, plain, plain, __VA_ARGS__)
+#define DCM_FORM_LAUNCHERS_(FORM, HAS_RN, P_, R_, ...)                                                                              \
     namespace {                                                                                                                      \
     struct FORM##_form {                                                                                                             \
-        struct fast { DCM_FORMS(plain##rollout_fast, renewing##rollout_fast) };                                                      \
-        struct general { DCM_FORMS(plain##rollout_random, renewing##rollout_random) };                                               \
+        static constexpr bool has_renewing = HAS_RN;                                                                                 \
+        struct fast { DCM_FORMS(P_##rollout_fast, R_##rollout_fast) };                                                               \
+        struct general { DCM_FORMS(P_##rollout_random, R_##rollout_random) };                                                        \
         template <class Fam, auto... V>                                                                                              \
         static int go(unsigned grid, unsigned lds_bytes, hipStream_t stream, const RolloutArgs& a) {                                 \
-            return launch_family<Fam, false, V...>(a.form, grid, lds_bytes, stream, a.kernel_args(), a.rn, __VA_ARGS__);             \
+            if constexpr (HAS_RN)                                                                                                    \
+                return launch_family<Fam, false, V...>(a.form, grid, lds_bytes, stream, a.kernel_args(), a.rn, __VA_ARGS__);         \
+            else {                                                                                                                   \
+                if (a.form != plan::RenewForm::Plain) return -1;                                                                     \
+                launch(Fam::template plain<V...>(), grid, lds_bytes, stream, a.kernel_args(), __VA_ARGS__);                          \
+                return 0;                                                                                                            \
+            }                                                                                                                        \
         }                                                                                                                            \
     };                                                                                                                               \
     }                                                                                                                                \
@@ -1889,6 +1915,11 @@ DCM_FORM_LAUNCHERS(log, k_lg_, k_lgrn_, a.policy, a.lg)
 #ifdef DCM_HAVE_EXPLORE
 DCM_FORM_LAUNCHERS(explore, k_ex_, k_exrn_, a.policy, a.explore_q32, a.lg)
 #endif
+#ifdef DCM_HAVE_BEST
+DCM_PLAIN_FORM_LAUNCHERS(best, k_bs_, a.policy, a.explore_q32, a.lg, a.best)
+#endif
+#undef DCM_FORM_LAUNCHERS_
+#undef DCM_PLAIN_FORM_LAUNCHERS
 #undef DCM_FORM_LAUNCHERS
 #undef DCM_FORMS
 #undef DCM_FORM
@@ -1994,7 +2025,8 @@ dcm::RolloutArgs rollout_args(const dcm_env* env, plan::RenewForm form, int32_t 
 }
 
 // A greedy, logging or epsilon-greedy form to the host: its launcher, and what `fn` says when a size-renewing launch asks for it
-struct RolloutForm { dcm::FormLauncher* launch; const char* no_sizes_form; };
+// (keeps_best: the best-keeping form, which rollout_form also refuses without the rollout log and while any renewal stride is set)
+struct RolloutForm { dcm::FormLauncher* launch; const char* no_sizes_form; bool keeps_best = false; };
 const RolloutForm FORM_POLICY{dcm::launch_rollout_policy,
     "%s: no greedy policy while a ragged batch renews its sizes (DCM_PARAM_RENEW_SIZES with a stride set): "
     "clear the stride with dcm_set_instance_renewal(env, 0), or use DCM_POLICY_RANDOM"};
@@ -2004,13 +2036,25 @@ const RolloutForm FORM_LOG{dcm::launch_rollout_log,
 const RolloutForm FORM_EXPLORE{dcm::launch_rollout_explore,
     "%s: no epsilon-greedy policy while a ragged batch renews its sizes (DCM_PARAM_RENEW_SIZES with a stride "
     "set): clear the stride with dcm_set_instance_renewal(env, 0), or use dcm_rollout_random"};
+const RolloutForm FORM_BEST{dcm::launch_rollout_best,
+    "%s: no best log while instances are renewed (the best episode of different instances means nothing): clear the stride with "
+    "dcm_set_instance_renewal(env, 0), or clear the best log with dcm_set_best_log(env, NULL, NULL, NULL, NULL, NULL)", true};
+// the form an entry point takes: the best-keeping one while dcm_set_best_log is set, else its own
+const RolloutForm& form_of(const dcm_env* env, const RolloutForm& own) { return env->best_log.episode ? FORM_BEST : own; }
 
 // The common tail of the entry points that launch such a form: dcm_rollout_policy, dcm_rollout_explore, and dcm_rollout_random /
 // dcm_rollout_policy while the rollout log is set (FORM_LOG, under any of the three policies).  The caller `fn` has validated its
 // arguments.  explore_q32: 0 and 2^32 run the same kernels as every other value, no shortcut to the greedy / random forms.
+// While dcm_set_best_log is set every one of them comes here with FORM_BEST (form_of), which needs the rollout log and no stride.
 int rollout_form(dcm_env* env, const char* fn, const RolloutForm& form, int32_t policy, uint64_t explore_q32, int32_t episodes,
                  int64_t max_decisions, const int64_t* max_decisions_in, float* agents_out, float* tasks_out, uint8_t* mask_out,
                  int64_t* steps_out, void* stream) {
+    if (form.keeps_best) {
+        if (!env->rollout_log.len)
+            return fail(DCM_ERR_STATE, "%s: the best log is set and the rollout log is not: the kept episode is copied from it; call "
+                                       "dcm_set_rollout_log first, or clear the best log with dcm_set_best_log(env, NULL, NULL, NULL, NULL, NULL)", fn);
+        if (env->renew_stride != 0) return fail(DCM_ERR_STATE, form.no_sizes_form, fn);
+    }
     if (!plan::form_ok(launch_form(env))) return fail(DCM_ERR_STATE, form.no_sizes_form, fn);
     DCM_TRY(dcm::flush_pending(env, stream));
     dcm::RolloutArgs ra = rollout_args(env, renewing_launch(env, stream), episodes, max_decisions, max_decisions_in, agents_out, tasks_out,
@@ -2018,6 +2062,7 @@ int rollout_form(dcm_env* env, const char* fn, const RolloutForm& form, int32_t 
     ra.policy = policy;
     ra.explore_q32 = explore_q32;
     ra.lg = env->rollout_log;          // (the epsilon-greedy forms take it set or not: one set of forms)
+    ra.best = env->best_log;
     const bool all_obs = agents_out && tasks_out && mask_out, no_obs = !agents_out && !tasks_out && !mask_out;
     const plan::Shape shape = shape_of(env);
     const bool fast = plan::form_rollout_kind(shape, all_obs || no_obs) == plan::Rollout::Fast;
@@ -2129,6 +2174,7 @@ int dcm_create(const dcm_params* params, dcm_env** out) {
     dcm::allow_lds_policy(lds);
     dcm::allow_lds_log(lds);
     dcm::allow_lds_explore(lds);
+    dcm::allow_lds_best(lds);
     allow_lds(lds, k_get_tasks<M>, k_get_agents<M>, k_get_tasks<MW>, k_get_agents<MW>);
     return DCM_OK;
 }
@@ -2290,6 +2336,12 @@ int dcm_reset(dcm_env* env, const uint64_t* seeds, void* stream) {
         HIP_TRY(hipMemsetAsync(env->log.len, 0, (size_t)env->p.n_envs * env->A * sizeof(int32_t), (hipStream_t)stream));
     if (env->rollout_log.len)
         HIP_TRY(hipMemsetAsync(env->rollout_log.len, 0, (size_t)env->p.n_envs * env->A * sizeof(int32_t), (hipStream_t)stream));
+    if (env->best_log.episode) {       // no episode kept: ordinal -1, a NaN summary row (all bits set), lengths 0
+        const size_t B = (size_t)env->p.n_envs;
+        HIP_TRY(hipMemsetAsync(env->best_log.episode, 0xFF, B * sizeof(int32_t), (hipStream_t)stream));
+        HIP_TRY(hipMemsetAsync(env->best_log.summary, 0xFF, B * 8 * sizeof(double), (hipStream_t)stream));
+        HIP_TRY(hipMemsetAsync(env->best_log.len, 0, B * env->A * sizeof(int32_t), (hipStream_t)stream));
+    }
     env->reset_done = true;
     // the restart image of the register-resident lockstep kernel (dcm_env::init, read by k_step_fast only): what this reset produced
     env->init_valid = false;
@@ -2416,13 +2468,23 @@ int dcm_set_rollout_log(dcm_env* env, int16_t* route_task, double* route_arrival
     return make_route_log("dcm_set_rollout_log", route_task, route_arrival, route_len, cap, &env->rollout_log);
 }
 
+int dcm_set_best_log(dcm_env* env, int16_t* best_task, double* best_arrival, int32_t* best_len, double* best_summary,
+                     int32_t* best_episode) {
+    CHECK_HANDLE(env);
+    const bool off = !best_task && !best_arrival && !best_len && !best_summary && !best_episode;
+    if (!off && (!best_task || !best_arrival || !best_len || !best_summary || !best_episode))
+        return fail(DCM_ERR_INVALID, "dcm_set_best_log: give all five arrays, or all NULL");
+    env->best_log = dcm::BestLog{best_task, best_arrival, best_len, best_summary, best_episode};
+    return DCM_OK;
+}
+
 int dcm_rollout_random(dcm_env* env, int32_t episodes, int64_t max_decisions, const int64_t* max_decisions_in,
                        float* agents_out, float* tasks_out, uint8_t* mask_out, int64_t* steps_out, void* stream) {
     CHECK_ENV(env);
     if (!env->reset_done) return fail(DCM_ERR_STATE, "dcm_rollout_random: call dcm_reset first");
     if (episodes < 1) return fail(DCM_ERR_INVALID, "dcm_rollout_random: episodes must be >= 1");
-    if (env->rollout_log.len)
-        return rollout_form(env, "dcm_rollout_random", FORM_LOG, DCM_POLICY_RANDOM, 0, episodes, max_decisions, max_decisions_in, agents_out,
+    if (env->rollout_log.len || env->best_log.episode)
+        return rollout_form(env, "dcm_rollout_random", form_of(env, FORM_LOG), DCM_POLICY_RANDOM, 0, episodes, max_decisions, max_decisions_in, agents_out,
                             tasks_out, mask_out, steps_out, stream);
     DCM_TRY(dcm::flush_pending(env, stream));
     // the renewing (k_rn_*) or size-renewing (k_rs_*) form of whichever kernel serves the handle, while a stride is set (dcm_set_instance_renewal)
@@ -2481,7 +2543,7 @@ int dcm_rollout_policy(dcm_env* env, int32_t policy, int32_t episodes, int64_t m
     if (!env->reset_done) return fail(DCM_ERR_STATE, "dcm_rollout_policy: call dcm_reset first");
     if (episodes < 1) return fail(DCM_ERR_INVALID, "dcm_rollout_policy: episodes must be >= 1");
     DCM_TRY(need_budget(env, "dcm_rollout_policy", max_decisions, max_decisions_in));
-    return rollout_form(env, "dcm_rollout_policy", env->rollout_log.len ? FORM_LOG : FORM_POLICY, policy, 0, episodes, max_decisions,
+    return rollout_form(env, "dcm_rollout_policy", form_of(env, env->rollout_log.len ? FORM_LOG : FORM_POLICY), policy, 0, episodes, max_decisions,
                         max_decisions_in, agents_out, tasks_out, mask_out, steps_out, stream);
 }
 
@@ -2495,7 +2557,7 @@ int dcm_rollout_explore(dcm_env* env, int32_t policy, uint64_t explore_q32, int3
     if (!env->reset_done) return fail(DCM_ERR_STATE, "dcm_rollout_explore: call dcm_reset first");
     if (episodes < 1) return fail(DCM_ERR_INVALID, "dcm_rollout_explore: episodes must be >= 1");
     DCM_TRY(need_budget(env, "dcm_rollout_explore", max_decisions, max_decisions_in));
-    return rollout_form(env, "dcm_rollout_explore", FORM_EXPLORE, policy, explore_q32, episodes, max_decisions, max_decisions_in, agents_out,
+    return rollout_form(env, "dcm_rollout_explore", form_of(env, FORM_EXPLORE), policy, explore_q32, episodes, max_decisions, max_decisions_in, agents_out,
                         tasks_out, mask_out, steps_out, stream);
 }
 

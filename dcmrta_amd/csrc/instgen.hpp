@@ -240,7 +240,7 @@ __device__ __forceinline__ void take_sizes(SimT& S, uint32_t packed) {
     S.rA = (int)(packed & 0xFFFFu); S.rT = (int)(packed >> 16);
 }
 
-#if !defined(DCM_TU_G) && !defined(DCM_TU_P) && !defined(DCM_TU_L) && !defined(DCM_TU_E)   // (the units of k_rollout_fast_g, of the greedy-policy, the logging and the epsilon-greedy forms need the routines above only)
+#if !defined(DCM_TU_G) && !defined(DCM_TU_P) && !defined(DCM_TU_L) && !defined(DCM_TU_E) && !defined(DCM_TU_B)   // (the units of k_rollout_fast_g, of the greedy-policy, the logging, the epsilon-greedy and the best-keeping forms need the routines above only)
 
 // dcm_generate_instances: sizes = the handle's per-env sizes [B][2] on a ragged batch, else nullptr
 __global__ __launch_bounds__(WAVE) void k_generate_instances(int PA, int PT, int PC, unsigned char* state, const uint64_t* seeds, GenArgs g,
@@ -300,4 +300,4 @@ __global__ __launch_bounds__(WAVE) void k_generator_draws(const uint64_t* seeds,
     wave_doubles(p, lane_j, n_doubles, lane, [&](int j, double v) { doubles_out[(size_t)e * n_doubles + j] = v; });
     wave_bounded(p, lane_j, rng, n_ints, lane, [&](int i, uint32_t v) { ints_out[(size_t)e * n_ints + i] = v; });
 }
-#endif   // DCM_TU_G, DCM_TU_P, DCM_TU_L, DCM_TU_E
+#endif   // DCM_TU_G, DCM_TU_P, DCM_TU_L, DCM_TU_E, DCM_TU_B

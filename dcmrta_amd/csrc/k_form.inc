@@ -5,7 +5,7 @@
 //     #define KPOLICY_FORMS 1            only if it has the forms of the second table
 //     #include "k_form.inc"
 // in front of its kernel, declares it as KNAME(..., KSIZES, ... int retcap KRENEW_PARAM KPOLICY_PARAM), and ends with
-// #include "k_form_end.inc".  Whoever includes the text sets DCM_RENEW and at most one of DCM_POLICY, DCM_LOG, DCM_EXPLORE.
+// #include "k_form_end.inc".  Whoever includes the text sets DCM_RENEW and at most one of DCM_POLICY, DCM_LOG, DCM_EXPLORE, DCM_BEST.
 //
 //   DCM_RENEW   KNAME          launched                                            KRENEW_PARAM   KSIZES
 //   0           k_<base>       without a renewal stride                            --             const int32_t* sizes
@@ -20,22 +20,32 @@
 //   DCM_POLICY    k_hp_<base> / k_hprn_<base>    dcm_rollout_policy, FIRST / NEAREST  , int policy
 //   DCM_LOG       k_lg_<base> / k_lgrn_<base>    either, dcm_set_rollout_log set      , int policy, RouteLog lg
 //   DCM_EXPLORE   k_ex_<base> / k_exrn_<base>    dcm_rollout_explore                  , int policy, uint64_t explore_q32, RouteLog lg
+//   DCM_BEST      k_bs_<base> / --               any of the three, dcm_set_best_log   , int policy, uint64_t explore_q32, RouteLog lg, BestLog best
 // Greedy: the action comes from `policy` (wave-uniform) instead of protocol slot 1.  Logging: `policy` covers all three policies
 // (DCM_POLICY_RANDOM takes slot 1 as the plain form does) and every agent_step is appended to the log.  Epsilon-greedy: the logging
 // form with explore_q32; the log may be unset there (lg.len null).  These forms exist for k_rollout_fast and k_rollout_random only,
 // each set in a translation unit of its own (rollout_policy.hpp, rollout_log.hpp, rollout_explore.hpp), and none of them has a
 // size-renewing form: the host refuses that launch (plan::form_ok).
+// Best-keeping (rollout_best.hpp): the epsilon-greedy form with the log always set and `policy` covering all three as in the logging
+// form (explore_q32 = 0 under dcm_rollout_random / dcm_rollout_policy: their k_lg_* decisions and budget rule), plus ONE hook where the
+// text sees a freshly finished episode: keep_best (rollout_best.hpp) copies the env's summary row and its rows of the log to the best
+// log if the episode beats the kept one.  No renewing form at all: the host refuses a best-keeping launch while a stride is set.
+// KEXPLORES (defined here, for the texts): the form draws explore words -- DCM_EXPLORE or DCM_BEST.
 //
 // Two kernels from one text leave the first as it was: a form holds nothing of the others and compiles to the code it had before
-// they existed (DESIGN 4, 6).  A new form: one #elif here, its rollout_<form>.hpp, one DCM_FORM_LAUNCHERS line in dcmrta_env.hip.
+// they existed (DESIGN 4, 6).  A new form: one #elif here, its rollout_<form>.hpp, one DCM_FORM_LAUNCHERS line in dcmrta_env.hip
+// (DCM_PLAIN_FORM_LAUNCHERS for a form without renewing kernels).
 #ifndef KBASE
 #error "k_form.inc: the including text sets KBASE"
 #endif
-#if defined(DCM_POLICY) + defined(DCM_LOG) + defined(DCM_EXPLORE) > 1
-#error "at most one of DCM_POLICY, DCM_LOG, DCM_EXPLORE"
+#if defined(DCM_POLICY) + defined(DCM_LOG) + defined(DCM_EXPLORE) + defined(DCM_BEST) > 1
+#error "at most one of DCM_POLICY, DCM_LOG, DCM_EXPLORE, DCM_BEST"
 #endif
-#if (defined(DCM_POLICY) || defined(DCM_LOG) || defined(DCM_EXPLORE)) && !defined(KPOLICY_FORMS)
-#error "this kernel text has no greedy, logging or epsilon-greedy form"
+#if (defined(DCM_POLICY) || defined(DCM_LOG) || defined(DCM_EXPLORE) || defined(DCM_BEST)) && !defined(KPOLICY_FORMS)
+#error "this kernel text has no greedy, logging, epsilon-greedy or best-keeping form"
+#endif
+#if defined(DCM_BEST) && DCM_RENEW != 0
+#error "no renewing best-keeping form"
 #endif
 #if (defined(DCM_LOG) || defined(DCM_EXPLORE)) && DCM_RENEW == 2
 #error "no size-renewing logging form"
@@ -66,12 +76,18 @@
 #elif defined(DCM_EXPLORE)
 #define KPREFIX KFORM_PICK(k_ex_, k_exrn_)
 #define KPOLICY_PARAM , int policy, uint64_t explore_q32, RouteLog lg
+#elif defined(DCM_BEST)
+#define KPREFIX k_bs_
+#define KPOLICY_PARAM , int policy, uint64_t explore_q32, RouteLog lg, BestLog best
 #elif DCM_RENEW == 2
 #define KPREFIX k_rs_
 #define KPOLICY_PARAM
 #else
 #define KPREFIX KFORM_PICK(k_, k_rn_)
 #define KPOLICY_PARAM
+#endif
+#if defined(DCM_EXPLORE) || defined(DCM_BEST)
+#define KEXPLORES 1
 #endif
 #define KFORM_PASTE_(prefix, base) prefix##base
 #define KFORM_PASTE(prefix, base) KFORM_PASTE_(prefix, base)

@@ -4,6 +4,7 @@
 #undef KFORM_PASTE_
 #undef KPREFIX
 #undef KPOLICY_PARAM
+#undef KEXPLORES
 #undef KSIZES
 #undef KRENEW_PARAM
 #undef KFORM_PICK

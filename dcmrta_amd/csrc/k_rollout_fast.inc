@@ -1,5 +1,5 @@
 // k_rollout_fast.inc -- the kernel k_rollout_fast and all its forms (k_form.inc), compiled once per form: the plain, renewing and
-// size-renewing ones by rollout_fast.hpp, the others by rollout_policy.hpp, rollout_log.hpp and rollout_explore.hpp.
+// size-renewing ones by rollout_fast.hpp, the others by rollout_policy.hpp, rollout_log.hpp, rollout_explore.hpp and rollout_best.hpp.
 // Logging forms: Fast<>::apply appends to the log where it commits the member lanes.  Lane a keeps agent a's running length in a
 // register (FastLog): loaded once at the head, zeroed at a restart, written back once at the end -- nothing is loaded in the decision
 // loop on the log's behalf.
@@ -7,6 +7,8 @@
 // and kv2: one mix64, the high word kept); per decision one v_readlane, one scalar compare against explore_q32 and a wave-uniform
 // choice between DCM_POLICY_RANDOM and the base policy in front of decide_logged's ONE apply.  With the log unset: cap 0, nothing
 // stored, no length loaded or written back.
+// Best-keeping form (rollout_best.hpp): the epsilon-greedy code, the log always set, plus keep_best behind a finished episode; the
+// lengths it needs are the FastLog registers.  Nothing of it is in the decision loop.
 #define KBASE rollout_fast
 #define KPOLICY_FORMS 1
 #include "k_form.inc"
@@ -36,7 +38,7 @@ __global__ __launch_bounds__(WAVE, 4) void KNAME(int A, int T, int PA, int PT, K
     F f{S, (uint4*)(smem + (SimT::SCR_IN_LDS ? L.lds_bytes() : SimT::lds_image_bytes(L)))};
     f.init(lane);
     f.build_removal_table(lane);
-#ifdef DCM_EXPLORE
+#ifdef KEXPLORES
     // the env's rows of the log as in the logging form, or -- no log set -- a log of cap 0, to which apply<true> stores nothing
     const bool logged = lg.len != nullptr;
     FastLog fl{lg.task + (size_t)e * BA * lg.cap, lg.arrival + (size_t)e * BA * lg.cap, logged ? lg.cap : 0,
@@ -66,7 +68,7 @@ __global__ __launch_bounds__(WAVE, 4) void KNAME(int A, int T, int PA, int PT, K
     // chain of 20 scalar ones at the head of every decision); ki = the lane that holds the current decision's key
     uint64_t kv = mix64(gd + GAMMA * (uint64_t)lane);
     uint64_t kv2 = mix64(kv + GAMMA);                  // ... and their second keys (follower draws 0 and 1)
-#ifdef DCM_EXPLORE
+#ifdef KEXPLORES
     uint32_t xv = (uint32_t)(mix64(kv ^ EXPLORE_SALT) >> 32);   // ... and their explore words
 #endif
     int ki = 0;
@@ -126,7 +128,7 @@ __global__ __launch_bounds__(WAVE, 4) void KNAME(int A, int T, int PA, int PT, K
 #if DCM_RENEW
                 f.load_consts(r);
 #endif
-#if defined(DCM_LOG) || defined(DCM_EXPLORE)
+#if defined(DCM_LOG) || defined(KEXPLORES)
                 fl.len = 0;                                                       // the log is the new episode's
 #endif
                 need_adv = true;
@@ -148,7 +150,7 @@ __global__ __launch_bounds__(WAVE, 4) void KNAME(int A, int T, int PA, int PT, K
                 FPHK(f, 12);
                 CNT(0);
                 const uint64_t k1 = rl(kv, ki), k2 = rl(kv2, ki);
-#ifdef DCM_EXPLORE
+#ifdef KEXPLORES
                 // the decision explores iff its explore word < explore_q32: then the random policy's action (protocol slot 1), else the base pick
                 const bool explores = x_all || rl(xv, ki) < x_q;
                 const int rlen = f.decide_logged(r, h, P, lane, k1, agrow, tkrow, mkp, &k2, explores ? DCM_POLICY_RANDOM : policy, fl);
@@ -161,7 +163,7 @@ __global__ __launch_bounds__(WAVE, 4) void KNAME(int A, int T, int PA, int PT, K
 #endif
                 if (h.flags & DCM_FLAG_DONE) break;
                 gd += GAMMA;
-#ifdef DCM_EXPLORE
+#ifdef KEXPLORES
                 if (++ki == WAVE) { kv = mix64(gd + GAMMA * (uint64_t)lane); kv2 = mix64(kv + GAMMA); xv = (uint32_t)(mix64(kv ^ EXPLORE_SALT) >> 32); ki = 0; }
 #else
                 if (++ki == WAVE) { kv = mix64(gd + GAMMA * (uint64_t)lane); kv2 = mix64(kv + GAMMA); ki = 0; if constexpr (use_prio) set_prio(ep); }
@@ -184,6 +186,12 @@ __global__ __launch_bounds__(WAVE, 4) void KNAME(int A, int T, int PA, int PT, K
             FPHK(f, 12);
             if (need_adv) continue;
         }
+#ifdef DCM_BEST
+        // a finished episode, its restart (fl.len = 0) still to come: keep it if it beats the kept one.  Also reached by an episode
+        // that ends with the budget's last decision, which leaves the loop below without coming back.
+        if ((h.flags & DCM_FLAG_DONE) && !(h.flags & ROLLOUT_ERR))
+            keep_best<true>(best, lg, e, BA, S.A(), row, fl.len);
+#endif
         if (left == 0) break;
         ep++;
         if constexpr (use_prio) { if (ep < episodes) { nv_last = S.T(); set_prio(ep); } }
@@ -191,7 +199,7 @@ __global__ __launch_bounds__(WAVE, 4) void KNAME(int A, int T, int PA, int PT, K
     PH_FLUSH(lane);
     FPHK(f, 13);
     FPH_FLUSH(f, lane);
-#ifdef DCM_EXPLORE
+#ifdef KEXPLORES
     if (logged && f.inA) lg.len[(size_t)e * BA + f.la] = fl.len;
 #elif defined(DCM_LOG)
     if (f.inA) lg.len[(size_t)e * BA + f.la] = fl.len;

@@ -1,9 +1,11 @@
 // k_rollout_random.inc -- the kernel k_rollout_random and all its forms (k_form.inc), compiled once per form: the plain, renewing and
-// size-renewing ones by dcmrta_env.hip, the others by rollout_policy.hpp, rollout_log.hpp and rollout_explore.hpp.
+// size-renewing ones by dcmrta_env.hip, the others by rollout_policy.hpp, rollout_log.hpp, rollout_explore.hpp and rollout_best.hpp.
 // Logging forms: apply_and_advance appends to the log, and the env zeroes its lengths when it restarts an episode.
 // Epsilon-greedy forms: a decision whose explore word (mix64(key_1 ^ EXPLORE_SALT) >> 32) is below explore_q32 takes
 // pick_random_action, every other one pick_policy_action of the base policy (FIRST / NEAREST).  The budget is the greedy forms'
 // (rollout_budget_policy).
+// Best-keeping form (rollout_best.hpp): the epsilon-greedy decision with `policy` covering DCM_POLICY_RANDOM and the budget rule of the
+// logging forms (explore_q32 = 0 there: the k_lg_* launch), plus keep_best behind the decision loop of a finished episode.
 #define KBASE rollout_random
 #define KPOLICY_FORMS 1
 #include "k_form.inc"
@@ -41,7 +43,7 @@ __global__ __launch_bounds__(WAVE, 3) void KNAME(int A, int T, int PA, int PT, K
     double* row = summary + (size_t)e * 8;
 #if defined(DCM_POLICY) || defined(DCM_EXPLORE)
     const int left0 = rollout_budget_policy(e, budget_all, budget_in, P);
-#elif defined(DCM_LOG)
+#elif defined(DCM_LOG) || defined(DCM_BEST)
     const int left0 = policy == DCM_POLICY_RANDOM ? rollout_budget(e, budget_all, budget_in) : rollout_budget_policy(e, budget_all, budget_in, P);
 #else
     const int left0 = rollout_budget(e, budget_all, budget_in);
@@ -62,7 +64,7 @@ __global__ __launch_bounds__(WAVE, 3) void KNAME(int A, int T, int PA, int PT, K
 #elif DCM_RENEW
             wave_renew_instance_call(S, rec, rn, e, lane, xy);
 #endif
-#ifdef DCM_EXPLORE
+#ifdef KEXPLORES
             if (lg.len) for (int a = lane; a < S.A(); a += WAVE) lg.len[(size_t)e * BA + a] = 0;   // the log, if set, is the new episode's
 #elif defined(DCM_LOG)
             for (int a = lane; a < S.A(); a += WAVE) lg.len[(size_t)e * BA + a] = 0;   // the log is the new episode's (as k_step's restart)
@@ -83,10 +85,14 @@ __global__ __launch_bounds__(WAVE, 3) void KNAME(int A, int T, int PA, int PT, K
             if (all_obs) { __builtin_assume(ag != nullptr); __builtin_assume(tk != nullptr); __builtin_assume(mk != nullptr); S.observe(h, lane, leader, ag, tk, mk, xy); }
             else S.observe(h, lane, leader, ag, tk, mk, xy);
             PH_MARK(1);
-#ifdef DCM_EXPLORE
+#ifdef KEXPLORES
             // the decision explores iff its explore word < explore_q32 (wave-uniform): protocol slot 1 then, the base policy's pick otherwise
             const bool explores = (uint64_t)(uint32_t)(mix64(k1 ^ EXPLORE_SALT) >> 32) < explore_q32;
+#ifdef DCM_BEST
+            const int action = (explores || policy == DCM_POLICY_RANDOM) ? S.pick_random_action(lane, k1) : S.pick_policy_action(lane, leader, policy, xy);
+#else
             const int action = explores ? S.pick_random_action(lane, k1) : S.pick_policy_action(lane, leader, policy, xy);
+#endif
 #elif defined(DCM_POLICY)
             const int action = S.pick_policy_action(lane, leader, policy, xy);
 #elif defined(DCM_LOG)
@@ -95,7 +101,7 @@ __global__ __launch_bounds__(WAVE, 3) void KNAME(int A, int T, int PA, int PT, K
             const int action = S.pick_random_action(lane, k1);
 #endif
             PH_MARK(2);
-#if defined(DCM_LOG) || defined(DCM_EXPLORE)
+#if defined(DCM_LOG) || defined(KEXPLORES)
             S.template apply_and_advance<true>(h, P, lane, leader, gm, action, k1, -1, nullptr, row PH_PASS, lg, e * BA, false, 0, true, false, &xy);
 #else
             S.template apply_and_advance<true>(h, P, lane, leader, gm, action, k1, -1, nullptr, row PH_PASS, RouteLog{nullptr, nullptr, nullptr, 0}, 0, false, 0, true, false, &xy);
@@ -103,6 +109,11 @@ __global__ __launch_bounds__(WAVE, 3) void KNAME(int A, int T, int PA, int PT, K
             gd += GAMMA;
             left--;
         }
+#ifdef DCM_BEST
+        // a finished episode, its restart (the lg.len zeroing) still to come: keep it if it beats the kept one
+        if ((h.flags & DCM_FLAG_DONE) && !(h.flags & ROLLOUT_ERR))
+            keep_best<false>(best, lg, e, BA, S.A(), row, 0);
+#endif
         if (left == 0) break;
     }
     PH_FLUSH(lane);

@@ -18,8 +18,7 @@
 // k_rollout_fast_g: their shapes take k_ex_rollout_random (plan::form_rollout_kind).
 #pragma once
 
-constexpr uint64_t EXPLORE_SALT = 0xD6E8FEB86659FD93ULL;
-
+// (EXPLORE_SALT: common.hpp, beside the protocol's other constants)
 #define DCM_EXPLORE 1
 #include "k_rollout_forms.inc"
 #undef DCM_EXPLORE

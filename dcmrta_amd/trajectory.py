@@ -29,12 +29,15 @@ def route_lists(task, arrival, length, what="enable_route_log(cap)"):
 
 
 def route_history(env, b=0, log="step"):
-    """log: "step" = the lockstep log (enable_route_log), "rollout" = the persistent launches' (enable_rollout_log)."""
+    """log: "step" = the lockstep log (enable_route_log), "rollout" = the persistent launches' (enable_rollout_log), "best" = the
+    env's kept episode (enable_best_log)."""
     if log == "step":
         return route_lists(*(x[b].cpu().numpy() for x in env.routes()))
     if log == "rollout":
         return route_lists(*(x[b].cpu().numpy() for x in env.rollout_routes()), what="enable_rollout_log(cap)")
-    raise ValueError('log must be "step" or "rollout"')
+    if log == "best":
+        return route_lists(*(x[b].cpu().numpy() for x in env.best_routes()), what="enable_rollout_log(cap)")
+    raise ValueError('log must be "step", "rollout" or "best"')
 
 
 def routes_to_yaml(env, path, b=0, log="step"):
@@ -128,7 +131,15 @@ def trajectories(routes, depot, task_xy, members, feasible, time_start, time_fin
 
 def generate_traj(env, b=0, dt=0.1, log="step"):
     """trajectories() of env b of a BatchedTaskEnv whose route log was enabled before the episode (enable_route_log; log="rollout": an
-    episode played by rollout() with enable_rollout_log)."""
+    episode played by rollout() with enable_rollout_log; log="best": the env's kept episode, enable_best_log).
+    The task state comes from the env's records, which hold the LAST episode: with log="best" the kept episode must be that one
+    (best_episode == episodes - 1, the env DONE), else ValueError -- the best log keeps routes, not records; replay best_plan(b)
+    (load_routes / execute_routes / replay_trajectories) for an earlier one."""
+    if log == "best":
+        kept, played, flags = int(env.best_episode()[b]), int(env.episodes()[b]), int(env.status()["flags"][b])
+        if kept < 0 or kept != played - 1 or not flags & 1:                      # DCM_FLAG_DONE
+            raise ValueError(f"env {b} keeps episode {kept} but its records hold episode {played - 1 if flags & 1 else played}: "
+                             "generate_traj needs the kept episode's final task state; replay best_plan(b) instead")
     ts = {k: v[b].cpu().numpy() for k, v in env.tasks_state().items()}
     mem = env.task_members()[b].cpu().numpy()
     members = [[int(x) for x in row if x >= 0] for row in mem]

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define DCM_ABI_VERSION 5 /* v3: dcm_build_id, dcm_set_visibility, dcm_load_instances validates req on the device; v4: dcm_set_replay_placement; v5: DCM_PARAM_WIDE_MEMBERS; still v5, additions only: dcm_generate_instances, dcm_get_instances, dcm_generator_draws, dcm_set_instance_renewal, dcm_instance_index, DCM_PARAM_RENEW_SIZES, dcm_set_rollout_log */
+#define DCM_ABI_VERSION 5 /* v3: dcm_build_id, dcm_set_visibility, dcm_load_instances validates req on the device; v4: dcm_set_replay_placement; v5: DCM_PARAM_WIDE_MEMBERS; still v5, additions only: dcm_generate_instances, dcm_get_instances, dcm_generator_draws, dcm_set_instance_renewal, dcm_instance_index, DCM_PARAM_RENEW_SIZES, dcm_set_rollout_log, dcm_set_best_log */
 
 typedef struct dcm_env dcm_env; /* opaque */
 
@@ -271,6 +271,32 @@ int dcm_set_route_log(dcm_env *env, int16_t *route_task, double *route_arrival, 
  *     the logging forms of the one-chunk register-resident kernel and of the general one, under all three policies.)
  * Host-side setter. */
 int dcm_set_rollout_log(dcm_env *env, int16_t *route_task, double *route_arrival, int32_t *route_len, int32_t cap);
+
+/* The best episode of every env, kept on the device: with dcm_set_rollout_log set as well, the persistent launches (dcm_rollout_random,
+ * dcm_rollout_policy, dcm_rollout_explore) keep for every env the best episode it has finished since dcm_reset -- across the
+ * episodes of a launch and across launches -- so that ONE launch of B envs x E episodes yields B x E samples and B plans.
+ * best_task[B,A,cap] i16, best_arrival[B,A,cap] f64, best_len[B,A] i32, best_summary[B,8] f64, best_episode[B] i32: caller-owned
+ * device memory that must outlive its use; A and cap are those of the rollout log that is set when a launch runs.  All NULL
+ * disables; some NULL and some not is DCM_ERR_INVALID.
+ *   Candidates: an episode that reaches its end inside one of the three entry points without an error flag -- also one that began in
+ *     an earlier launch or under dcm_step.  An episode the decision budget stops in mid-flight is no candidate until a later launch
+ *     ends it; episodes that dcm_step ends never are.
+ *   Order: a candidate replaces the kept episode if the env keeps none (best_episode == -1), if its n_finished (summary column 1) is
+ *     larger, or if n_finished is equal and its reward (column 0) is larger.  Strict and exact in fp64: on a tie the earliest stays.
+ *   On replacement best_summary[b] becomes the episode's eight dcm_summary values, best_episode[b] its ordinal since dcm_reset (the
+ *     k of dcm_set_return_log), best_len[b, a] the rollout log's length (it may exceed cap), and best_task / best_arrival the rollout
+ *     log's entries [0, min(len, cap)) of every agent row a < the env's own A.  Nothing is defined behind that prefix or in rows
+ *     beyond the env's A.
+ *   dcm_reset sets every best_episode to -1, every best_summary row to NaN and every best_len to 0.
+ *   Invariant: a launch with the best log set returns exactly what the same launch returns with only the rollout log set -- steps,
+ *     records, summaries, the return log, the rollout log (still the last episode), observation stores, status, episode counts.  (It
+ *     runs another kernel form, k_bs_*.)
+ *   Refusals, nothing launched and nothing changed: a launch while the best log is set and the rollout log is not, DCM_ERR_STATE; a
+ *     launch while a renewal stride is set (dcm_set_instance_renewal), DCM_ERR_STATE -- the best of different instances means nothing:
+ *     clear the stride or the best log.  Every refusal the entry point makes anyway stays as it is.
+ * Host-side setter; not part of dcm_clone_state / dcm_restore_state. */
+int dcm_set_best_log(dcm_env *env, int16_t *best_task, double *best_arrival, int32_t *best_len, double *best_summary,
+                     int32_t *best_episode);
 
 /* Optional history of route replay: what execute_by_route leaves for generate_traj / plot_animation (env/task_env.py:375-418,
  * 589-590) -- agent['route'] / ['arrival_time'], task['members'] and task['feasible_assignment'].  When set, dcm_execute_routes

@@ -2,13 +2,17 @@
 """A plan by sampling: play one instance many times under the epsilon-greedy `nearest` policy and keep the best episode.
 
     python tools/sample_plan.py [--agents 20 --tasks 50 --instance-seed 7000 | --golden I] [--envs 4096] [--eps 0.05] [--seed 11]
-                                [--cap 64] [--out plan.yaml]
+                                [--episodes 1] [--cap 64] [--out plan.yaml]
 
 The instance -- generate_instance(agents, tasks, instance_seed), or the I-th of tests/golden/instances_20A50T.npz -- is replicated over
 `envs` envs with seeds env_seed(seed, b).  Every env plays ONE episode of rollout("nearest", explore=eps) with the rollout log set; the
 best env is the one with the largest pair (number of finished tasks, reward = -makespan).  Prints that pair next to the pair of the
 pure `nearest` policy (one env: every episode of it on an instance ends alike) as one JSON line, and writes the best env's routes with
-routes_to_yaml (the file Worker.generate_route writes, which load_routes / execute_routes replay).  Needs a HIP device."""
+routes_to_yaml (the file Worker.generate_route writes, which load_routes / execute_routes replay).
+With --episodes E > 1 every env plays E episodes in the ONE launch -- the decision counter keeps running across restarts, so they
+differ -- with the best log set (enable_best_log): each env keeps its best episode on the device, the best env is picked from
+best_summary, its best_plan is written, and the JSON line also carries `episodes` and the kept episode's ordinal `best_episode`.
+Needs a HIP device."""
 import argparse
 import json
 import os
@@ -33,12 +37,15 @@ def main():
     ap.add_argument("--envs", type=int, default=4096)
     ap.add_argument("--eps", type=float, default=0.05)
     ap.add_argument("--seed", type=int, default=11, help="base of the env seeds env_seed(seed, b)")
+    ap.add_argument("--episodes", type=int, default=1, help="episodes per env in the one launch; > 1 keeps each env's best on the device")
     ap.add_argument("--cap", type=int, default=64, help="entries per agent of the rollout log")
     ap.add_argument("--out", default="plan.yaml")
     ap.add_argument("--device", default="cuda:0")
     args = ap.parse_args()
     if args.envs < 1:
         ap.error("--envs must be >= 1")
+    if args.episodes < 1:
+        ap.error("--episodes must be >= 1")
     if args.golden is not None:
         z = np.load(os.path.join(ROOT, "tests", "golden", "instances_20A50T.npz"))
         if not 0 <= args.golden < len(z["depot"]):
@@ -58,15 +65,21 @@ def main():
 
     env = BatchedTaskEnv(args.envs, A, T, device=args.device).load_instances(*rep(args.envs))
     env.enable_rollout_log(args.cap)
+    many = args.episodes > 1
+    if many:
+        env.enable_best_log()
     env.reset(env_seeds(args.seed, 0, args.envs), observe=False)
-    steps = env.rollout("nearest", episodes=1, write_obs=False, explore=args.eps)
-    sm = env.summary().cpu().numpy()
+    steps = env.rollout("nearest", episodes=args.episodes, write_obs=False, explore=args.eps)
+    sm = (env.best_summary() if many else env.summary()).cpu().numpy()
     best = max(range(args.envs), key=lambda b: pair(sm[b]))
-    routes_to_yaml(env, args.out, best, log="rollout")                          # ValueError if a route is longer than --cap
+    routes_to_yaml(env, args.out, best, log="best" if many else "rollout")      # ValueError if a route is longer than --cap
     s = pair(sm[best])
-    print(json.dumps(dict(instance=source, envs=args.envs, eps=args.eps, explore_q32=explore_q32(args.eps), decisions=int(steps.sum()),
-                          nearest=dict(finished=g[0], reward=g[1]), sampled=dict(finished=s[0], reward=s[1], env=int(best)),
-                          distinct_returns=int(len(set(sm[:, 0].tolist()))), out=args.out)))
+    line = dict(instance=source, envs=args.envs, eps=args.eps, explore_q32=explore_q32(args.eps), decisions=int(steps.sum()),
+                nearest=dict(finished=g[0], reward=g[1]), sampled=dict(finished=s[0], reward=s[1], env=int(best)),
+                distinct_returns=int(len(set(sm[:, 0].tolist()))), out=args.out)
+    if many:
+        line.update(episodes=args.episodes, best_episode=int(env.best_episode()[best]))
+    print(json.dumps(line))
 
 
 if __name__ == "__main__":
