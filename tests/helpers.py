@@ -47,6 +47,16 @@ def host_random_action(mask_row, seed_e, d):
     return int(valid[below(draw(seed_e, d, 1), len(valid))])
 
 
+def sized_env(gpu_device, A, T, inst, sizes=None, **kw):
+    """A handle with the batch loaded; sizes = (a, t): every env plays its first a agents and t tasks (a ragged batch of equal sizes)."""
+    from dcmrta_amd.batched_env import BatchedTaskEnv
+    B = len(inst["depot"])
+    env = BatchedTaskEnv(B, A, T, device=gpu_device, **kw)
+    if sizes:
+        return env.load_instances(**inst, n_agents=np.full(B, sizes[0], np.int32), n_tasks=np.full(B, sizes[1], np.int32))
+    return env.load_instances(**inst)
+
+
 def run_lockstep(env, seeds, policy, inject=None, max_iters=100000):
     """Drive a BatchedTaskEnv step by step (fused observe) and record per-env traces.
 

@@ -5,6 +5,7 @@ import pytest
 import torch
 
 import helpers as H
+from fixtures_ref import anymask_action
 
 pytestmark = pytest.mark.gpu
 
@@ -442,18 +443,6 @@ def test_requirements_are_validated_on_the_device(gpu_device):
     assert not (env.status()["flags"].cpu().numpy() & _lib.FLAG_BAD_INSTANCE).any()
 
 
-def _anymask_action(mask_row, seed_e, d, T):
-    """Host mirror of ORC_POLICY_ANY / tests/golden/make_golden_masked.py: a policy that does not respect the mask."""
-    from dcmrta_amd.choice import below, draw
-    r = draw(seed_e, d, 1)
-    if r % 16 == 1:
-        return 0
-    if r % 4 == 0:
-        return 1 + (r >> 4) % T
-    valid = np.flatnonzero(mask_row == 0)
-    return int(valid[below(r, len(valid))])
-
-
 def test_masked_actions_are_simulated(gpu_device, oracle_lib, golden_dir):
     """TaskEnv.step has no mask check (env/task_env.py:326-342): an action on a feasible / full / stale-status task sends the
     leader alone, the task lists a surplus member, an agent that joins a task that is already over is released in the past
@@ -471,7 +460,7 @@ def test_masked_actions_are_simulated(gpu_device, oracle_lib, golden_dir):
     inst = generate_batch(B, A, T, base_seed=400)
     seeds = env_seeds(13, 0, B)
     env = BatchedTaskEnv(B, A, T, device=gpu_device).load_instances(**inst)
-    got = H.run_lockstep(env, seeds, lambda b, i, m, l: _anymask_action(m, int(seeds[b]), i, T))
+    got = H.run_lockstep(env, seeds, lambda b, i, m, l: anymask_action(m, int(seeds[b]), i, T))
     fin = H.gpu_final(env)
     n_exact = n_over = masked = backwards = 0
     for b in range(B):

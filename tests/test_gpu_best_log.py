@@ -9,7 +9,8 @@ well.  Every comparison is exact."""
 import numpy as np
 import pytest
 
-from test_gpu_explore import ALL_FORMS, _assert_same, _form_instances, _snap
+import oracle_ref as O
+from forms import Forms, assert_same, snap
 
 pytestmark = pytest.mark.gpu
 
@@ -19,10 +20,19 @@ Q30 = 1 << 30
 ERR_FLAGS = 0x38 | 0x40                                                         # bad action, overflow, bad leader, bad instance
 PLAYS = {"random": ("random", None), "nearest": ("nearest", None), "nearest-q30": ("nearest", Q30)}
 
-
-def _shared():
-    import test_gpu_rollout_log as L
-    return L
+# id: (A, T, B, BatchedTaskEnv keywords, ragged ranges, scalar budget of every launch) -- the entries and base seeds of
+# test_gpu_explore.py, so the two files share the cached instances and oracle runs (forms.py caches by value)
+FORMS = {
+    "F1": (20, 50, 6, {}, None, -1),                                            # fast, exact
+    "F2": (20, 50, 6, {}, ((10, 20), (20, 50)), -1),                            # fast, runtime sizes (a ragged batch)
+    "F3": (30, 60, 4, {}, None, -1),                                            # fast, Lay{64,64}
+    "F4": (10, 64, 4, {}, None, -1),                                            # general: no free depot lane
+    "F5": (66, 70, 4, {}, None, -1),                                            # general, the mid-size layout
+    "F6": (10, 20, 4, dict(max_waiting_time=0.0), None, 60),                    # general, the literal rule; every launch under a budget
+}
+BIG_FORMS = {"F7-above-64KiB": (4, 700, 2, {}, None, -1)}                       # record_bytes > 64 KiB: the raised dynamic-LDS limit
+ALL_FORMS = {**FORMS, **BIG_FORMS}
+F = Forms(FORMS, BIG_FORMS, 6000, 6100, 41)
 
 
 def _play(env, play, episodes, budget=None):
@@ -34,10 +44,7 @@ def _play(env, play, episodes, budget=None):
 
 
 def _env(gpu_device, form, best, cap=CAP):
-    from dcmrta_amd.batched_env import BatchedTaskEnv
-    A, T, B, kw, _, _ = ALL_FORMS[form]
-    inst, seeds = _form_instances(form)
-    env = BatchedTaskEnv(B, A, T, device=gpu_device, **kw).load_instances(**inst)
+    env, seeds = F.env(gpu_device, form)
     env.enable_rollout_log(cap)
     if best:
         env.enable_best_log()
@@ -113,26 +120,8 @@ def _assert_best(got, kept, sizes, tag):
 
 def _sizes(form):
     A, _, B, _, ranges, _ = ALL_FORMS[form]
-    inst, _ = _form_instances(form)
+    inst, _ = F.instances(form)
     return [A] * B if ranges is None else [int(x) for x in inst["n_agents"]]
-
-
-def _oracle_episodes(form, policy, episodes):
-    """The oracle's episodes 0 .. episodes-1 of every env of a form under a pinned policy: [b][k] = an object with .o and .a."""
-    L = _shared()
-    A, T, B, kw, ranges, _ = ALL_FORMS[form]
-    inst, seeds = _form_instances(form)
-    out = []
-    for b in range(B):
-        a, t = (A, T) if ranges is None else (int(inst["n_agents"][b]), int(inst["n_tasks"][b]))
-        s = L._Sim(a, t, lambda j, one=L._one(inst, b, t): one, seeds[b], policy, kw.get("max_waiting_time", 10.0))
-        eps = []
-        for _ in range(episodes):
-            s.launch(1, -1)
-            assert s.done
-            eps.append(type("Episode", (), dict(o=s.o, a=a))())
-        out.append(eps)
-    return out
 
 
 # ---------------------------------------------------------------------------------------------------- 1. + 2. the chain, not vacuous
@@ -161,15 +150,14 @@ def test_one_launch_keeps_what_the_chain_of_one_episode_launches_keeps(gpu_devic
     if play == "random":
         assert eps.tolist() == KEPT_RANDOM[form], (tag, eps)
     if play in ("random", "nearest"):                                           # ... and the kept lists are the oracle's
-        L = _shared()
-        orc = _oracle_episodes(form, play, episodes)
+        orc = F.episodes(form, play, episodes)
         log = (got["task"], got["arrival"], got["len"])
         for b in range(env.B):
             fin = [e.o.final() for e in orc[b]]
             order = [(int(f["finished"].sum()), f["reward"]) for f in fin]
             assert int(eps[b]) == max(range(episodes), key=lambda i: (order[i], -i)), (tag, b, order)   # the earliest of the best
             assert (got["summary"][b, 1], got["summary"][b, 0]) == order[int(eps[b])], (tag, b)
-            L._assert_log(log, b, orc[b][int(eps[b])], tag)
+            O.assert_log(log, b, orc[b][int(eps[b])], tag)
 
 
 # ---------------------------------------------------------------------------------------------------- 3. the invariant
@@ -177,10 +165,10 @@ def test_one_launch_keeps_what_the_chain_of_one_episode_launches_keeps(gpu_devic
 @pytest.mark.parametrize("form", ["F1", "F4", "F5", "F7-above-64KiB"])
 def test_a_launch_with_the_best_log_returns_what_it_returns_with_the_rollout_log_alone(gpu_device, form, play):
     twin = _env(gpu_device, form, False)
-    ref = _snap(twin, _play(twin, play, E))
+    ref = snap(twin, _play(twin, play, E))
     env = _env(gpu_device, form, True)
-    got = _snap(env, _play(env, play, E))
-    _assert_same(got, ref, f"{form} {play}")
+    got = snap(env, _play(env, play, E))
+    assert_same(got, ref, f"{form} {play}")
     assert (env.best_episode().cpu().numpy() >= 0).all()
 
 
@@ -191,7 +179,7 @@ def test_budget_stops_keep_nothing_and_later_launches_carry_on(gpu_device, form,
     tag = f"{form} {play}"
     B = ALL_FORMS[form][2]
     whole = _env(gpu_device, form, True)
-    ref = _snap(whole, _play(whole, play, E))
+    ref = snap(whole, _play(whole, play, E))
     ref_best = _best(whole)
     kept = [dict(summary=ref_best["summary"][b], episode=int(ref_best["episode"][b]), len=ref_best["len"][b], task=ref_best["task"][b],
                  arrival=ref_best["arrival"][b]) for b in range(B)]
@@ -202,7 +190,7 @@ def test_budget_stops_keep_nothing_and_later_launches_carry_on(gpu_device, form,
     assert np.array_equal(first, budgets) and not (env.status()["flags"].cpu().numpy() & 1).any()
     _assert_best(_best(env), [None] * B, _sizes(form), tag + " stopped")
     second = _play(env, play, E)
-    _assert_same(_snap(env, first + second), ref, tag + " continued")
+    assert_same(snap(env, first + second), ref, tag + " continued")
     _assert_best(_best(env), kept, _sizes(form), tag + " continued")
     # two launches of two episodes
     env = _env(gpu_device, form, True)
@@ -210,10 +198,10 @@ def test_budget_stops_keep_nothing_and_later_launches_carry_on(gpu_device, form,
     half = _best(env)
     assert (half["episode"] >= 0).all() and (half["episode"] <= 1).all()
     steps = steps + _play(env, play, 2)
-    _assert_same(_snap(env, steps), ref, tag + " 2 + 2")
+    assert_same(snap(env, steps), ref, tag + " 2 + 2")
     _assert_best(_best(env), kept, _sizes(form), tag + " 2 + 2")
     # reset() forgets
-    env.reset(_form_instances(form)[1], observe=False)
+    env.reset(F.instances(form)[1], observe=False)
     cleared = _best(env)
     assert (cleared["episode"] == -1).all() and np.isnan(cleared["summary"]).all() and (cleared["len"] == 0).all()
 
@@ -230,7 +218,7 @@ def test_on_the_literal_rule_a_budgeted_launch_keeps_nothing_or_what_the_chain_k
     print("F6", play, total, "kept episodes", got["episode"].tolist(), "steps", steps.tolist())
     assert np.array_equal(steps, taken)
     _assert_best(got, kept, _sizes("F6"), f"F6 {play}")
-    _assert_same(_snap(env, steps), _snap(twin, taken), f"F6 {play}")
+    assert_same(snap(env, steps), snap(twin, taken), f"F6 {play}")
 
 
 # ---------------------------------------------------------------------------------------------------- 5. a small cap
@@ -305,7 +293,7 @@ def test_refusals_launch_nothing_and_change_nothing(gpu_device):
         env.enable_best_log(False).best_routes()
     # episodes that dcm_step ends are no candidates
     env = _env(gpu_device, "F1", True)
-    seeds = _form_instances("F1")[1]
+    seeds = F.instances("F1")[1]
     H.run_lockstep(env, seeds, lambda b, i, m, l: H.host_random_action(m, int(seeds[b]), i))
     assert (env.episodes().cpu().numpy() >= 1).all()
     got = _best(env)
@@ -316,7 +304,7 @@ def test_the_rollout_logs_cap_takes_the_best_log_with_it(gpu_device):
     env = _env(gpu_device, "F1", True)
     env.enable_rollout_log(16)
     assert env.best_routes()[0].shape == (6, 20, 16) and env.rollout_routes()[0].shape == (6, 20, 16)
-    env.reset(_form_instances("F1")[1], observe=False)
+    env.reset(F.instances("F1")[1], observe=False)
     _play(env, "random", 2)
     assert (env.best_episode().cpu().numpy() >= 0).all()
     env.enable_rollout_log(0)

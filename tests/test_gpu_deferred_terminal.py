@@ -6,20 +6,9 @@ import pytest
 import torch
 
 import helpers as H
+import oracle_ref as O
 
 pytestmark = pytest.mark.gpu
-
-
-def _oracle_episodes(oracle_lib, inst, seeds, A, T, b, n):
-    """The first n consecutive episodes of env b under the random policy (the decision counter keeps running)."""
-    out, d0 = [], 0
-    o = oracle_lib.OracleEnv(A, T).load(inst["depot"][b], inst["task_xy"][b], inst["req"][b], inst["dur"][b])
-    for _ in range(n):
-        r = o.rollout(int(seeds[b]), d0, oracle_lib.POLICY_RANDOM, cap_steps=20000, record=False)
-        out.append(r)
-        d0 += r["n_steps"]
-        o.clear_decisions()
-    return out
 
 
 @pytest.mark.parametrize("A,T,B,steps", [(20, 50, 96, 700), (12, 23, 64, 500), (64, 63, 16, 900)])
@@ -47,13 +36,10 @@ def test_summaries_read_rarely_match_the_oracle(gpu_device, oracle_lib, A, T, B,
     rl = ring.cpu().numpy()
     assert eps.min() >= 2 and eps.max() <= cap
     for b in range(B):
-        ref = _oracle_episodes(oracle_lib, inst, seeds, A, T, b, int(eps[b]))
+        ref = O.episodes(A, T, O.one(inst, b), seeds[b], "random", int(eps[b]))
         for k, r in enumerate(ref):
             assert rl[b, k] == r["reward"], (b, k)
-        last = ref[-1]
-        assert sm[b, 0] == last["reward"] and int(sm[b, 1]) == int(last["finished"].sum()), b
-        for i in range(6):
-            assert sm[b, 2 + i] == last["metrics"][i], (b, i)
+        O.assert_summary(sm[b], ref[-1], f"env{b}")
         assert sum(r["n_steps"] for r in ref) <= dcount[b]
 
 
@@ -69,7 +55,7 @@ def test_an_env_that_ends_again_before_the_flush(gpu_device, oracle_lib):
     env = BatchedTaskEnv(B, A, T, device=gpu_device, auto_reset=True).load_instances(**inst)
     obs = env.reset(seeds)
     dcount = np.zeros(B, np.int64)
-    refs = [_oracle_episodes(oracle_lib, inst, seeds, A, T, b, 80) for b in range(B)]
+    refs = [O.episodes(A, T, O.one(inst, b), seeds[b], "random", 80) for b in range(B)]
     bounds = [np.cumsum([r["n_steps"] for r in refs[b]]) for b in range(B)]
     for s in range(150):
         mk = obs.mask.cpu().numpy().astype(np.uint8)
@@ -169,7 +155,7 @@ def test_restart_image_follows_reloads_and_restores(gpu_device, oracle_lib):
         rl = ring.cpu().numpy()
         assert eps.min() >= 2 and eps.max() <= 64
         for b in range(B):
-            ref = _oracle_episodes(oracle_lib, inst, seeds, A, T, b, int(eps[b]))
+            ref = O.episodes(A, T, O.one(inst, b), seeds[b], "random", int(eps[b]))
             for k, r in enumerate(ref):
                 assert rl[b, k] == r["reward"], (b, k)
             for i in range(6):

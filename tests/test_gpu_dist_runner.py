@@ -32,7 +32,7 @@ def test_two_rank_sharded_training_rounds(gpu_device, oracle_lib, tmp_path):
     from dcmrta_amd.instances import generate_batch
     from dcmrta_amd.policy import AttentionNet
     from dcmrta_amd.runner import BatchedRunner
-    from test_gpu_runner import _replay_recorded
+    from fixtures_ref import replay_recorded
     lines = _launch(tmp_path, 29581)
     assert len(lines) == 2 and all(l["decisions"] > 13 * 5 for l in lines)
     logs = [json.load(open(tmp_path / f"log_rank{r}.json")) for r in range(2)]
@@ -53,7 +53,7 @@ def test_two_rank_sharded_training_rounds(gpu_device, oracle_lib, tmp_path):
             inst = generate_batch(hi - lo, A, T, base_seed=7, first=first)
             seeds = env_seeds(7, first, hi - lo)
             rec = {k: torch.from_numpy(d[r][k]) for k in ("agents", "tasks", "mask", "action", "leader", "active")}
-            _replay_recorded(oracle_lib, rec, d[r]["summary"], inst, seeds, A, T)
+            replay_recorded(oracle_lib, rec, d[r]["summary"], inst, seeds, A, T)
         if rnd == 0:
             # the unsharded job with rank 0's initial weights: same instances, same greedy twins (deterministic argmax rollouts)
             torch.manual_seed(1234)

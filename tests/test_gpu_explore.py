@@ -5,10 +5,11 @@ the rollout log set and without it.
 Yardsticks: explore_q32 = 0 is the greedy launch and explore_q32 = 2^32 the random one, byte for byte, and both are the oracle's; every
 value in between is a chain of one-decision greedy / random launches chosen on the host by choice.explores -- existing, oracle-pinned
 entry points only; and four known answers computed on the CPU from the definition.  Every comparison is exact."""
-import functools
-
 import numpy as np
 import pytest
+
+import oracle_ref as O
+from forms import Forms, assert_same, snap
 
 pytestmark = pytest.mark.gpu
 
@@ -29,66 +30,16 @@ FORMS = {
 # ... and one whose launches need the raised dynamic-LDS limit (record_bytes > 64 KiB): the two ends only
 BIG_FORMS = {"F7-above-64KiB": (4, 700, 2, {}, None, -1)}
 ALL_FORMS = {**FORMS, **BIG_FORMS}
-
-
-def _shared():
-    import test_gpu_rollout_log as L
-    return L
-
-
-@functools.lru_cache(maxsize=None)
-def _form_instances(form):
-    from dcmrta_amd.choice import env_seeds
-    from dcmrta_amd.instances import generate_batch, generate_batch_ranges
-    A, T, B, _, ranges, _ = ALL_FORMS[form]
-    inst = generate_batch(B, A, T, base_seed=6000 + 3 * A + T) if ranges is None else generate_batch_ranges(range(6100, 6100 + B), *ranges)
-    return inst, env_seeds(41, 0, B)
-
-
-@functools.lru_cache(maxsize=None)
-def _form_sims(form, policy, episodes):
-    """The oracle's side of one launch of `episodes` episodes on a form under one of the three pinned policies: computed once, shared."""
-    L = _shared()
-    A, T, B, kw, ranges, budget = ALL_FORMS[form]
-    inst, seeds = _form_instances(form)
-    sims, steps = [], []
-    for b in range(B):
-        a, t = (A, T) if ranges is None else (int(inst["n_agents"][b]), int(inst["n_tasks"][b]))
-        s = L._Sim(a, t, lambda j, one=L._one(inst, b, t): one, seeds[b], policy, kw.get("max_waiting_time", 10.0))
-        steps.append(s.launch(episodes, budget))
-        sims.append(s)
-    return sims, np.array(steps, np.int64)
+F = Forms(FORMS, BIG_FORMS, 6000, 6100, 41)                                     # base seeds: uniform instances, ragged ones, choice
 
 
 def _form_env(gpu_device, form, logged=True, ring=2):
-    from dcmrta_amd.batched_env import BatchedTaskEnv
-    A, T, B, kw, _, _ = ALL_FORMS[form]
-    inst, seeds = _form_instances(form)
-    env = BatchedTaskEnv(B, A, T, device=gpu_device, **kw).load_instances(**inst)
-    assert (env.record_bytes() > 65536) == (form in BIG_FORMS)
+    env, seeds = F.env(gpu_device, form)
     if logged:
         env.enable_rollout_log(CAP)
     env._ring = env.enable_return_log(ring)
     env.reset(seeds, observe=False)
     return env, seeds
-
-
-def _snap(env, steps):
-    """Everything a launch leaves: steps, records, summary rows, the return log, status, episode counts, the observation buffers and --
-    if it is set -- the rollout log.  As bytes."""
-    o = env.obs()
-    st = env.status()
-    parts = dict(steps=steps, state=env.clone_state(), summary=env.summary(), ring=env._ring, flags=st["flags"], decisions=st["decisions"],
-                 now=st["now"], episodes=env.episodes(), agents=o.agents, tasks=o.tasks, mask=o.mask)
-    if getattr(env, "_rollout_route", None) is not None:
-        parts.update(zip(("log_task", "log_arrival", "log_len"), env.rollout_routes()))
-    return {k: np.ascontiguousarray((v if isinstance(v, np.ndarray) else v.cpu().numpy())).copy() for k, v in parts.items()}
-
-
-def _assert_same(got, ref, tag):
-    assert sorted(got) == sorted(ref), tag
-    for k in ref:
-        assert got[k].dtype == ref[k].dtype and got[k].shape == ref[k].shape and got[k].tobytes() == ref[k].tobytes(), f"{tag}: {k}"
 
 
 # ---------------------------------------------------------------------------------------------------- 1. + 2. the two ends
@@ -98,16 +49,15 @@ def _assert_same(got, ref, tag):
 def test_the_ends_are_the_greedy_and_the_random_policy(gpu_device, form, base, logged):
     """explore_q32 = 0 against rollout(base), explore_q32 = 2^32 against rollout("random"), each on a twin handle, two episodes: byte for
     byte; and the twin's launch is the oracle's (steps, the last episode's reward, the logged lists)."""
-    L = _shared()
     budget = ALL_FORMS[form][5]
     for q32, pinned in ((0, base), (Q_ALL, "random")):
         tag = f"{form} {base} q={q32} {'log' if logged else 'nolog'}"
         twin, _ = _form_env(gpu_device, form, logged)
-        ref = _snap(twin, twin.rollout(pinned, episodes=2, max_decisions=budget).cpu().numpy())
+        ref = snap(twin, twin.rollout(pinned, episodes=2, max_decisions=budget).cpu().numpy())
         env, _ = _form_env(gpu_device, form, logged)
-        got = _snap(env, env.rollout(base, episodes=2, max_decisions=budget, explore_q32=q32).cpu().numpy())
-        _assert_same(got, ref, tag)
-        sims, ref_steps = _form_sims(form, pinned, 2)
+        got = snap(env, env.rollout(base, episodes=2, max_decisions=budget, explore_q32=q32).cpu().numpy())
+        assert_same(got, ref, tag)
+        sims, ref_steps = F.sims(form, pinned, 2)
         assert np.array_equal(got["steps"], ref_steps), tag
         for b, s in enumerate(sims):
             if s.done:
@@ -115,9 +65,9 @@ def test_the_ends_are_the_greedy_and_the_random_policy(gpu_device, form, base, l
             else:
                 assert budget >= 0 and not got["flags"][b] & 1, (tag, b)
         if logged:
-            log = L._log(env)
+            log = O.log(env)
             for b, s in enumerate(sims):
-                L._assert_log(log, b, s, tag)
+                O.assert_log(log, b, s, tag)
 
 
 # ---------------------------------------------------------------------------------------------------- 3. in between: the chain
@@ -160,10 +110,10 @@ def test_a_launch_is_the_chain_of_pinned_one_decision_launches(gpu_device, form,
     twin, seeds = _form_env(gpu_device, form)
     taken, n_ex, n_gr = _chain(twin, seeds, base, q32, 2, budget)
     assert ((n_ex > 0) & (n_gr > 0)).any(), (n_ex, n_gr)                        # some env both explored and did not: not vacuous
-    ref = _snap(twin, taken)
+    ref = snap(twin, taken)
     env, _ = _form_env(gpu_device, form)
-    got = _snap(env, env.rollout(base, episodes=2, max_decisions=budget, explore_q32=q32).cpu().numpy())
-    _assert_same(got, ref, f"{form} {base} q={q32}")
+    got = snap(env, env.rollout(base, episodes=2, max_decisions=budget, explore_q32=q32).cpu().numpy())
+    assert_same(got, ref, f"{form} {base} q={q32}")
 
 
 # ---------------------------------------------------------------------------------------------------- 4. budget stop and continuation
@@ -173,14 +123,14 @@ def test_a_budget_stop_in_mid_episode_and_a_second_launch_equal_the_uninterrupte
     q32 = 1 << 30
     B = FORMS[form][2]
     whole, _ = _form_env(gpu_device, form)
-    ref = _snap(whole, whole.rollout(base, episodes=2, explore_q32=q32).cpu().numpy())
+    ref = snap(whole, whole.rollout(base, episodes=2, explore_q32=q32).cpu().numpy())
     budgets = np.array([0, 1, 7, 23, 2, 30][:B], np.int64)                      # all inside the first episode (checked below)
     env, _ = _form_env(gpu_device, form)
     first = env.rollout(base, episodes=2, max_decisions=budgets, explore_q32=q32).cpu().numpy()
     assert np.array_equal(first, budgets) and not (env.status()["flags"].cpu().numpy() & 1).any()
     second = env.rollout(base, episodes=2, explore_q32=q32).cpu().numpy()
     assert (second > 0).all()
-    _assert_same(_snap(env, first + second), ref, f"{form} {base}")
+    assert_same(snap(env, first + second), ref, f"{form} {base}")
 
 
 # ---------------------------------------------------------------------------------------------------- 5. instance renewal
@@ -203,10 +153,10 @@ def test_three_episodes_under_instance_renewal_play_instances_0_1_2(gpu_device, 
     twin = make()
     taken, n_ex, n_gr = _chain(twin, seeds, "nearest", q32, 3, -1)
     assert ((n_ex > 0) & (n_gr > 0)).any()
-    ref = _snap(twin, taken)
+    ref = snap(twin, taken)
     env = make()
-    got = _snap(env, env.rollout("nearest", episodes=3, explore_q32=q32).cpu().numpy())
-    _assert_same(got, ref, f"renewal {A}A{T}T")
+    got = snap(env, env.rollout("nearest", episodes=3, explore_q32=q32).cpu().numpy())
+    assert_same(got, ref, f"renewal {A}A{T}T")
     assert (env.instance_index().cpu().numpy() == 2).all() and (twin.instance_index().cpu().numpy() == 2).all()
     held = {k: v.cpu().numpy() for k, v in env.instances().items() if v is not None}
     for b in range(B):

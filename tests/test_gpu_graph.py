@@ -4,13 +4,10 @@ import numpy as np
 import pytest
 import torch
 
-from test_gpu_runner import _replay_recorded
+from fixtures_ref import replay_recorded
+from renewal_ref import first_valid
 
 pytestmark = pytest.mark.gpu
-
-
-def first_valid(obs):
-    return torch.argmax((~obs.mask).to(torch.int32), dim=1)   # lowest unmasked action id
 
 
 def test_graph_replay_matches_oracle(gpu_device, oracle_lib):
@@ -26,21 +23,21 @@ def test_graph_replay_matches_oracle(gpu_device, oracle_lib):
     summary, n = g.run(seeds)
     rec = {k: v[:n] for k, v in g.rec.items()}
     assert int(rec["active"].sum()) == int(env.status()["decisions"].sum())
-    _replay_recorded(oracle_lib, rec, summary.cpu().numpy(), inst, seeds, A, T)
+    replay_recorded(oracle_lib, rec, summary.cpu().numpy(), inst, seeds, A, T)
     # the captured graph is reusable: other instances and seeds, same graph object
     inst2, seeds2 = generate_batch(B, A, T, base_seed=99), env_seeds(5, 0, B)
     env.load_instances(**inst2)
     graph_before = g.graph
     summary2, n2 = g.run(seeds2)
     assert g.graph is graph_before
-    _replay_recorded(oracle_lib, {k: v[:n2] for k, v in g.rec.items()}, summary2.cpu().numpy(), inst2, seeds2, A, T)
+    replay_recorded(oracle_lib, {k: v[:n2] for k, v in g.rec.items()}, summary2.cpu().numpy(), inst2, seeds2, A, T)
     # switching the handle to a ragged batch changes what the captured dcm_step has baked in (per-env sizes pointer, kernel
     # instantiation): the rollout must re-capture instead of replaying a stale graph
     rag = generate_batch_ranges(range(700, 700 + B), (10, 20), (20, 50))
     env.load_instances(**rag)
     summary3, n3 = g.run(seeds)
     assert g.graph is not graph_before
-    _replay_recorded(oracle_lib, {k: v[:n3] for k, v in g.rec.items()}, summary3.cpu().numpy(), rag, seeds, A, T,
+    replay_recorded(oracle_lib, {k: v[:n3] for k, v in g.rec.items()}, summary3.cpu().numpy(), rag, seeds, A, T,
                      n_agents=rag["n_agents"], n_tasks=rag["n_tasks"])
     # ... and back to uniform
     env.load_instances(**inst)
@@ -73,7 +70,7 @@ def test_compacted_policy_buckets_match_oracle(gpu_device, oracle_lib):
         assert torch.equal(rec[k][act], rec_full[k][act]), k
     assert torch.equal(rec["action"][act], rec_full["action"][act])
     assert g.bucket_steps[B] > 0 and sum(v for n, v in g.bucket_steps.items() if n < B) > 0, g.bucket_steps
-    _replay_recorded(oracle_lib, rec, s_b.cpu().numpy(), inst, seeds, A, T, n_agents=inst["n_agents"], n_tasks=inst["n_tasks"])
+    replay_recorded(oracle_lib, rec, s_b.cpu().numpy(), inst, seeds, A, T, n_agents=inst["n_agents"], n_tasks=inst["n_tasks"])
     # with auto-reset and an episode limit the active set also only shrinks: 2 episodes per env, compacted
     env2 = BatchedTaskEnv(B, A, T, device=gpu_device, auto_reset=True, auto_reset_episodes=2).load_instances(**inst)
     g2 = GraphedRollout(env2, first_valid, check_every=4, buckets=(1.0, 0.5, 0.25))
@@ -129,5 +126,5 @@ def test_attention_policy_graph_loop_at_full_batch(gpu_device, oracle_lib):
     pick = np.linspace(0, B - 1, 32).astype(int)
     rec = {k: v[:n][:, pick].contiguous() for k, v in g.rec.items()}
     sub = {k: v[pick] for k, v in inst.items()}
-    _replay_recorded(oracle_lib, rec, summary[pick].cpu().numpy(), sub, seeds[pick], A, T)
+    replay_recorded(oracle_lib, rec, summary[pick].cpu().numpy(), sub, seeds[pick], A, T)
     assert not rec["mask"].gather(2, rec["action"].unsqueeze(2))[rec["active"]].any()     # no sampled action was masked

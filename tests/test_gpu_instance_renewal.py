@@ -1,106 +1,23 @@
 """-m gpu: instance renewal (dcm_set_instance_renewal) -- an env that restarts an episode inside a kernel first draws its next
 instance, seed inst_seeds[e] + (n + 1) * stride, the way every reference Worker builds a new TaskEnv(..., seed=...) (worker.py:32).
 
-The yardstick is the oracle, driven as test_gpu_deferred_terminal._oracle_episodes drives it, with a new host instance per episode:
+The yardstick is the oracle (renewal_ref.oracle_chain, on oracle_ref.episodes), with a new host instance per episode:
 episode k of an env loads generate_instance(A, T, seed + k * stride) and runs rollout(choice_seed, d0, POLICY_RANDOM) with the running
 decision counter d0, which keeps running across instances.  Every comparison is array_equal."""
-import functools
-
 import numpy as np
 import pytest
 import torch
 
 import helpers as H
+import oracle_ref as O
+import renewal_ref as R
+from renewal_ref import EPISODES, M64
 
 pytestmark = pytest.mark.gpu
 
-M64 = 1 << 64
 GAMMA = 0x9E3779B97F4A7C15
-EPISODES = 3
 ERR_STATE = -4
 WRAP_STRIDE = (1 << 63) + 12345          # two of them pass 2^64
-
-
-def _inst_seeds(base, B):
-    return np.array([(base + b) % M64 for b in range(B)], dtype=np.uint64)
-
-
-def _host_instance(A, T, seed, mcs):
-    from dcmrta_amd.instances import generate_instance
-    return generate_instance(A, T, int(seed), max_coalition_size=mcs)
-
-
-@functools.lru_cache(maxsize=None)
-def _oracle_chain(A, T, inst_seed, stride, choice_seed, mcs=5, n=EPISODES):
-    """Episodes 0..n-1 of one env under renewal: (rollout results, instances), computed once per env and shared by the tests."""
-    import oracle
-    from dcmrta_amd.instances import renewal_seeds
-    oracle.build()
-    eps, insts, d0 = [], [], 0
-    for k in range(n):
-        inst = _host_instance(A, T, renewal_seeds(inst_seed, k, stride), mcs)
-        r = oracle.OracleEnv(A, T).load(inst["depot"], inst["task_xy"], inst["req"], inst["dur"]) \
-            .rollout(int(choice_seed), d0, oracle.POLICY_RANDOM, cap_steps=20000, record=False)
-        eps.append(dict(n_steps=r["n_steps"], row=np.array([r["reward"], float(r["finished"].sum()), *r["metrics"][:6]], np.float64)))
-        insts.append(inst)
-        d0 += r["n_steps"]
-    return eps, insts
-
-
-@functools.lru_cache(maxsize=None)
-def _oracle_chain_on(A, T, inst_seed, stride, choice_seed, indices, mcs=5):
-    """As _oracle_chain, but episode k plays the instance of index indices[k] (an env whose renewal was turned off on the way)."""
-    import oracle
-    from dcmrta_amd.instances import renewal_seeds
-    oracle.build()
-    eps, insts, d0 = [], [], 0
-    for n in indices:
-        inst = _host_instance(A, T, renewal_seeds(inst_seed, n, stride), mcs)
-        r = oracle.OracleEnv(A, T).load(inst["depot"], inst["task_xy"], inst["req"], inst["dur"]) \
-            .rollout(int(choice_seed), d0, oracle.POLICY_RANDOM, cap_steps=20000, record=False)
-        eps.append(dict(n_steps=r["n_steps"], row=np.array([r["reward"], float(r["finished"].sum()), *r["metrics"][:6]], np.float64)))
-        insts.append(inst)
-        d0 += r["n_steps"]
-    return eps, insts
-
-
-def _make(gpu_device, B, A, T, base, stride, mcs=5, member_cap=5, **kw):
-    """A handle with generated instances base + 0..B-1, renewal on, a return log of EPISODES columns; not reset yet."""
-    from dcmrta_amd.batched_env import BatchedTaskEnv
-    env = BatchedTaskEnv(B, A, T, device=gpu_device, member_cap=member_cap, **kw)
-    env.generate_instances(_inst_seeds(base, B), max_coalition_size=mcs)
-    env.set_instance_renewal(stride)
-    ring = env.enable_return_log(EPISODES)
-    return env, ring
-
-
-def _held(env):
-    return {k: v.cpu().numpy() for k, v in env.instances().items() if v is not None}
-
-
-def _assert_instance(held, b, inst):
-    assert np.array_equal(held["depot"][b], inst["depot"]), b
-    assert np.array_equal(held["task_xy"][b], inst["task_xy"]), b
-    assert np.array_equal(held["req"][b], inst["req"]), b
-    assert np.array_equal(held["dur"][b], inst["dur"]), b
-
-
-def _assert_after_three(env, ring, chains, rows, steps=None):
-    """What every path must leave after three episodes: the three returns, the last episode's summary row, index 2, instance 2."""
-    sm, rl, idx, held = env.summary().cpu().numpy(), ring.cpu().numpy(), env.instance_index().cpu().numpy(), _held(env)
-    assert np.array_equal(env.episodes().cpu().numpy()[rows], np.full(len(rows), EPISODES))
-    for b in rows:
-        eps, insts = chains[b]
-        assert np.array_equal(rl[b], np.array([e["row"][0] for e in eps])), b
-        assert np.array_equal(sm[b], eps[-1]["row"], equal_nan=True), b
-        assert idx[b] == EPISODES - 1, (b, idx[b])
-        _assert_instance(held, b, insts[-1])
-        if steps is not None:
-            assert steps[b] == sum(e["n_steps"] for e in eps), b
-
-
-def _chains(A, T, B, base, stride, choice_seeds, mcs=5, rows=None):
-    return {b: _oracle_chain(A, T, (base + b) % M64, stride, int(choice_seeds[b]), mcs) for b in (range(B) if rows is None else rows)}
 
 
 # shape, batch, member_cap / max_coalition_size, stride (None = B), base seed: one case per kernel class of dcm_rollout_random
@@ -121,12 +38,12 @@ def test_persistent_rollout_plays_a_new_instance_every_episode(gpu_device, A, T,
     from dcmrta_amd.choice import env_seeds
     stride = B if stride is None else stride
     seeds = env_seeds(51, 0, B)
-    env, ring = _make(gpu_device, B, A, T, base, stride, mcs, member_cap)
+    env, ring = R.make(gpu_device, B, A, T, base, stride, mcs, member_cap)
     if T == 700:
         assert env.record_bytes() > 65536
     env.reset(seeds, observe=False)
     steps = env.rollout_random(episodes=EPISODES).cpu().numpy()
-    _assert_after_three(env, ring, _chains(A, T, B, base, stride, seeds, mcs), range(B), steps)
+    R.assert_after(env, ring, R.chains(A, T, B, base, stride, seeds, mcs), steps)
 
 
 def test_machine_filling_launch_renews_too(gpu_device):
@@ -134,11 +51,11 @@ def test_machine_filling_launch_renews_too(gpu_device):
     from dcmrta_amd.choice import env_seeds
     A, T, B, base = 20, 50, 4096, 9000
     seeds = env_seeds(52, 0, B)
-    env, ring = _make(gpu_device, B, A, T, base, B)
+    env, ring = R.make(gpu_device, B, A, T, base, B)
     env.reset(seeds, observe=False)
     steps = env.rollout_random(episodes=EPISODES).cpu().numpy()
     rows = [int(b) for b in np.arange(64) * 64 + (np.arange(64) * 37) % 64]
-    _assert_after_three(env, ring, _chains(A, T, B, base, B, seeds, rows=rows), rows, steps)
+    R.assert_after(env, ring, R.chains(A, T, B, base, B, seeds, rows=rows), steps, rows)
     assert np.array_equal(env.instance_index().cpu().numpy(), np.full(B, EPISODES - 1))
 
 
@@ -148,56 +65,34 @@ def test_split_calls_give_the_same_results(gpu_device):
     from dcmrta_amd.choice import env_seeds
     A, T, B, base = 20, 50, 32, 8100
     seeds = env_seeds(51, 0, B)
-    chains = _chains(A, T, B, base, B, seeds)
+    chains = R.chains(A, T, B, base, B, seeds)
     n0 = np.array([chains[b][0][0]["n_steps"] for b in range(B)], np.int64)
     n1 = np.array([chains[b][0][1]["n_steps"] for b in range(B)], np.int64)
     # three calls of one episode each
-    env, ring = _make(gpu_device, B, A, T, base, B)
+    env, ring = R.make(gpu_device, B, A, T, base, B)
     env.reset(seeds, observe=False)
     steps = sum(env.rollout_random(episodes=1).cpu().numpy() for _ in range(EPISODES))
-    _assert_after_three(env, ring, chains, range(B), steps)
+    R.assert_after(env, ring, chains, steps)
     # a budget that ends in the middle of episode 1 (every env its own), then the rest: the pending episode counts as one
-    env, ring = _make(gpu_device, B, A, T, base, B)
+    env, ring = R.make(gpu_device, B, A, T, base, B)
     env.reset(seeds, observe=False)
     s1 = env.rollout_random(episodes=EPISODES, max_decisions=n0 + n1 // 2).cpu().numpy()
     assert np.array_equal(s1, n0 + n1 // 2)
     assert np.array_equal(env.instance_index().cpu().numpy(), np.ones(B, np.int64))
     s2 = env.rollout_random(episodes=2).cpu().numpy()
-    _assert_after_three(env, ring, chains, range(B), s1 + s2)
+    R.assert_after(env, ring, chains, s1 + s2)
     # a budget that runs out exactly at the end of episode 0: the finished episode's instance and results stay
-    env, ring = _make(gpu_device, B, A, T, base, B)
+    env, ring = R.make(gpu_device, B, A, T, base, B)
     env.reset(seeds, observe=False)
     s1 = env.rollout_random(episodes=EPISODES, max_decisions=n0).cpu().numpy()
     assert np.array_equal(s1, n0)
     assert np.array_equal(env.instance_index().cpu().numpy(), np.zeros(B, np.int64))
-    held, sm = _held(env), env.summary().cpu().numpy()
+    held, sm = R.held(env), env.summary().cpu().numpy()
     for b in range(B):
-        _assert_instance(held, b, chains[b][1][0])
+        R.assert_instance(held, b, chains[b][1][0])
         assert np.array_equal(sm[b], chains[b][0][0]["row"], equal_nan=True), b
     s2 = env.rollout_random(episodes=2).cpu().numpy()
-    _assert_after_three(env, ring, chains, range(B), s1 + s2)
-
-
-def _lockstep(env, seeds, read_summary_every=0, policy=None):
-    """Step an auto-resetting handle until every env is inactive; actions from the choice protocol's host mirror."""
-    B = env.B
-    obs = env.reset(seeds)
-    dcount = np.zeros(B, np.int64)
-    for s in range(4001):
-        active = obs.active.cpu().numpy()
-        if not active.any():
-            break
-        assert s < 4000, "envs still active after 4000 steps"
-        if policy is None:
-            mk = obs.mask.cpu().numpy().astype(np.uint8)
-            act = np.array([H.host_random_action(mk[b], int(seeds[b]), int(dcount[b])) if active[b] else 0 for b in range(B)], np.int32)
-        else:
-            act = policy(obs)
-        obs = env.step(act)
-        dcount += active
-        if read_summary_every and s % read_summary_every == read_summary_every - 1:
-            env.summary()                       # completes the deferred rows on the way
-    return dcount
+    R.assert_after(env, ring, chains, s1 + s2)
 
 
 @pytest.mark.parametrize("A,T,B,base,read_every", [
@@ -210,11 +105,11 @@ def _lockstep(env, seeds, read_summary_every=0, policy=None):
 def test_lockstep_auto_reset_renews(gpu_device, A, T, B, base, read_every):
     from dcmrta_amd.choice import env_seeds
     seeds = env_seeds(53, 0, B)
-    env, ring = _make(gpu_device, B, A, T, base, B, auto_reset=True, auto_reset_episodes=EPISODES)
+    env, ring = R.make(gpu_device, B, A, T, base, B, auto_reset=True, auto_reset_episodes=EPISODES)
     if T == 700:
         assert env.record_bytes() > 65536
-    dcount = _lockstep(env, seeds, read_every)
-    _assert_after_three(env, ring, _chains(A, T, B, base, B, seeds), range(B), dcount)
+    dcount = R.lockstep_to_end(env, seeds, read_every)
+    R.assert_after(env, ring, R.chains(A, T, B, base, B, seeds), dcount)
     assert np.array_equal(env.status()["decisions"].cpu().numpy(), dcount)
 
 
@@ -225,13 +120,14 @@ def test_lockstep_auto_reset_renews_with_individual_selection(gpu_device, oracle
     from dcmrta_amd.instances import renewal_seeds
     A, T, B, base = 20, 50, 96, 9500
     seeds = env_seeds(54, 0, B)
-    env, ring = _make(gpu_device, B, A, T, base, B, auto_reset=True, auto_reset_episodes=EPISODES, individual_selection=True)
-    dcount = _lockstep(env, seeds, 40, policy=lambda obs: torch.argmax((~obs.mask).to(torch.int32), dim=1).to(torch.int32))
-    sm, rl, idx, held = env.summary().cpu().numpy(), ring.cpu().numpy(), env.instance_index().cpu().numpy(), _held(env)
+    env, ring = R.make(gpu_device, B, A, T, base, B, auto_reset=True, auto_reset_episodes=EPISODES, individual_selection=True)
+    dcount = R.lockstep_to_end(env, seeds, 40, policy=lambda obs: torch.argmax((~obs.mask).to(torch.int32), dim=1).to(torch.int32))
+    sm, rl, idx, held = env.summary().cpu().numpy(), ring.cpu().numpy(), env.instance_index().cpu().numpy(), R.held(env)
     for b in range(B):
         total, rows = 0, []
         for k in range(EPISODES):
-            inst = _host_instance(A, T, renewal_seeds((base + b) % M64, k, B), 5)
+            sized = R.host_instance(A, T, int(renewal_seeds((base + b) % M64, k, B)), 5)
+            inst = sized[1]
             o = oracle_lib.OracleEnv(A, T).load(inst["depot"], inst["task_xy"], inst["req"], inst["dur"])
             finished, guard = False, 0
             while not finished and o.now < 100:                                  # worker.py:163
@@ -247,11 +143,11 @@ def test_lockstep_auto_reset_renews_with_individual_selection(gpu_device, oracle
                 assert guard < 5000
             oracle_lib.lib().orc_finish_episode(o._h)
             ref = o.final()
-            rows.append(np.array([ref["reward"], float(ref["finished"].sum()), *ref["metrics"][:6]], np.float64))
+            rows.append(O.summary_row(ref))
         assert np.array_equal(rl[b], np.array([r[0] for r in rows])), b
         assert np.array_equal(sm[b], rows[-1], equal_nan=True), b
         assert idx[b] == EPISODES - 1 and dcount[b] == total, b
-        _assert_instance(held, b, inst)
+        R.assert_instance(held, b, sized)
 
 
 def test_first_observation_after_a_renewal_is_the_new_instances(gpu_device):
@@ -261,7 +157,7 @@ def test_first_observation_after_a_renewal_is_the_new_instances(gpu_device):
     from dcmrta_amd.choice import env_seeds
     A, T, B, base = 20, 50, 64, 9600
     seeds = env_seeds(55, 0, B)
-    env, _ = _make(gpu_device, B, A, T, base, B, auto_reset=True, auto_reset_episodes=2)
+    env, _ = R.make(gpu_device, B, A, T, base, B, auto_reset=True, auto_reset_episodes=2)
     obs = env.reset(seeds)
     dcount, seen, got = np.zeros(B, np.int64), np.zeros(B, bool), {}
     for s in range(4000):
@@ -278,7 +174,7 @@ def test_first_observation_after_a_renewal_is_the_new_instances(gpu_device):
         if seen.all():
             break
     assert seen.all()
-    twin = BatchedTaskEnv(B, A, T, device=gpu_device).generate_instances(_inst_seeds(base + B, B))
+    twin = BatchedTaskEnv(B, A, T, device=gpu_device).generate_instances(R.inst_seeds(base + B, B))
     tobs = twin.reset(np.array([(int(seeds[b]) + GAMMA * got[b][0]) % M64 for b in range(B)], dtype=np.uint64))
     ta, tt, tm, tl = tobs.agents.cpu().numpy(), tobs.tasks.cpu().numpy(), tobs.mask.cpu().numpy(), tobs.leader.cpu().numpy()
     for b in range(B):
@@ -294,7 +190,7 @@ def test_renewal_turned_off_after_renewals_restarts_from_the_held_instance(gpu_d
     from dcmrta_amd.choice import env_seeds
     A, T, B, base = 20, 50, 32, 9800
     seeds = env_seeds(58, 0, B)
-    env, ring = _make(gpu_device, B, A, T, base, B, auto_reset=True, auto_reset_episodes=EPISODES)
+    env, ring = R.make(gpu_device, B, A, T, base, B, auto_reset=True, auto_reset_episodes=EPISODES)
     obs = env.reset(seeds)
     dcount, at_switch = np.zeros(B, np.int64), None
     for s in range(4001):
@@ -312,15 +208,15 @@ def test_renewal_turned_off_after_renewals_restarts_from_the_held_instance(gpu_d
                 at_switch = idx
                 env.set_instance_renewal(0)
     assert at_switch is not None and (at_switch < EPISODES - 1).any()        # episodes do end after the switch
-    sm, rl, idx, held = env.summary().cpu().numpy(), ring.cpu().numpy(), env.instance_index().cpu().numpy(), _held(env)
+    sm, rl, idx, held = env.summary().cpu().numpy(), ring.cpu().numpy(), env.instance_index().cpu().numpy(), R.held(env)
     assert np.array_equal(env.episodes().cpu().numpy(), np.full(B, EPISODES))
     assert np.array_equal(idx, at_switch)
     for b in range(B):
         n = int(at_switch[b])
-        eps, insts = _oracle_chain_on(A, T, (base + b) % M64, B, int(seeds[b]), tuple(min(k, n) for k in range(EPISODES)))
+        eps, insts = R.oracle_chain(A, T, (base + b) % M64, B, int(seeds[b]), indices=tuple(min(k, n) for k in range(EPISODES)))
         assert np.array_equal(rl[b], np.array([e["row"][0] for e in eps])), b
         assert np.array_equal(sm[b], eps[-1]["row"], equal_nan=True), b
-        _assert_instance(held, b, insts[-1])
+        R.assert_instance(held, b, insts[-1])
         assert dcount[b] == sum(e["n_steps"] for e in eps), b
 
 
@@ -328,26 +224,26 @@ def test_clone_and_restore_carry_index_and_instance(gpu_device):
     from dcmrta_amd.choice import env_seeds
     A, T, B, base = 20, 50, 16, 8100
     seeds = env_seeds(51, 0, B)
-    chains = _chains(A, T, B, base, 32, seeds)                     # (the first 16 envs of the B = 32 case: stride 32)
-    env, ring = _make(gpu_device, B, A, T, base, 32)
+    chains = R.chains(A, T, B, base, 32, seeds)                     # (the first 16 envs of the B = 32 case: stride 32)
+    env, ring = R.make(gpu_device, B, A, T, base, 32)
     env.reset(seeds, observe=False)
     s0 = env.rollout_random(episodes=1, max_decisions=20).cpu().numpy()          # in episode 0
     snap = env.clone_state()
     s1 = env.rollout_random(episodes=EPISODES).cpu().numpy()                     # into episode 2
-    _assert_after_three(env, ring, chains, range(B), s0 + s1)
-    first = (env.summary().clone(), ring.clone(), _held(env))
+    R.assert_after(env, ring, chains, s0 + s1)
+    first = (env.summary().clone(), ring.clone(), R.held(env))
     env.restore_state(snap)
     assert np.array_equal(env.instance_index().cpu().numpy(), np.zeros(B, np.int64))
-    held = _held(env)
+    held = R.held(env)
     for b in range(B):
-        _assert_instance(held, b, chains[b][1][0])
+        R.assert_instance(held, b, chains[b][1][0])
     ring.fill_(float("nan"))
     s2 = env.rollout_random(episodes=EPISODES).cpu().numpy()
     assert np.array_equal(s2, s1)
     assert torch.equal(env.summary().view(torch.int64), first[0].view(torch.int64)) and torch.equal(ring.view(torch.int64), first[1].view(torch.int64))
-    again = _held(env)
+    again = R.held(env)
     assert all(np.array_equal(again[k], first[2][k]) for k in again)
-    _assert_after_three(env, ring, chains, range(B), s0 + s2)
+    R.assert_after(env, ring, chains, s0 + s2)
 
 
 def test_state_rules(gpu_device):
@@ -361,12 +257,12 @@ def test_state_rules(gpu_device):
     setter = lambda stride: env._lib.dcm_set_instance_renewal(env._h, stride)
 
     def two_episodes_change_nothing():
-        before = _held(env)
+        before = R.held(env)
         env.reset(seeds, observe=False)
         env.rollout_random(episodes=2)
         assert np.array_equal(env.episodes().cpu().numpy(), np.full(B, 2))
         assert np.array_equal(env.instance_index().cpu().numpy(), np.zeros(B, np.int64))
-        after = _held(env)
+        after = R.held(env)
         assert all(np.array_equal(before[k], after[k]) for k in before)
 
     # refused after load_instances, and on a batch generated with a real range; stride 0 is always accepted
@@ -382,11 +278,11 @@ def test_state_rules(gpu_device):
     assert setter(B) == ERR_STATE
     # never set: three episodes on the same instance
     env.generate_instances(100)
-    before = _held(env)
+    before = R.held(env)
     env.reset(seeds, observe=False)
     env.rollout_random(episodes=3)
     assert np.array_equal(env.instance_index().cpu().numpy(), np.zeros(B, np.int64))
-    assert all(np.array_equal(before[k], v) for k, v in _held(env).items())
+    assert all(np.array_equal(before[k], v) for k, v in R.held(env).items())
     # on, then a new generate_instances / load_instances turn it off
     assert setter(B) == 0
     env.generate_instances(200)
@@ -405,14 +301,14 @@ def test_state_rules(gpu_device):
     # dcm_reset does not renew and leaves the index alone
     env.reset(seeds, observe=False)
     assert np.array_equal(env.instance_index().cpu().numpy(), np.ones(B, np.int64))
-    held = _held(env)
+    held = R.held(env)
     for b in range(B):
-        _assert_instance(held, b, _host_instance(A, T, 300 + b + B, 5))
+        R.assert_instance(held, b, R.host_instance(A, T, 300 + b + B, 5))
     # stride 0 after renewals have happened: the next two episodes stay on the held instance, index 1
     assert setter(0) == 0
     env.rollout_random(episodes=2)
     assert np.array_equal(env.instance_index().cpu().numpy(), np.ones(B, np.int64))
-    after = _held(env)
+    after = R.held(env)
     assert all(np.array_equal(held[k], after[k]) for k in held)
     # load_instances and generate_instances zero an index that was not 0
     env.load_instances(**generate_batch(B, A, T, base_seed=3))
@@ -432,15 +328,15 @@ def test_captured_step_loop_renews_like_the_eager_loop(gpu_device):
     A, T, B, base = 20, 50, 64, 9700
     seeds = env_seeds(57, 0, B)
     policy = lambda obs: torch.argmax((~obs.mask).to(torch.int32), dim=1).to(torch.int32)
-    eager, ering = _make(gpu_device, B, A, T, base, B, auto_reset=True, auto_reset_episodes=EPISODES)
-    _lockstep(eager, seeds, policy=policy)
-    env, ring = _make(gpu_device, B, A, T, base, B, auto_reset=True, auto_reset_episodes=EPISODES)
+    eager, ering = R.make(gpu_device, B, A, T, base, B, auto_reset=True, auto_reset_episodes=EPISODES)
+    R.lockstep_to_end(eager, seeds, policy=policy)
+    env, ring = R.make(gpu_device, B, A, T, base, B, auto_reset=True, auto_reset_episodes=EPISODES)
     GraphedRollout(env, policy, check_every=8).run(seeds, max_steps=4000)
     assert np.array_equal(env.episodes().cpu().numpy(), np.full(B, EPISODES))
     assert np.array_equal(ring.cpu().numpy(), ering.cpu().numpy())
     assert np.array_equal(env.summary().cpu().numpy(), eager.summary().cpu().numpy(), equal_nan=True)
     assert np.array_equal(env.instance_index().cpu().numpy(), np.full(B, EPISODES - 1))
-    a, b = _held(env), _held(eager)
+    a, b = R.held(env), R.held(eager)
     assert all(np.array_equal(a[k], b[k]) for k in a)
     # ... and the eager loop's returns differ from episode to episode, i.e. the instances really changed
     assert not np.array_equal(ering.cpu().numpy()[:, 0], ering.cpu().numpy()[:, 1])

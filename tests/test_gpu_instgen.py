@@ -10,26 +10,10 @@ import pytest
 import torch
 
 import helpers as H
-from test_gpu_runner import _replay_recorded
+from fixtures_ref import BIG_SEEDS, assert_same_instances, held_instances, replay_recorded
+from renewal_ref import first_valid
 
 pytestmark = pytest.mark.gpu
-
-BIG_SEEDS = [2 ** 32, 2 ** 32 + 12345, 2 ** 40 + 17, 2 ** 63, 2 ** 63 + 2 ** 31 + 5, 12345678901234567890, 2 ** 64 - 1]
-
-
-def _held(env):
-    return {k: (None if v is None else v.cpu().numpy()) for k, v in env.instances().items()}
-
-
-def _assert_same_instances(got, want, what=""):
-    for k in ("depot", "task_xy", "req", "dur"):
-        assert got[k].dtype == np.asarray(want[k]).dtype and np.array_equal(got[k], want[k]), (what, k)
-    for k in ("n_agents", "n_tasks"):
-        if want.get(k) is None:
-            assert got[k] is None, (what, k)
-        else:
-            assert np.array_equal(got[k], want[k]), (what, k)
-
 
 # ------------------------------------------------------------------ 1. known answers of the stream
 @pytest.mark.parametrize("bound", [5, 3 * 2 ** 30, 2 ** 32 - 1])
@@ -66,7 +50,7 @@ def test_uniform_batch_equals_generate_batch(gpu_device, shape):
     B = 96
     env = BatchedTaskEnv(B, A, T, device=gpu_device)
     assert env.generate_instances(1000) is env and env.n_agents is None and env.n_tasks is None
-    _assert_same_instances(_held(env), generate_batch(B, A, T, base_seed=1000), shape)
+    assert_same_instances(held_instances(env), generate_batch(B, A, T, base_seed=1000), shape)
     # other requirement range and duration; seeds as an array, and as a torch tensor, incl. seeds >= 2^32 and >= 2^63
     seeds = np.array(list(range(7, 7 + B - len(BIG_SEEDS))) + BIG_SEEDS, dtype=np.uint64)
     want = generate_batch(B, A, T, max_coalition_size=3, max_duration=2.5)
@@ -75,9 +59,9 @@ def test_uniform_batch_equals_generate_batch(gpu_device, shape):
         for k in want:
             want[k][b] = one[k][0]
     env.generate_instances(seeds, max_coalition_size=3, max_duration=2.5)
-    _assert_same_instances(_held(env), want, shape)
+    assert_same_instances(held_instances(env), want, shape)
     env.generate_instances(torch.from_numpy(seeds.view(np.int64)).to(gpu_device), A, (T, T), 3, 2.5)
-    _assert_same_instances(_held(env), want, shape)
+    assert_same_instances(held_instances(env), want, shape)
 
 
 def test_wide_handle_at_sixteen(gpu_device):
@@ -87,9 +71,9 @@ def test_wide_handle_at_sixteen(gpu_device):
     env = BatchedTaskEnv(B, A, T, device=gpu_device, member_cap=16).generate_instances(300, max_coalition_size=16)
     want = generate_batch(B, A, T, base_seed=300, max_coalition_size=16)
     assert want["req"].max() == 16
-    _assert_same_instances(_held(env), want)
+    assert_same_instances(held_instances(env), want)
     env.generate_instances(300, (10, 20), (20, 50), max_coalition_size=16)
-    _assert_same_instances(_held(env), generate_batch_ranges(range(300, 300 + B), (10, 20), (20, 50), max_coalition_size=16))
+    assert_same_instances(held_instances(env), generate_batch_ranges(range(300, 300 + B), (10, 20), (20, 50), max_coalition_size=16))
 
 
 @pytest.mark.parametrize("ranges", [((10, 20), (20, 50)), (15, (20, 50)), ((10, 20), 40), ((3, 128), (1, 300)), ((20, 20), (50, 50)),
@@ -112,10 +96,10 @@ def test_ragged_batch_equals_generate_batch_ranges(gpu_device, ranges):
             want["n_agents"] = want["n_tasks"] = None
         else:
             assert np.array_equal(env.n_agents, want["n_agents"]) and np.array_equal(env.n_tasks, want["n_tasks"])
-        _assert_same_instances(_held(env), want, (ranges, m))
+        assert_same_instances(held_instances(env), want, (ranges, m))
     if A <= 18 and T <= 45:
         env = BatchedTaskEnv(B, 20, 50, device=gpu_device).generate_instances(seeds, ar, tr)
-        got, want = _held(env), generate_batch_ranges([int(s) for s in seeds], ar, tr)
+        got, want = held_instances(env), generate_batch_ranges([int(s) for s in seeds], ar, tr)
         assert np.array_equal(got["n_agents"], want["n_agents"]) and np.array_equal(got["task_xy"][:, :T], want["task_xy"])
         assert np.array_equal(got["req"][:, :T], want["req"]) and (got["req"][:, T:] == 1).all() and not got["task_xy"][:, T:].any()
 
@@ -130,7 +114,7 @@ def test_reference_golden_instances(gpu_device, golden_dir):
         seeds = z[f"{name}/seeds"]
         env = BatchedTaskEnv(len(seeds), a_hi, t_hi, device=gpu_device, member_cap=m)
         env.generate_instances(seeds, (a_lo, a_hi) if a_tuple else a_lo, (t_lo, t_hi) if t_tuple else t_lo, max_coalition_size=m, max_duration=5)
-        got = _held(env)
+        got = held_instances(env)
         for k in ("depot", "task_xy", "req", "dur"):
             assert np.array_equal(got[k], z[f"{name}/{k}"]), (name, k)
         if a_lo != a_hi or t_lo != t_hi:
@@ -146,10 +130,10 @@ def test_instances_getter_returns_loaded_instances(gpu_device):
     B, A, T = 32, 20, 50
     inst = generate_batch(B, A, T, base_seed=4)
     env = BatchedTaskEnv(B, A, T, device=gpu_device).load_instances(**inst)
-    _assert_same_instances(_held(env), inst)
+    assert_same_instances(held_instances(env), inst)
     rag = generate_batch_ranges(range(B), (10, 20), (20, 50))
     env.load_instances(**rag)
-    _assert_same_instances(_held(env), rag)
+    assert_same_instances(held_instances(env), rag)
 
 
 # ------------------------------------------------------------------ 3. a generated handle behaves like a host-loaded twin
@@ -221,10 +205,6 @@ def test_route_replay_equals_host_loaded_twin(gpu_device):
 
 
 # ------------------------------------------------------------------ 4. raggedness switching on one handle
-def first_valid(obs):
-    return torch.argmax((~obs.mask).to(torch.int32), dim=1)   # lowest unmasked action id
-
-
 def test_uniform_ragged_uniform_on_one_handle(gpu_device, oracle_lib):
     from dcmrta_amd.batched_env import BatchedTaskEnv
     from dcmrta_amd.choice import env_seeds
@@ -237,19 +217,19 @@ def test_uniform_ragged_uniform_on_one_handle(gpu_device, oracle_lib):
     epoch = env.graph_epoch
     g = GraphedRollout(env, first_valid, check_every=4, record=True)
     summary, n = g.run(seeds)
-    _replay_recorded(oracle_lib, {k: v[:n] for k, v in g.rec.items()}, summary.cpu().numpy(), inst, seeds, A, T)
+    replay_recorded(oracle_lib, {k: v[:n] for k, v in g.rec.items()}, summary.cpu().numpy(), inst, seeds, A, T)
     graph_before = g.graph
     env.generate_instances(99)                                  # uniform again: the captured graph stays
     assert env.graph_epoch == epoch
     summary2, n2 = g.run(seeds)
     assert g.graph is graph_before
-    _replay_recorded(oracle_lib, {k: v[:n2] for k, v in g.rec.items()}, summary2.cpu().numpy(), generate_batch(B, A, T, base_seed=99), seeds, A, T)
+    replay_recorded(oracle_lib, {k: v[:n2] for k, v in g.rec.items()}, summary2.cpu().numpy(), generate_batch(B, A, T, base_seed=99), seeds, A, T)
     rag = generate_batch_ranges(range(700, 700 + B), (10, 20), (20, 50))
     env.generate_instances(700, (10, 20), (20, 50))             # ragged: per-env sizes pointer, other kernel instantiation
     assert env.graph_epoch == epoch + 1 and np.array_equal(env.n_tasks, rag["n_tasks"])
     summary3, n3 = g.run(seeds)
     assert g.graph is not graph_before
-    _replay_recorded(oracle_lib, {k: v[:n3] for k, v in g.rec.items()}, summary3.cpu().numpy(), rag, seeds, A, T,
+    replay_recorded(oracle_lib, {k: v[:n3] for k, v in g.rec.items()}, summary3.cpu().numpy(), rag, seeds, A, T,
                      n_agents=rag["n_agents"], n_tasks=rag["n_tasks"])
     env.generate_instances(21)                                  # ... and back
     assert env.graph_epoch == epoch + 2 and env.n_tasks is None
@@ -271,7 +251,7 @@ def test_invalid_arguments_change_nothing(gpu_device):
     from dcmrta_amd.choice import env_seeds
     B, A, T = 16, 20, 50
     env = BatchedTaskEnv(B, A, T, device=gpu_device, auto_reset=True, auto_reset_episodes=1).generate_instances(5)
-    before = _held(env)
+    before = held_instances(env)
     obs = env.reset(env_seeds(3, 0, B))
     while bool(obs.active.any()):                               # eager auto-reset steps: terminal rows wait for the deferred flush
         obs = env.step(first_valid(obs).to(torch.int32))
@@ -289,7 +269,7 @@ def test_invalid_arguments_change_nothing(gpu_device):
             env.generate_instances(5, **kw)
     assert env.n_tasks is None
     # the handle still holds its instances and its finished episodes' summaries
-    _assert_same_instances(_held(env), before)
+    assert_same_instances(held_instances(env), before)
     sm = env.summary().cpu().numpy()
     assert not np.isnan(sm).any()
     twin = BatchedTaskEnv(B, A, T, device=gpu_device, auto_reset=True, auto_reset_episodes=1).generate_instances(5)

@@ -14,10 +14,13 @@ dropping tasks' `gone` masks run at most decisions -- asserted from the oracle o
 for bit: decisions per env, both episodes' returns, summary(), the observation and mask tensors of the decision at a stop in the
 middle of the first episode -- through rollout_random (k_rollout_fast) and through the lockstep step loop (k_step_fast runs the same
 Fast<> text), whose every decision's observation is compared."""
+import functools
+
 import numpy as np
 import pytest
 
 import helpers as H
+import oracle_ref as O
 
 B = 16
 #        A,  T,  env's sizes (None: the handle's own)
@@ -25,46 +28,19 @@ SHAPES = [(20, 50, None), (20, 50, (17, 20)), (64, 63, None), (5, 8, None)]
 MWTS = [10.0, 2.0]
 CASES = [(A, T, s, w) for A, T, s in SHAPES for w in MWTS]
 
-_refs = {}
 
-
+@functools.lru_cache(maxsize=None)
 def references(oracle_lib, A, T, sizes, mwt):
     """(instances, seeds, first-episode traces, second-episode results): computed once per case, read-only afterwards"""
-    key = (A, T, sizes, mwt)
-    if key not in _refs:
-        from dcmrta_amd.choice import env_seeds
-        from dcmrta_amd.instances import generate_batch
-        a, t = sizes or (A, T)
-        inst = generate_batch(B, A, T, base_seed=7)
-        seeds = env_seeds(3, 0, B)
-
-        def run(b, d0, record):
-            o = oracle_lib.OracleEnv(a, t, max_waiting_time=mwt).load(inst["depot"][b], inst["task_xy"][b, :t], inst["req"][b, :t],
-                                                                      inst["dur"][b, :t])
-            return o.rollout(int(seeds[b]), d0, oracle_lib.POLICY_RANDOM, cap_steps=20000, record=record)
-        ep1 = [run(b, 0, True) for b in range(B)]
-        ep2 = [run(b, ep1[b]["n_steps"], False) for b in range(B)]
-        _refs[key] = (inst, seeds, ep1, ep2)
-    return _refs[key]
+    from dcmrta_amd.choice import env_seeds
+    from dcmrta_amd.instances import generate_batch
+    inst, seeds = generate_batch(B, A, T, base_seed=7), env_seeds(3, 0, B)
+    return (inst, seeds) + O.two_episodes(inst, seeds, *(sizes or (A, T)), mwt)
 
 
 def abandonments(ep1):
     """per env: appends to an abandoned_agent list in the first episode"""
     return [int(r["n_abandoned"].sum()) for r in ep1]
-
-
-def _make_env(gpu_device, A, T, sizes, mwt, inst):
-    from dcmrta_amd.batched_env import BatchedTaskEnv
-    env = BatchedTaskEnv(B, A, T, device=gpu_device, max_waiting_time=mwt)
-    if sizes:
-        return env.load_instances(**inst, n_agents=np.full(B, sizes[0], np.int32), n_tasks=np.full(B, sizes[1], np.int32))
-    return env.load_instances(**inst)
-
-
-def _assert_summary(sm, ref, name):
-    assert sm[0] == ref["reward"] and int(sm[1]) == int(ref["finished"].sum()), name + ": reward / finished tasks"
-    for i in range(6):
-        assert sm[2 + i] == ref["metrics"][i], f"{name}: metric {i} {sm[2 + i]!r} != {ref['metrics'][i]!r}"
 
 
 @pytest.mark.parametrize("A,T,sizes,mwt", CASES)
@@ -91,7 +67,7 @@ def test_rollout_against_the_oracle(gpu_device, oracle_lib, A, T, sizes, mwt):
     n1 = np.array([r["n_steps"] for r in ep1], np.int64)
     n2 = np.array([r["n_steps"] for r in ep2], np.int64)
     # two episodes in one launch: decisions, both returns, summary() of the second
-    env = _make_env(gpu_device, A, T, sizes, mwt, inst)
+    env = H.sized_env(gpu_device, A, T, inst, sizes, max_waiting_time=mwt)
     ring = env.enable_return_log(2)
     env.reset(seeds, observe=False)
     steps = env.rollout_random(episodes=2).cpu().numpy()
@@ -99,7 +75,7 @@ def test_rollout_against_the_oracle(gpu_device, oracle_lib, A, T, sizes, mwt):
     assert np.array_equal(steps, n1 + n2), (tag, steps, n1 + n2)
     for b in range(B):
         assert got[b, 0] == ep1[b]["reward"] and got[b, 1] == ep2[b]["reward"], (tag, b, got[b], ep1[b]["reward"], ep2[b]["reward"])
-        _assert_summary(sm[b], ep2[b], f"{tag} env{b} episode 2")
+        O.assert_summary(sm[b], ep2[b], f"{tag} env{b} episode 2")
     # a stop in the middle of the first episode: what the kernel stored for the last decision taken is the oracle's record of it
     env.enable_return_log(0)
     env.reset(seeds, observe=False)
@@ -118,7 +94,7 @@ def test_rollout_against_the_oracle(gpu_device, oracle_lib, A, T, sizes, mwt):
     assert np.array_equal(steps, n1 - at), (tag, steps, n1 - at)
     sm = env.summary().cpu().numpy()
     for b in range(B):
-        _assert_summary(sm[b], ep1[b], f"{tag} env{b} episode 1 after the stop")
+        O.assert_summary(sm[b], ep1[b], f"{tag} env{b} episode 1 after the stop")
     env.close()
 
 
@@ -129,7 +105,7 @@ def test_lockstep_against_the_oracle(gpu_device, oracle_lib, A, T, sizes, mwt):
     inst, seeds, ep1, _ = references(oracle_lib, A, T, sizes, mwt)
     a, t = sizes or (A, T)
     tag = f"lockstep {A}A/{T}T sizes {sizes} mwt {mwt}"
-    env = _make_env(gpu_device, A, T, sizes, mwt, inst)
+    env = H.sized_env(gpu_device, A, T, inst, sizes, max_waiting_time=mwt)
     got = H.run_lockstep(env, seeds, lambda b, i, m, l: H.host_random_action(m[:t + 1], int(seeds[b]), i))
     sm = env.summary().cpu().numpy()
     for b, r in enumerate(ep1):
@@ -140,5 +116,5 @@ def test_lockstep_against_the_oracle(gpu_device, oracle_lib, A, T, sizes, mwt):
         assert np.array_equal(g["mask"][:, :t + 1], r["mask"]), name + ": mask"
         assert np.array_equal(g["agents_obs"][:, :a], r["agents_obs"]), name + ": agents observation"
         assert np.array_equal(g["tasks_obs"][:, :t + 1], r["tasks_obs"]), name + ": tasks observation"
-        _assert_summary(sm[b], r, name)
+        O.assert_summary(sm[b], r, name)
     env.close()

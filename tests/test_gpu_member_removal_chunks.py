@@ -4,7 +4,7 @@ incremental chunk visiting), FastMc (csrc/rollout_fast_mc.hpp), Sim<...>::task_u
 with sixteen member slots -- against the oracle, decision by decision.
 
 max_waiting_time is short in every case, so both removal rules fire all the time.  The oracle is walked with walk_episode of
-test_gpu_member_removal.py (checked in walks() against the oracle's own rollout), and from that walk alone -- no kernel involved --
+removal_ref.py (checked in walks() against the oracle's own rollout), and from that walk alone -- no kernel involved --
 test_inputs_reach_every_removal_path shows that the inputs hold what each kernel can get wrong: a removal at every slot of a full list
 (slot 4 is the idh word), removals in every task chunk, of agents of the second agent chunk, of both agent chunks by one task, and agents
 abandoned more than AB_CAP = 16 times in an episode (the overflow table, also in a ragged env whose own T is below the layout's).
@@ -15,7 +15,8 @@ import numpy as np
 import pytest
 
 import helpers as H
-from test_gpu_member_removal import coverage, walk_episode
+import oracle_ref as O
+from removal_ref import coverage, walk_episode
 
 AB_CAP = 16                 # entries of an agent's abandonment log (csrc/common.hpp); further ones go to the count table
 INST_SEED, CHOICE_SEED = 11, 5
@@ -84,15 +85,6 @@ def _load(oracle_lib, name, inst, b):
                                                                               inst["dur"][b, :t])
 
 
-def _episodes(make, seed_e, policy, n=3, record_first=False):
-    """n consecutive episodes of the oracle, the decision counter running on; make(k) = a loaded OracleEnv for episode k"""
-    eps, d0 = [], 0
-    for k in range(n):
-        eps.append(make(k).rollout(seed_e, d0, policy, cap_steps=20000, record=(record_first and k == 0)))
-        d0 += eps[-1]["n_steps"]
-    return eps
-
-
 def walks(oracle_lib, name):
     """(instances, seeds, per-env snapshots, per-env removals, the oracle's own three episodes): computed once, read-only afterwards.
     The walk is checked against the oracle's rollout of the first episode here, every decision's record; the snapshots then keep the
@@ -102,7 +94,7 @@ def walks(oracle_lib, name):
         snaps, rem, eps = [], [], []
         for b in range(CASES[name]["B"]):
             s, r = walk_episode(_load(oracle_lib, name, inst, b), inst["req"][b], int(seeds[b]))
-            three = _episodes(lambda k: _load(oracle_lib, name, inst, b), int(seeds[b]), oracle_lib.POLICY_RANDOM, record_first=True)
+            three = O.episodes_first_recorded(*sizes(name, b), O.one(inst, b, sizes(name, b)[1]), seeds[b], "random", 3, CASES[name]["mwt"])
             first = three[0]
             assert len(s) == first["n_steps"], (name, b)
             for k in ("leader", "action", "now", "mask", "agents_obs", "tasks_obs"):
@@ -233,11 +225,6 @@ def _assert_final(env, name, eps):
         H.assert_final_matches(got, three[0], f"{name} env {b}")
 
 
-def _assert_summary(sm, ref, tag):
-    assert sm[0] == ref["reward"] and int(sm[1]) == int(ref["finished"].sum()), tag
-    assert np.array_equal(sm[2:8], ref["metrics"]), (tag, sm, ref["metrics"])
-
-
 @pytest.mark.gpu
 @pytest.mark.parametrize("name", [n for n, c in CASES.items() if c["lockstep"] is not None])
 def test_lockstep_after_every_decision(gpu_device, oracle_lib, name):
@@ -279,7 +266,7 @@ def test_lockstep_after_every_decision(gpu_device, oracle_lib, name):
         raise AssertionError("the lockstep loop did not end")
     sm = env.summary().cpu().numpy()
     for b in range(B):
-        _assert_summary(sm[b], eps[b][0], (name, b))
+        O.assert_summary(sm[b], eps[b][0], (name, b))
     _assert_final(env, name, eps)
     env.close()
 
@@ -337,7 +324,7 @@ def _assert_three(name, steps, ring, sm, eps):
     assert np.array_equal(steps, np.array([sum(r["n_steps"] for r in three) for three in eps])), (name, steps)
     for b, three in enumerate(eps):
         assert [ring[b, i] for i in range(3)] == [r["reward"] for r in three], (name, b)
-        _assert_summary(sm[b], three[2], (name, b))
+        O.assert_summary(sm[b], three[2], (name, b))
 
 
 @pytest.mark.gpu
@@ -359,7 +346,7 @@ def test_three_greedy_episodes_in_one_launch(gpu_device, oracle_lib, name):
     """rollout("first"): the general form of the greedy kernels at these shapes, against the oracle under POLICY_FIRST"""
     inst, seeds = instances(name)
     if name not in _first:
-        _first[name] = [_episodes(lambda k: _load(oracle_lib, name, inst, b), int(seeds[b]), oracle_lib.POLICY_FIRST)
+        _first[name] = [O.episodes(*sizes(name, b), O.one(inst, b, sizes(name, b)[1]), seeds[b], "first", 3, CASES[name]["mwt"])
                         for b in range(CASES[name]["B"])]
     env = _env(gpu_device, name, inst)
     ring = env.enable_return_log(3)
@@ -379,12 +366,9 @@ def test_three_episodes_on_renewed_instances(gpu_device, oracle_lib):
     B, A, T = c["B"], c["A"], c["T"]
     seeds = env_seeds(CHOICE_SEED, 0, B)
 
-    def make(b, k):
-        inst = generate_instance(A, T, int(renewal_seeds(c["base"] + b, k, B)))
-        return oracle_lib.OracleEnv(A, T, max_waiting_time=c["mwt"]).load(inst["depot"], inst["task_xy"], inst["req"], inst["dur"])
-
     if not _renew:
-        _renew["eps"] = [_episodes(lambda k: make(b, k), int(seeds[b]), oracle_lib.POLICY_RANDOM) for b in range(B)]
+        _renew["eps"] = [O.episodes(A, T, lambda k: generate_instance(A, T, int(renewal_seeds(c["base"] + b, k, B))), seeds[b], "random", 3, c["mwt"])
+                         for b in range(B)]
     env = BatchedTaskEnv(B, A, T, device=gpu_device, max_waiting_time=c["mwt"])
     env.generate_instances(c["base"])
     env.set_instance_renewal(B)

@@ -11,8 +11,13 @@ One shape per kernel and reduction width, each compared with the oracle bit for 
 summary(), and the per-decision outputs at a stop right behind a next-group step.  That every env's inputs contain such steps is
 asserted from the oracle's trace (a test of its own, without a GPU): consecutive decisions with equal `now` and a different leader
 position (row 0 of tasks_obs holds depot - leader position)."""
+import functools
+
 import numpy as np
 import pytest
+
+import helpers as H
+import oracle_ref as O
 
 DUR = 2.0
 #        A,  T,  env's sizes (None: the handle's own), B     kernel, reduction
@@ -43,40 +48,12 @@ def next_group_steps(ref):
     return np.flatnonzero((now[1:] == now[:-1]) & (pos[1:] != pos[:-1]).any(axis=1))
 
 
-def _oracle(oracle_lib, inst, b, a, t, seed, d0, record):
-    o = oracle_lib.OracleEnv(a, t).load(inst["depot"][b], inst["task_xy"][b, :t], inst["req"][b, :t], inst["dur"][b, :t])
-    return o.rollout(int(seed), d0, oracle_lib.POLICY_RANDOM, cap_steps=20000, record=record)
-
-
-_refs = {}
-
-
+@functools.lru_cache(maxsize=None)
 def references(oracle_lib, A, T, sizes, B):
     """(instances, seeds, first-episode traces, second-episode results) of a shape: computed once, read-only afterwards"""
-    key = (A, T, sizes, B)
-    if key not in _refs:
-        from dcmrta_amd.choice import env_seeds
-        a, t = sizes or (A, T)
-        inst = mirror_batch(B, A, T, seed=1000 * A + T + (7 if sizes else 0))
-        seeds = env_seeds(52, 0, B)
-        ep1 = [_oracle(oracle_lib, inst, b, a, t, seeds[b], 0, True) for b in range(B)]
-        ep2 = [_oracle(oracle_lib, inst, b, a, t, seeds[b], ep1[b]["n_steps"], False) for b in range(B)]
-        _refs[key] = (inst, seeds, ep1, ep2)
-    return _refs[key]
-
-
-def _make_env(gpu_device, A, T, sizes, B, inst):
-    from dcmrta_amd.batched_env import BatchedTaskEnv
-    env = BatchedTaskEnv(B, A, T, device=gpu_device)
-    if sizes:
-        return env.load_instances(**inst, n_agents=np.full(B, sizes[0], np.int32), n_tasks=np.full(B, sizes[1], np.int32))
-    return env.load_instances(**inst)
-
-
-def _assert_summary(sm, ref, name):
-    assert sm[0] == ref["reward"] and int(sm[1]) == int(ref["finished"].sum()), name + ": reward / finished tasks"
-    for i in range(6):
-        assert sm[2 + i] == ref["metrics"][i], f"{name}: metric {i} {sm[2 + i]!r} != {ref['metrics'][i]!r}"
+    from dcmrta_amd.choice import env_seeds
+    inst, seeds = mirror_batch(B, A, T, seed=1000 * A + T + (7 if sizes else 0)), env_seeds(52, 0, B)
+    return (inst, seeds) + O.two_episodes(inst, seeds, *(sizes or (A, T)))
 
 
 @pytest.mark.parametrize("A,T,sizes,B", SHAPES)
@@ -98,7 +75,7 @@ def test_mirror_instances_against_the_oracle(gpu_device, oracle_lib, A, T, sizes
     n1 = np.array([r["n_steps"] for r in ep1], np.int64)
     n2 = np.array([r["n_steps"] for r in ep2], np.int64)
     # two episodes in one launch: decisions, both returns, summary() of the second
-    env = _make_env(gpu_device, A, T, sizes, B, inst)
+    env = H.sized_env(gpu_device, A, T, inst, sizes)
     ring = env.enable_return_log(2)
     env.reset(seeds, observe=False)
     steps = env.rollout_random(episodes=2).cpu().numpy()
@@ -106,7 +83,7 @@ def test_mirror_instances_against_the_oracle(gpu_device, oracle_lib, A, T, sizes
     assert np.array_equal(steps, n1 + n2), (tag, steps, n1 + n2)
     for b in range(B):
         assert got[b, 0] == ep1[b]["reward"] and got[b, 1] == ep2[b]["reward"], (tag, b, got[b], ep1[b]["reward"], ep2[b]["reward"])
-        _assert_summary(sm[b], ep2[b], f"{tag} env{b} episode 2")
+        O.assert_summary(sm[b], ep2[b], f"{tag} env{b} episode 2")
     # stop right behind a next-group step (the one nearest to the middle of the episode): the last decision taken is the first of
     # the new group, and what the kernel stored for it is the oracle's record of it
     env.enable_return_log(0)
@@ -143,7 +120,7 @@ def test_mirror_instances_against_the_oracle(gpu_device, oracle_lib, A, T, sizes
     assert np.array_equal(steps, n1 - at), (tag, steps, n1 - at)
     sm = env.summary().cpu().numpy()
     for b in range(B):
-        _assert_summary(sm[b], ep1[b], f"{tag} env{b} episode 1 after the stop")
+        O.assert_summary(sm[b], ep1[b], f"{tag} env{b} episode 1 after the stop")
 
 
 @pytest.mark.gpu
@@ -153,11 +130,11 @@ def test_full_machine_launch_on_mirror_instances(gpu_device, oracle_lib):
     B, A, T = 4096, 20, 50
     inst = mirror_batch(B, A, T, seed=99)
     seeds = env_seeds(53, 0, B)
-    env = _make_env(gpu_device, A, T, None, B, inst)
+    env = H.sized_env(gpu_device, A, T, inst)
     env.reset(seeds, observe=False)
     steps = env.rollout_random(episodes=1).cpu().numpy()
     sm = env.summary().cpu().numpy()
     for b in range(B):
-        ref = _oracle(oracle_lib, inst, b, A, T, seeds[b], 0, False)
+        ref = O.episodes(A, T, O.one(inst, b), seeds[b], "random", 1)[0]
         assert steps[b] == ref["n_steps"], (b, steps[b], ref["n_steps"])
-        _assert_summary(sm[b], ref, f"env{b} of 4096")
+        O.assert_summary(sm[b], ref, f"env{b} of 4096")

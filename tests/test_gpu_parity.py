@@ -218,7 +218,7 @@ def test_extra_hashed_traces(gpu_device, golden_dir):
     per-decision output of the lockstep API (leader, action, event time, mask, both observation tensors) and the terminal
     arrays must equal the reference's; the persistent kernel must end in the same state.  The range-drawn instances run
     as ONE ragged batch."""
-    from test_oracle_golden import extra_instance
+    from fixtures_ref import extra_instance
     hashes = json.load(open(os.path.join(golden_dir, "trace_hashes_extra.json")))
     groups = {}
     for name, meta in hashes.items():

@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import helpers as H
+import oracle_ref as O
 
 pytestmark = pytest.mark.gpu
 
@@ -19,29 +20,8 @@ ERR_INVALID, ERR_STATE = -1, -4
 POLICIES = ("first", "nearest")
 
 
-def _opol(name):
-    import oracle
-    return {"first": oracle.POLICY_FIRST, "nearest": oracle.POLICY_NEAREST}[name]
-
-
 def _bits(x):
     return np.ascontiguousarray(x, np.float32).view(np.uint32)
-
-
-def _oracle_episodes(A, T, inst, seed, policy, episodes=1, mwt=10.0, record=True):
-    """`episodes` consecutive episodes of one env on one instance: the decision counter runs on across them (d0)."""
-    import oracle
-    out, d0 = [], 0
-    for _ in range(episodes):
-        r = oracle.OracleEnv(A, T, max_waiting_time=mwt).load(inst["depot"], inst["task_xy"], inst["req"], inst["dur"]) \
-            .rollout(int(seed), d0, _opol(policy), cap_steps=20000, record=record)
-        out.append(r)
-        d0 += r["n_steps"]
-    return out
-
-
-def _row(r):
-    return np.array([r["reward"], float(r["finished"].sum()), *r["metrics"][:6]], np.float64)
 
 
 def _obs(env):
@@ -162,9 +142,9 @@ def _case_refs(A, T, B, ranges, policy, mwt):
     refs = []
     for b in range(B):
         a, t = (A, T) if ranges is None else (int(inst["n_agents"][b]), int(inst["n_tasks"][b]))
-        one = dict(depot=inst["depot"][b], task_xy=inst["task_xy"][b, :t], req=inst["req"][b, :t], dur=inst["dur"][b, :t])
-        eps = _oracle_episodes(a, t, one, seeds[b], policy, 3, mwt, record=False)
-        first = _oracle_episodes(a, t, one, seeds[b], policy, 1, mwt, record=True)[0]
+        one = O.one(inst, b, t)
+        eps = O.episodes(a, t, one, seeds[b], policy, 3, mwt)
+        first = O.episodes(a, t, one, seeds[b], policy, 1, mwt, record=True)[0]
         refs.append((a, t, eps, first))
     return seeds, refs
 
@@ -206,7 +186,7 @@ def test_three_episodes_and_a_random_stop_against_the_oracle(gpu_device, A, T, B
         tag = f"{A}A{T}T {policy} env{b}"
         assert steps[b] == sum(e["n_steps"] for e in eps), tag
         assert np.array_equal(rl[b], np.array([e["reward"] for e in eps])), tag
-        assert np.array_equal(sm[b], _row(eps[-1])), tag
+        assert np.array_equal(sm[b], O.summary_row(eps[-1])), tag
         f = dict(fin[b])
         for k in ("finished", "feasible", "time_start", "time_finish", "task_wait", "n_members", "n_abandoned"):
             f[k] = f[k][:t]
@@ -248,7 +228,7 @@ def test_zero_max_waiting_time_under_a_budget(gpu_device, policy):
     A, T, B, N = 20, 50, 8, 400
     inst, seeds = _case_instances(A, T, B, None), env_seeds(23, 0, B)
     refs = [oracle.OracleEnv(A, T, max_waiting_time=0.0).load(inst["depot"][b], inst["task_xy"][b], inst["req"][b], inst["dur"][b])
-            .rollout(int(seeds[b]), 0, _opol(policy), cap_steps=N, record=True, allow_cap=True) for b in range(B)]
+            .rollout(int(seeds[b]), 0, O.opol(policy), cap_steps=N, record=True, allow_cap=True) for b in range(B)]
     assert all(r["n_steps"] == N for r in refs)
     env = BatchedTaskEnv(B, A, T, device=gpu_device, max_waiting_time=0.0).load_instances(**inst)
     ring = env.enable_return_log(3)
@@ -375,7 +355,7 @@ def test_nearest_ties_go_to_the_lowest_index_and_roots_are_compared(gpu_device, 
     env = BatchedTaskEnv(B, A, T, device=gpu_device, max_waiting_time=mwt)
     env.load_instances(*[np.stack([i[k] for i in insts]) for k in ("depot", "task_xy", "req", "dur")])
     env.reset(seeds, observe=False)
-    refs = [_oracle_episodes(A, T, insts[b], seeds[b], "nearest", 1, mwt)[0] for b in range(B)]
+    refs = [O.episodes(A, T, insts[b], seeds[b], "nearest", 1, mwt, record=True)[0] for b in range(B)]
 
     def launch(budget):
         if form != "general-partial-obs":
@@ -412,7 +392,6 @@ def test_nearest_under_instance_renewal(gpu_device, A, T, B, base):
     from dcmrta_amd.batched_env import BatchedTaskEnv
     from dcmrta_amd.choice import env_seeds
     from dcmrta_amd.instances import generate_instance, renewal_seeds
-    import oracle
     seeds = env_seeds(61, 0, B)
     env = BatchedTaskEnv(B, A, T, device=gpu_device)
     env.generate_instances(np.arange(base, base + B, dtype=np.uint64))
@@ -423,15 +402,12 @@ def test_nearest_under_instance_renewal(gpu_device, A, T, B, base):
     rl, sm, idx, fin = ring.cpu().numpy(), env.summary().cpu().numpy(), env.instance_index().cpu().numpy(), H.gpu_final(env)
     held = {k: v.cpu().numpy() for k, v in env.instances().items() if v is not None}
     for b in range(B):
-        d0, rets, r, inst = 0, [], None, None
-        for k in range(3):
-            inst = generate_instance(A, T, int(renewal_seeds(base + b, k, B)))
-            assert int(renewal_seeds(base + b, k, B)) == base + k * B + b
-            r = oracle.OracleEnv(A, T).load(inst["depot"], inst["task_xy"], inst["req"], inst["dur"]) \
-                .rollout(int(seeds[b]), d0, oracle.POLICY_NEAREST, cap_steps=20000, record=False)
-            rets.append(r["reward"])
-            d0 += r["n_steps"]
-        assert steps[b] == d0 and np.array_equal(rl[b], np.array(rets)) and np.array_equal(sm[b], _row(r)), b
+        assert all(int(renewal_seeds(base + b, k, B)) == base + k * B + b for k in range(3))
+        insts = [generate_instance(A, T, int(renewal_seeds(base + b, k, B))) for k in range(3)]
+        eps = O.episodes(A, T, insts.__getitem__, seeds[b], "nearest", 3)
+        r, inst = eps[-1], insts[-1]
+        assert steps[b] == sum(e["n_steps"] for e in eps) and np.array_equal(rl[b], np.array([e["reward"] for e in eps])), b
+        assert np.array_equal(sm[b], O.summary_row(r)), b
         assert idx[b] == 2, (b, idx[b])
         assert all(np.array_equal(held[k][b], inst[k]) for k in ("depot", "task_xy", "req", "dur")), b
         H.assert_final_matches(fin[b], r, f"renewal {A}A{T}T env{b}")
@@ -493,8 +469,7 @@ def test_budget_stop_leaves_a_valid_decision_point_for_the_lockstep_api(gpu_devi
     from dcmrta_amd.instances import generate_batch
     B, A, T = 6, 20, 50
     inst, seeds = generate_batch(B, A, T, base_seed=808), env_seeds(14, 0, B)
-    refs = [_oracle_episodes(A, T, {k: inst[k][b] for k in ("depot", "task_xy", "req", "dur")}, seeds[b], policy, 1, record=False)[0]
-            for b in range(B)]
+    refs = [O.episodes(A, T, O.one(inst, b), seeds[b], policy, 1)[0] for b in range(B)]
     env = BatchedTaskEnv(B, A, T, device=gpu_device).load_instances(**inst)
     env.reset(seeds, observe=False)
     at = np.array([max(1, r["n_steps"] // 3) for r in refs], np.int64)

@@ -9,7 +9,7 @@ before it left behind.  At max_coalition_size <= 16 a word is rejected with prob
   3. the same seeds as the instance an env RENEWS to inside every kernel form that compiles the renewal separately.
 
 Every comparison is exact: numpy itself for 1, the host generators of dcmrta_amd/instances.py for 2, the oracle on host-generated
-instances for 3 (the chains of test_gpu_instance_renewal / test_gpu_size_renewal)."""
+instances for 3 (the chains of renewal_ref.py, as in test_gpu_instance_renewal / test_gpu_size_renewal)."""
 import functools
 import os
 
@@ -17,15 +17,11 @@ import numpy as np
 import pytest
 import torch
 
-import test_gpu_instance_renewal as IR
-import test_gpu_size_renewal as SR
-from test_gpu_instgen import BIG_SEEDS, _assert_same_instances, _held
-from test_rejecting_seeds_host import load_fixture, no_rejection_form, numpy_words
+import renewal_ref as R
+from fixtures_ref import BIG_SEEDS, assert_same_instances, held_instances, load_rejecting_seeds, no_rejection_form, numpy_words
+from renewal_ref import EPISODES, M64
 
 pytestmark = pytest.mark.gpu
-
-M64 = 1 << 64
-EPISODES = IR.EPISODES
 
 
 # ------------------------------------------------------------------ 1. the stream at a bound that rejects now and then
@@ -89,7 +85,7 @@ def test_generator_draws_with_occasional_rejections(gpu_device, bound, n, n_seed
 # ------------------------------------------------------------------ 2. dcm_generate_instances on the fixture seeds
 @pytest.fixture(scope="module")
 def fixture_seeds(golden_dir):
-    return load_fixture(golden_dir)
+    return load_rejecting_seeds(golden_dir)
 
 
 def _rejects(e):
@@ -105,8 +101,8 @@ def _rejects(e):
     return A, inst
 
 
-# one case per class the fixture holds (test_rejecting_seeds_host.NEEDED says which it must hold)
-CLASSES = sorted(load_fixture(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")))
+# one case per class the fixture holds (NEEDED in test_rejecting_seeds_host.py says which it must hold)
+CLASSES = sorted(load_rejecting_seeds(os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")))
 
 
 @pytest.mark.parametrize("name", CLASSES)
@@ -117,7 +113,7 @@ def test_generate_instances_on_rejecting_seeds(gpu_device, fixture_seeds, name):
     for e in entries:
         _rejects(e)
     ar, tr, m = entries[0]["agents_range"], entries[0]["tasks_range"], entries[0]["max_coalition_size"]
-    A, T = SR._dim(ar), SR._dim(tr)
+    A, T = R.dim(ar), R.dim(tr)
     B = 32
     fx = [e["seed"] for e in entries]
     # fixture seeds between ordinary ones, at both ends of the batch and in the middle
@@ -130,10 +126,10 @@ def test_generate_instances_on_rejecting_seeds(gpu_device, fixture_seeds, name):
         want["n_agents"] = want["n_tasks"] = None
     env = BatchedTaskEnv(B, A, T, device=gpu_device, member_cap=16 if m > 5 else 5)
     env.generate_instances(seeds, ar, tr, max_coalition_size=m)
-    _assert_same_instances(_held(env), want, name)
+    assert_same_instances(held_instances(env), want, name)
     env.generate_instances(0)                                            # other instances in between
     env.generate_instances(torch.from_numpy(seeds.view(np.int64)).to(gpu_device), ar, tr, m)
-    _assert_same_instances(_held(env), want, name)
+    assert_same_instances(held_instances(env), want, name)
     if ragged:
         assert np.array_equal(env.n_agents, want["n_agents"]) and np.array_equal(env.n_tasks, want["n_tasks"])
 
@@ -150,11 +146,11 @@ def test_buffered_half_word_across_blocks(gpu_device, ranges, m):
     seeds = np.array(list(range(600, 600 + B - len(BIG_SEEDS))) + BIG_SEEDS, dtype=np.uint64)
     want = generate_batch_ranges([int(s) for s in seeds], ar, tr, max_coalition_size=m)
     assert want["n_tasks"].max() > 128
-    env = BatchedTaskEnv(B, SR._dim(ar), SR._dim(tr), device=gpu_device).generate_instances(seeds, ar, tr, max_coalition_size=m)
+    env = BatchedTaskEnv(B, R.dim(ar), R.dim(tr), device=gpu_device).generate_instances(seeds, ar, tr, max_coalition_size=m)
     assert np.array_equal(env.n_agents, want["n_agents"]) and np.array_equal(env.n_tasks, want["n_tasks"])
-    _assert_same_instances(_held(env), want, (ranges, m))
+    assert_same_instances(held_instances(env), want, (ranges, m))
     env.generate_instances(torch.from_numpy(seeds.view(np.int64)).to(gpu_device), ar, tr, m)
-    _assert_same_instances(_held(env), want, (ranges, m))
+    assert_same_instances(held_instances(env), want, (ranges, m))
 
 
 # ------------------------------------------------------------------ 3. the fall-back inside the kernels that restart episodes
@@ -190,11 +186,11 @@ def _uniform_case(fixture_seeds, name, B, choice_base):
     stride = B
     inst_seeds, at = _renewing_batch(entries, B, stride, 7000)
     seeds = env_seeds(choice_base, 0, B)
-    chains = {b: IR._oracle_chain(A, T, inst_seeds[b], stride, int(seeds[b]), mcs) for b in range(B)}
+    chains = {b: R.oracle_chain(A, T, inst_seeds[b], stride, int(seeds[b]), mcs) for b in range(B)}
     for b, (k, e) in at.items():
         assert int(renewal_seeds(inst_seeds[b], k, stride)) == e["seed"]
         _, inst = _rejects(e)
-        assert np.array_equal(chains[b][1][k]["req"], inst["req"]) and np.array_equal(chains[b][1][k]["task_xy"], inst["task_xy"])
+        assert np.array_equal(chains[b][1][k][1]["req"], inst["req"]) and np.array_equal(chains[b][1][k][1]["task_xy"], inst["task_xy"])
     return A, T, mcs, inst_seeds, stride, seeds, chains
 
 
@@ -214,7 +210,7 @@ def test_persistent_rollout_renews_into_a_rejecting_seed(gpu_device, fixture_see
     env, ring = _make(gpu_device, B, A, T, inst_seeds, stride, mcs, member_cap)
     env.reset(seeds, observe=False)
     steps = env.rollout_random(episodes=EPISODES).cpu().numpy()
-    IR._assert_after_three(env, ring, chains, range(B), steps)
+    R.assert_after(env, ring, chains, steps)
 
 
 @pytest.mark.parametrize("route_log", [pytest.param(False, id="k_rn_step_fast"), pytest.param(True, id="route-log-k_rn_step")])
@@ -224,8 +220,8 @@ def test_lockstep_auto_reset_renews_into_a_rejecting_seed(gpu_device, fixture_se
     env, ring = _make(gpu_device, B, A, T, inst_seeds, stride, mcs, auto_reset=True, auto_reset_episodes=EPISODES)
     if route_log:
         env.enable_route_log()
-    dcount = IR._lockstep(env, seeds, 40)
-    IR._assert_after_three(env, ring, chains, range(B), dcount)
+    dcount = R.lockstep_to_end(env, seeds, 40)
+    R.assert_after(env, ring, chains, dcount)
     assert np.array_equal(env.status()["decisions"].cpu().numpy(), dcount)
 
 
@@ -237,7 +233,7 @@ def _sized_case(fixture_seeds, B, choice_base):
     stride = B
     inst_seeds, at = _renewing_batch(entries, B, stride, 17000)
     seeds = env_seeds(choice_base, 0, B)
-    chains = {b: SR._oracle_chain(ar, tr, inst_seeds[b], stride, int(seeds[b]), mcs) for b in range(B)}
+    chains = {b: R.oracle_chain(ar, tr, inst_seeds[b], stride, int(seeds[b]), mcs) for b in range(B)}
     for b, (k, e) in at.items():
         assert int(renewal_seeds(inst_seeds[b], k, stride)) == e["seed"]
         A, inst = _rejects(e)
@@ -248,7 +244,7 @@ def _sized_case(fixture_seeds, B, choice_base):
 
 def _assert_fixture_sizes(env, at):
     """The fixture seed also fixes the env's sizes: an env whose LAST restart drew it holds the fixture's A and T."""
-    held = SR._held(env)
+    held = R.held(env)
     last = [(b, e) for b, (k, e) in at.items() if k == EPISODES - 1]
     assert last
     for b, e in last:
@@ -258,19 +254,19 @@ def _assert_fixture_sizes(env, at):
 def test_size_renewing_rollout_renews_into_a_rejecting_seed(gpu_device, fixture_seeds):
     B = 8
     ar, tr, mcs, inst_seeds, stride, seeds, chains, at = _sized_case(fixture_seeds, B, 75)
-    env, ring = _make(gpu_device, B, SR._dim(ar), SR._dim(tr), inst_seeds, stride, mcs, ar=ar, tr=tr, renew_sizes=True)
+    env, ring = _make(gpu_device, B, R.dim(ar), R.dim(tr), inst_seeds, stride, mcs, ar=ar, tr=tr, renew_sizes=True)
     env.reset(seeds, observe=False)
     steps = env.rollout_random(episodes=EPISODES).cpu().numpy()
-    SR._assert_after_three(env, ring, chains, steps)
+    R.assert_after(env, ring, chains, steps)
     _assert_fixture_sizes(env, at)
 
 
 def test_size_renewing_lockstep_renews_into_a_rejecting_seed(gpu_device, fixture_seeds):
     B = 8
     ar, tr, mcs, inst_seeds, stride, seeds, chains, at = _sized_case(fixture_seeds, B, 77)
-    env, ring = _make(gpu_device, B, SR._dim(ar), SR._dim(tr), inst_seeds, stride, mcs, ar=ar, tr=tr, renew_sizes=True,
+    env, ring = _make(gpu_device, B, R.dim(ar), R.dim(tr), inst_seeds, stride, mcs, ar=ar, tr=tr, renew_sizes=True,
                       auto_reset=True, auto_reset_episodes=EPISODES)
-    dcount = SR._lockstep(env, seeds, 40)
-    SR._assert_after_three(env, ring, chains, dcount)
+    dcount = R.lockstep_to_end(env, seeds, 40)
+    R.assert_after(env, ring, chains, dcount)
     _assert_fixture_sizes(env, at)
     assert np.array_equal(env.status()["decisions"].cpu().numpy(), dcount)

@@ -94,7 +94,7 @@ def test_random_route_replays_known_answers(gpu_device, golden_dir):
     """tests/golden/replay_random.json: the reference's own execute_by_route results on random routes (surplus visitors
     released before they arrive -> non-monotone arrival lists, too few visitors, None routes, shuffled order)."""
     from dcmrta_amd.batched_env import BatchedTaskEnv
-    from test_oracle_golden import random_replay_cases
+    from fixtures_ref import random_replay_cases
     n_ok = 0
     for c, inst in random_replay_cases(golden_dir):
         env = BatchedTaskEnv(1, c["A"], c["T"], device=gpu_device)
@@ -124,7 +124,7 @@ def test_random_route_replays_on_the_register_resident_kernel(gpu_device, golden
     """The same reference known answers through replay_fast.hpp (member_cap <= 8 and the default placement select it for these
     shapes); cases in which a task collects more members than the slots hold are flagged DCM_FLAG_OVERFLOW and not compared."""
     from dcmrta_amd.batched_env import BatchedTaskEnv
-    from test_oracle_golden import random_replay_cases
+    from fixtures_ref import random_replay_cases
     n_ok = n_over = 0
     for c, inst in random_replay_cases(golden_dir):
         env = BatchedTaskEnv(1, c["A"], c["T"], device=gpu_device)
@@ -156,7 +156,7 @@ def test_generalised_visibility_schedule(gpu_device, golden_dir, oracle_lib):
     schedule under which all 500 tasks appear, against the oracle on a small batch."""
     from dcmrta_amd.batched_env import BatchedTaskEnv
     from dcmrta_amd.instances import generate_batch
-    from test_oracle_golden import schedule_cases
+    from fixtures_ref import schedule_cases
     n_ok = 0
     for c, inst in schedule_cases(golden_dir):
         env = BatchedTaskEnv(1, c["A"], c["T"], device=gpu_device)

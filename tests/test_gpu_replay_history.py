@@ -13,7 +13,7 @@ import numpy as np
 import pytest
 import torch
 
-from test_replay_history_golden import MODES, history
+from fixtures_ref import MODES, history
 
 pytestmark = pytest.mark.gpu
 KEYS_EXACT = ("finished", "time_start", "time_finish", "task_wait", "n_members", "travel_dist", "returned", "agent_wait")

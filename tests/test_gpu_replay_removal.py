@@ -276,7 +276,7 @@ def coverage(c, routes, batch, walked):
 
 def golden_spread_calls(oracle_lib, golden_dir):
     """(static comparable cases, removing calls, spread-rule calls) of tests/golden/replay_random.json under walk_static"""
-    from test_oracle_golden import random_replay_cases
+    from fixtures_ref import random_replay_cases
     n_cases = n_calls = n_spread = 0
     for c, inst in random_replay_cases(golden_dir):
         if c["reactive"] or c["status"] != "ok":

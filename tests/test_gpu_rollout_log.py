@@ -5,7 +5,6 @@ logging form (k_lg_rollout_fast) and the general one (k_lg_rollout_random), plai
 Yardsticks: the reference's own route / arrival / members / trajectory arrays (tests/golden/traj_*.npz), the reference's route_len of
 the 50A/200T traces, and beyond them the oracle's lists (OracleEnv.route).  Every comparison is exact: task ids, lengths, arrival
 times as f64 bit patterns."""
-import ctypes as C
 import functools
 import os
 
@@ -13,83 +12,14 @@ import numpy as np
 import pytest
 
 import helpers as H
+import oracle_ref as O
+from fixtures_ref import traj_fixture
+from forms import Forms
 
 pytestmark = pytest.mark.gpu
 
 ERR_STATE = -4
 POLICIES = ("random", "first", "nearest")
-
-
-def _opol(name):
-    import oracle
-    return {"random": oracle.POLICY_RANDOM, "first": oracle.POLICY_FIRST, "nearest": oracle.POLICY_NEAREST}[name]
-
-
-def _one(inst, b, t=None):
-    return dict(depot=inst["depot"][b], task_xy=inst["task_xy"][b, :t], req=inst["req"][b, :t], dur=inst["dur"][b, :t])
-
-
-def _play(a, t, one, seed, d0, policy, cap, mwt):
-    """One oracle episode of at most `cap` decisions (None: to its end) from decision counter d0.  Returns (the OracleEnv, whose
-    route() lists are those of the decisions taken; decisions taken; whether the episode ended).  The raw return value tells a cap
-    that cut the episode (-1) from an episode of exactly `cap` decisions."""
-    import oracle
-    o = oracle.OracleEnv(a, t, max_waiting_time=mwt).load(one["depot"], one["task_xy"], one["req"], one["dur"])
-    n = oracle.lib().orc_rollout(o._h, C.c_uint64(int(seed)), C.c_uint64(int(d0)), _opol(policy), 1 << 40 if cap is None else int(cap),
-                                 *([None] * 12))
-    return (o, int(cap), False) if n < 0 else (o, int(n), True)
-
-
-class _Sim:
-    """What the persistent kernels do with one env over a sequence of launches, in oracle episodes: an env that is in the middle of an
-    episode plays it to its end (one of the launch's `episodes`), a finished env restarts -- on instance inst_of(j) for its j-th
-    restart -- unless its budget is spent, and a spent budget stops it where it is.  `.o` is the OracleEnv of the episode the log
-    should hold."""
-
-    def __init__(self, a, t, inst_of, seed, policy, mwt=10.0):
-        self.a, self.t, self.inst_of, self.seed, self.policy, self.mwt = a, t, inst_of, seed, policy, mwt
-        self.j, self.d0, self.k, self.done, self.o = 0, 0, 0, False, None
-
-    def launch(self, episodes, budget):
-        left = None if budget < 0 else int(budget)
-        if self.policy != "random" and not self.mwt > 0.0 and left is None:
-            left = 0                                            # a greedy "no limit" on a max_waiting_time <= 0 handle counts as 0
-        taken = 0
-        for _ in range(episodes):
-            if self.done:
-                if left == 0:
-                    break
-                self.j, self.d0, self.k, self.done = self.j + 1, self.d0 + self.k, 0, False
-            elif left == 0:
-                break
-            o, k, ended = _play(self.a, self.t, self.inst_of(self.j), self.seed, self.d0, self.policy,
-                                None if left is None else self.k + left, self.mwt)
-            taken += k - self.k
-            if left is not None:
-                left -= k - self.k
-            self.o, self.k, self.done = o, k, ended
-            if left == 0:
-                break
-        return taken
-
-
-def _log(env):
-    return tuple(x.cpu().numpy() for x in env.rollout_routes())
-
-
-def _assert_log(log, b, sim, tag):
-    """Env b's rows against the oracle episode they should hold: the true lengths, the stored prefix of every list, nothing written
-    behind it, and nothing in the rows of agents the env does not have."""
-    task, arr, ln = log
-    cap = task.shape[2]
-    for a in range(task.shape[1]):
-        rt, ra = sim.o.route(a) if (a < sim.a and sim.o is not None) else (np.zeros(0, np.int32), np.zeros(0))
-        n = min(len(rt), cap)
-        assert ln[b, a] == len(rt), f"{tag} env{b} agent{a}: length {ln[b, a]} != {len(rt)}"
-        assert np.array_equal(task[b, a, :n], rt[:n].astype(np.int16)), f"{tag} env{b} agent{a}: route"
-        assert np.array_equal(arr[b, a, :n].view(np.uint64), ra[:n].view(np.uint64)), f"{tag} env{b} agent{a}: arrival times"
-        if a >= sim.a:
-            assert (task[b, a] == -2).all() and (arr[b, a] == 0.0).all(), f"{tag} env{b}: row of agent {a} beyond the env's size"
 
 
 # ---------------------------------------------------------------------------------------------------- 1. the reference's own lists
@@ -98,8 +28,7 @@ TRAJ = [("traj_5A8T_random_s3.npz", "random"), ("traj_6A9T_random_s5.npz", "rand
 
 @functools.lru_cache(maxsize=None)
 def _traj(name):
-    from test_host import _traj_fixture
-    return _traj_fixture(H.GOLDEN, name)
+    return traj_fixture(H.GOLDEN, name)
 
 
 def test_the_oracle_reproduces_the_trajectory_fixtures_under_its_own_policy():
@@ -111,7 +40,7 @@ def test_the_oracle_reproduces_the_trajectory_fixtures_under_its_own_policy():
         z, routes, _, _ = _traj(name)
         A, T = z["route"].shape[0], z["task_xy"].shape[0]
         o = oracle.OracleEnv(A, T).load(z["depot"], z["task_xy"], z["req"], z["dur"])
-        r = o.rollout(int(z["seed_e"]), 0, _opol(policy), cap_steps=4096, record=True)
+        r = o.rollout(int(z["seed_e"]), 0, O.opol(policy), cap_steps=4096, record=True)
         assert np.array_equal(r["action"], z["action"]), name
         for a, (rt, ra) in enumerate(routes):
             ot, oa = o.route(a)
@@ -132,7 +61,7 @@ def test_reference_routes_arrivals_members_and_trajectories(gpu_device, name, po
     env.load_instances(z["depot"][None], z["task_xy"][None], z["req"][None], z["dur"][None])
     env.reset(np.array([int(z["seed_e"])], np.uint64), observe=False)
     assert int(env.rollout(policy, episodes=1)[0]) == len(z["action"])
-    task, arr, ln = _log(env)
+    task, arr, ln = O.log(env)
     for a, (rt, ra) in enumerate(routes):
         assert ln[0, a] == len(rt) and list(task[0, a, :len(rt)]) == rt, (name, a)
         assert np.array_equal(arr[0, a, :len(rt)].view(np.uint64), np.array(ra, np.float64).view(np.uint64)), (name, a)
@@ -160,39 +89,7 @@ BIG_FORMS = {"4A700T-general-above-64KiB": (4, 700, 2, {}, None, -1)}
 
 
 CAP = 64
-
-
-@functools.lru_cache(maxsize=None)
-def _form_instances(form):
-    from dcmrta_amd.choice import env_seeds
-    from dcmrta_amd.instances import generate_batch, generate_batch_ranges
-    A, T, B, _, ranges, _ = {**FORMS, **BIG_FORMS}[form]
-    inst = generate_batch(B, A, T, base_seed=4000 + 3 * A + T) if ranges is None else generate_batch_ranges(range(4100, 4100 + B), *ranges)
-    return inst, env_seeds(37, 0, B)
-
-
-@functools.lru_cache(maxsize=None)
-def _form_sims(form, policy, episodes):
-    """The oracle's side of one launch of `episodes` episodes on a form: computed once, shared, never changed."""
-    A, T, B, kw, ranges, budget = FORMS[form]
-    inst, seeds = _form_instances(form)
-    sims, steps = [], []
-    for b in range(B):
-        a, t = (A, T) if ranges is None else (int(inst["n_agents"][b]), int(inst["n_tasks"][b]))
-        one = _one(inst, b, t)
-        s = _Sim(a, t, lambda j, one=one: one, seeds[b], policy, kw.get("max_waiting_time", 10.0))
-        steps.append(s.launch(episodes, budget))
-        sims.append(s)
-    return sims, np.array(steps, np.int64)
-
-
-def _form_env(gpu_device, form):
-    from dcmrta_amd.batched_env import BatchedTaskEnv
-    A, T, B, kw, _, _ = {**FORMS, **BIG_FORMS}[form]
-    inst, seeds = _form_instances(form)
-    env = BatchedTaskEnv(B, A, T, device=gpu_device, **kw).load_instances(**inst)
-    assert (env.record_bytes() > 65536) == (form in BIG_FORMS)
-    return env, seeds
+F = Forms(FORMS, BIG_FORMS, 4000, 4100, 37)                                  # base seeds: uniform instances, ragged ones, choice
 
 
 @pytest.mark.parametrize("policy", POLICIES)
@@ -201,8 +98,8 @@ def test_two_episodes_leave_the_second_episodes_lists(gpu_device, form, policy):
     """Two episodes in one launch, so that the restart's zeroing runs: the log holds the second episode's lists (on the
     max_waiting_time = 0 handle, whose launch carries a budget of 60 decisions: the lists of the decisions taken)."""
     budget = FORMS[form][5]
-    sims, ref_steps = _form_sims(form, policy, 2)
-    env, seeds = _form_env(gpu_device, form)
+    sims, ref_steps = F.sims(form, policy, 2)
+    env, seeds = F.env(gpu_device, form)
     # (the longest list here has 56 entries -- a greedy policy on the max_waiting_time = 0 handle -- so a log of 64 holds every one)
     assert max(len(s.o.route(a)[0]) for s in sims for a in range(s.a)) <= CAP
     env.enable_rollout_log(CAP)
@@ -211,9 +108,9 @@ def test_two_episodes_leave_the_second_episodes_lists(gpu_device, form, policy):
     assert np.array_equal(steps, ref_steps), (form, policy)
     if budget < 0:
         assert all(s.j == 1 and s.done for s in sims)                           # every env restarted once and finished
-    log = _log(env)
+    log = O.log(env)
     for b, s in enumerate(sims):
-        _assert_log(log, b, s, f"{form} {policy}")
+        O.assert_log(log, b, s, f"{form} {policy}")
 
 
 @pytest.mark.parametrize("name,policy", [("trace_50A200T_nearest_s0.npz", "nearest"), ("trace_50A200T_random_s0.npz", "random")])
@@ -225,11 +122,11 @@ def test_route_lengths_of_the_reference_50A200T_traces(gpu_device, name, policy)
     env.load_instances(*[tr[k][None] for k in ("depot", "task_xy", "req", "dur")])
     env.reset(np.array([int(tr["seed_e"])], np.uint64), observe=False)
     assert int(env.rollout(policy, episodes=1)[0]) == int(tr["n_steps"])
-    log = _log(env)
+    log = O.log(env)
     assert np.array_equal(log[2][0], tr["route_len"])
-    s = _Sim(50, 200, lambda j: _one({k: tr[k][None] for k in ("depot", "task_xy", "req", "dur")}, 0), int(tr["seed_e"]), policy)
+    s = O.Sim(50, 200, lambda j: O.one({k: tr[k][None] for k in ("depot", "task_xy", "req", "dur")}, 0), int(tr["seed_e"]), policy)
     s.launch(1, -1)
-    _assert_log(log, 0, s, name)
+    O.assert_log(log, 0, s, name)
 
 
 # ---------------------------------------------------------------------------------------------------- 3. budget stops
@@ -241,28 +138,28 @@ def test_budget_stops_hold_the_prefix_and_a_later_launch_carries_on(gpu_device, 
     last decision.  A second, unlimited launch then appends from the stored lengths (the envs stopped in mid-episode) or restarts (the
     finished ones) and leaves full lists."""
     A, T, B = FORMS[form][:3]
-    inst, seeds = _form_instances(form)
-    n0 = _form_sims(form, policy, 1)[1]                                         # length of every env's first episode
+    inst, seeds = F.instances(form)
+    n0 = F.sims(form, policy, 1)[1]                                         # length of every env's first episode
     e = 7 % B                                                                   # its budget ends exactly at the episode's last decision
     budgets = np.array([0, 1, 2, 7, 40, 85, -1, 0, 3, 120, -1, 0, 19, 64, 200, 1] if B == 16 else [40, 0], np.int64)
     budgets[e] = n0[e]
-    sims = [_Sim(A, T, lambda j, one=_one(inst, b): one, seeds[b], policy) for b in range(B)]
-    env, _ = _form_env(gpu_device, form)
+    sims = [O.Sim(A, T, lambda j, one=O.one(inst, b): one, seeds[b], policy) for b in range(B)]
+    env, _ = F.env(gpu_device, form)
     env.enable_rollout_log(CAP)
     env.reset(seeds, observe=False)
     steps = env.rollout(policy, episodes=2, max_decisions=budgets).cpu().numpy()
     assert np.array_equal(steps, np.array([s.launch(2, int(k)) for s, k in zip(sims, budgets)]))
     assert sims[e].done and sims[e].j == 0 and steps[e] == n0[e]                # stopped at the boundary: the first episode's log stays
     assert any(not s.done and 0 < s.k for s in sims)                            # ... and somebody stopped in mid-episode
-    log = _log(env)
+    log = O.log(env)
     for b, s in enumerate(sims):
-        _assert_log(log, b, s, f"{form} {policy} after the budgets")
+        O.assert_log(log, b, s, f"{form} {policy} after the budgets")
     steps = env.rollout(policy, episodes=1).cpu().numpy()
     assert np.array_equal(steps, np.array([s.launch(1, -1) for s in sims]))
     assert all(s.done for s in sims)
-    log = _log(env)
+    log = O.log(env)
     for b, s in enumerate(sims):
-        _assert_log(log, b, s, f"{form} {policy} after the second launch")
+        O.assert_log(log, b, s, f"{form} {policy} after the second launch")
 
 
 # ---------------------------------------------------------------------------------------------------- 4. overflow
@@ -270,15 +167,15 @@ def test_budget_stops_hold_the_prefix_and_a_later_launch_carries_on(gpu_device, 
 def test_a_log_of_four_counts_the_true_lengths_and_keeps_its_neighbours(gpu_device, policy):
     """cap = 4 at 20A/50T, where routes reach 9 to 13 entries: route_len counts them all, the first four of every list are right, and
     no row spills into the next agent's or the next env's (every row of the batch is compared)."""
-    sims, ref_steps = _form_sims("20A50T-fast", policy, 1)
-    env, seeds = _form_env(gpu_device, "20A50T-fast")
+    sims, ref_steps = F.sims("20A50T-fast", policy, 1)
+    env, seeds = F.env(gpu_device, "20A50T-fast")
     env.enable_rollout_log(4)
     env.reset(seeds, observe=False)
     assert np.array_equal(env.rollout(policy, episodes=1).cpu().numpy(), ref_steps)
-    log = _log(env)
+    log = O.log(env)
     assert log[0].shape == (16, 20, 4) and log[2].max() >= 9 and (log[2] > 4).sum() > 16 * 20 // 2
     for b, s in enumerate(sims):
-        _assert_log(log, b, s, f"cap 4 {policy}")
+        O.assert_log(log, b, s, f"cap 4 {policy}")
     with pytest.raises(ValueError, match=r"enable_rollout_log\(cap\)"):
         env.rollout_plan()
 
@@ -297,14 +194,14 @@ def test_the_log_under_instance_renewal_is_the_third_instances(gpu_device, A, T,
     env.enable_rollout_log(CAP)
     env.reset(seeds, observe=False)
     steps = env.rollout(policy, episodes=3).cpu().numpy()
-    log, idx = _log(env), env.instance_index().cpu().numpy()
+    log, idx = O.log(env), env.instance_index().cpu().numpy()
     held = {k: v.cpu().numpy() for k, v in env.instances().items() if v is not None}
     for b in range(B):
-        s = _Sim(A, T, lambda j, b=b: generate_instance(A, T, int(renewal_seeds(base + b, j, B))), seeds[b], policy)
+        s = O.Sim(A, T, lambda j, b=b: generate_instance(A, T, int(renewal_seeds(base + b, j, B))), seeds[b], policy)
         assert steps[b] == s.launch(3, -1) and s.j == 2 and idx[b] == 2, b
         third = s.inst_of(2)
         assert all(np.array_equal(held[k][b], third[k]) for k in ("depot", "task_xy", "req", "dur")), b
-        _assert_log(log, b, s, f"renewal {A}A{T}T {policy}")
+        O.assert_log(log, b, s, f"renewal {A}A{T}T {policy}")
 
 
 # ---------------------------------------------------------------------------------------------------- 6. refusal
@@ -323,7 +220,7 @@ def test_a_size_renewing_launch_is_refused_while_the_log_is_set(gpu_device):
                                            r"dcm_set_rollout_log" % ERR_STATE):
             env.rollout(policy, episodes=2)
         assert np.array_equal(env.clone_state().cpu().numpy(), before), policy
-    assert (_log(env)[2] == 0).all()
+    assert (O.log(env)[2] == 0).all()
     env.enable_rollout_log(0)                                                   # without the log the size-renewing random launch runs
     assert int(env.rollout("random", episodes=2).sum()) > 0
     with pytest.raises(DcmError, match="rollout log is off"):
@@ -339,7 +236,7 @@ def test_a_launch_with_the_log_returns_what_it_returns_without(gpu_device, form,
     budget = {**FORMS, **BIG_FORMS}[form][5]
     out = []
     for logged in (False, True):
-        env, seeds = _form_env(gpu_device, form)
+        env, seeds = F.env(gpu_device, form)
         ring = env.enable_return_log(2)
         if logged:
             env.enable_rollout_log(CAP)
@@ -351,18 +248,18 @@ def test_a_launch_with_the_log_returns_what_it_returns_without(gpu_device, form,
         if logged:
             task, arr, ln = (x.cpu().numpy() for x in env.routes())
             assert (ln == 0).all() and (task == -2).all() and (arr == 0.0).all()     # the persistent launch never writes the lockstep log
-            assert int(_log(env)[2].sum()) > 0
+            assert int(O.log(env)[2].sum()) > 0
     assert int(out[0][0].sum()) > 0
     for i, (a, b) in enumerate(zip(*out)):
         assert a.shape == b.shape and np.array_equal(a.view(np.uint8), b.view(np.uint8)), (form, policy, i)
 
 
 def test_the_lockstep_api_never_writes_the_rollout_log(gpu_device):
-    env, seeds = _form_env(gpu_device, "10A20T-wide")
+    env, seeds = F.env(gpu_device, "10A20T-wide")
     env.enable_rollout_log(16)
     env.enable_route_log(16)
     H.run_lockstep(env, seeds, lambda b, i, m, l: H.host_random_action(m, int(seeds[b]), i))
-    task, arr, ln = _log(env)
+    task, arr, ln = O.log(env)
     assert (ln == 0).all() and (task == -2).all() and (arr == 0.0).all()
     assert int(env.routes()[2].sum()) > 0                                       # ... while its own log filled
 
@@ -381,7 +278,7 @@ def test_a_nearest_plan_replays_like_the_oracle_and_round_trips_through_yaml(gpu
     env.reset(seeds, observe=False)
     env.rollout("nearest", episodes=1)
     plan = env.rollout_plan()
-    ln = _log(env)[2]
+    ln = O.log(env)[2]
     assert [[len(r) for r in p] for p in plan] == ln.tolist() and ln.sum() > B * A
     assert env.rollout_plan(2) == plan[2]
     for b in range(B):                                                          # Worker.generate_route's file (worker.py:244-251)

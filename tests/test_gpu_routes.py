@@ -47,8 +47,8 @@ def test_generate_traj_from_device_state(gpu_device, golden_dir, name):
     equals the trajectories the reference produced for the same episode (recorded actions, protocol leaders/followers)."""
     from dcmrta_amd.batched_env import BatchedTaskEnv
     from dcmrta_amd.trajectory import generate_traj
-    from test_host import _traj_fixture
-    z, routes, members, ref = _traj_fixture(golden_dir, name)
+    from fixtures_ref import traj_fixture
+    z, routes, members, ref = traj_fixture(golden_dir, name)
     A, T = z["route"].shape[0], z["task_xy"].shape[0]
     env = BatchedTaskEnv(1, A, T, device=gpu_device).enable_route_log(cap=64)
     env.load_instances(z["depot"][None], z["task_xy"][None], z["req"][None], z["dur"][None])

@@ -6,6 +6,8 @@ import numpy as np
 import pytest
 import torch
 
+from fixtures_ref import replay_recorded
+
 pytestmark = pytest.mark.gpu
 
 
@@ -57,33 +59,12 @@ def test_job_contract_and_replay(gpu_device, oracle_lib, twin):
         assert np.allclose(a, np.float32(summary[b, 0] - greedy[b, 0]))          # worker.py:92-101
     # the greedy self-critic twin (worker.py:89,200-235: argmax of the same net on the same instance) is an episode of the
     # reference env too: replay its recorded decisions through the oracle
-    _replay_recorded(oracle_lib, r.last["greedy_rec"], greedy, inst, seeds, A, T)
+    replay_recorded(oracle_lib, r.last["greedy_rec"], greedy, inst, seeds, A, T)
     # ... and the argmax really was the greedy choice of the net on the recorded observations
     g = r.last["greedy_rec"]
     act = g["active"]
     lp = r.localNetwork(g["tasks"][act], g["agents"][act], g["mask"][act])
     assert (lp.gather(1, g["action"][act].unsqueeze(1))[:, 0] >= lp.max(1).values - 1e-4).all()
-
-
-def _replay_recorded(oracle_lib, rec, summary, inst, seeds, A, T, n_agents=None, n_tasks=None):
-    """Every episode of a recorded batched rollout ([S, B, ...] experience + `active`) through the oracle with the recorded
-    actions injected: leaders, observations, masks, reward and metrics must be the reference env's."""
-    act = rec["active"].cpu().numpy()
-    ag, tk, mk, ac, ld = (rec[k].cpu().numpy() for k in ("agents", "tasks", "mask", "action", "leader"))
-    summary = np.asarray(summary)
-    for b in range(act.shape[1]):
-        a = int(n_agents[b]) if n_agents is not None else A
-        t = int(n_tasks[b]) if n_tasks is not None else T
-        sel = act[:, b]
-        o = oracle_lib.OracleEnv(a, t).load(inst["depot"][b], inst["task_xy"][b, :t], inst["req"][b, :t], inst["dur"][b, :t])
-        ref = o.rollout(int(seeds[b]), 0, oracle_lib.POLICY_INJECTED, cap_steps=8192, inj_action=ac[sel, b].astype(np.int32))
-        assert ref["n_steps"] == int(sel.sum()), b
-        assert np.array_equal(ref["leader"], ld[sel, b]), b
-        assert np.array_equal(ref["agents_obs"], ag[sel, b, :a]) and np.array_equal(ref["tasks_obs"], tk[sel, b, :t + 1]), b
-        assert np.array_equal(ref["mask"], mk[sel, b, :t + 1].astype(np.uint8)), b
-        assert ref["reward"] == summary[b, 0], b
-        for i in range(6):
-            assert ref["metrics"][i] == summary[b, 2 + i], (b, i)
 
 
 def test_testing_greedy_is_deterministic(gpu_device):
@@ -179,7 +160,7 @@ def test_run_test_and_run_test_is(gpu_device, oracle_lib, golden_dir):
             assert np.array_equal(m[name], sm[:, 2 + k])
         if not is_mode:
             # leader-follower mode (worker.py:114-157): the recorded greedy episodes are episodes of the reference env
-            _replay_recorded(oracle_lib, rec, sm, sub, seeds, A, 50)
+            replay_recorded(oracle_lib, rec, sm, sub, seeds, A, 50)
         else:
             # individual selection (worker.py:159-198): the reference loop restated on the oracle with the recorded actions
             act, ac, ld = (rec[k].cpu().numpy() for k in ("active", "action", "leader"))
@@ -401,7 +382,7 @@ def test_tuned_gemms_job_replays_through_the_oracle(gpu_device, oracle_lib, tmp_
         r.job(w, w, episodeNumber=0, agents_num=A, tasks_num=T, as_lists=False)
         assert not tunable.tuning_is_enabled()                       # tuning only around the warm-up forwards
         inst = generate_batch(B, A, T, base_seed=3, first=0)
-        _replay_recorded(oracle_lib, r.last["greedy_rec"], r.last["greedy_summary"].cpu().numpy(), inst, env_seeds(3, 0, B), A, T)
+        replay_recorded(oracle_lib, r.last["greedy_rec"], r.last["greedy_summary"].cpu().numpy(), inst, env_seeds(3, 0, B), A, T)
     finally:
         r.close()
         tunable.enable(False)

@@ -3,60 +3,22 @@ an env that restarts an episode inside a kernel draws its next instance WITH its
 a fresh TaskEnv(agents_range, tasks_range, ..., seed=...) with the tuple ranges of parameters.py:15-16 (worker.py:32,
 env/task_env.py:58-65).
 
-The yardstick is the oracle with a new host instance per episode, as in test_gpu_instance_renewal, whose helpers are the model:
+The yardstick is the oracle with a new host instance per episode (renewal_ref.oracle_chain), as in test_gpu_instance_renewal:
 episode k of env b plays generate_instance_ranges(agents_range, tasks_range, renewal_seeds(base + b, k, stride)) on an
 OracleEnv(A_k, T_k), with the decision counter running across the episodes.  Every comparison is array_equal."""
-import functools
-
 import numpy as np
 import pytest
 import torch
 
 import helpers as H
+import renewal_ref as R
+from renewal_ref import EPISODES, M64
 
 pytestmark = pytest.mark.gpu
 
-M64 = 1 << 64
 GAMMA = 0x9E3779B97F4A7C15
-EPISODES = 3
 ERR_STATE = -4
 WRAP_STRIDE = (1 << 63) + 12345          # two of them pass 2^64
-
-
-def _dim(r):
-    return int(r[1]) if isinstance(r, tuple) else int(r)
-
-
-def _inst_seeds(base, B):
-    return np.array([(base + b) % M64 for b in range(B)], dtype=np.uint64)
-
-
-@functools.lru_cache(maxsize=None)
-def _host_instance(ar, tr, seed, mcs):
-    from dcmrta_amd.instances import generate_instance_ranges
-    return generate_instance_ranges(ar, tr, int(seed), max_coalition_size=mcs)
-
-
-@functools.lru_cache(maxsize=None)
-def _oracle_chain(ar, tr, inst_seed, stride, choice_seed, mcs=5, n=EPISODES):
-    """Episodes 0..n-1 of one env under size renewal: (rollout results, (A_k, instance) per episode); computed once per env and shared."""
-    import oracle
-    from dcmrta_amd.instances import renewal_seeds
-    oracle.build()
-    eps, insts, d0 = [], [], 0
-    for k in range(n):
-        A, inst = _host_instance(ar, tr, int(renewal_seeds(inst_seed, k, stride)), mcs)
-        T = inst["req"].shape[0]
-        r = oracle.OracleEnv(A, T).load(inst["depot"], inst["task_xy"], inst["req"], inst["dur"]) \
-            .rollout(int(choice_seed), d0, oracle.POLICY_RANDOM, cap_steps=20000, record=False)
-        eps.append(dict(n_steps=r["n_steps"], row=np.array([r["reward"], float(r["finished"].sum()), *r["metrics"][:6]], np.float64)))
-        insts.append((A, inst))
-        d0 += r["n_steps"]
-    return eps, insts
-
-
-def _chains(ar, tr, B, base, stride, choice_seeds, mcs=5):
-    return {b: _oracle_chain(ar, tr, (base + b) % M64, stride, int(choice_seeds[b]), mcs) for b in range(B)}
 
 
 def _size_table(ar, tr, B, base, stride, mcs=5, n=EPISODES):
@@ -66,7 +28,7 @@ def _size_table(ar, tr, B, base, stride, mcs=5, n=EPISODES):
     sz = np.zeros((n, B, 2), np.int64)
     for k in range(n):
         for b in range(B):
-            A, inst = _host_instance(ar, tr, int(renewal_seeds((base + b) % M64, k, stride)), mcs)
+            A, inst = R.host_instance(ar, tr, int(renewal_seeds((base + b) % M64, k, stride)), mcs)
             sz[k, b] = (A, inst["req"].shape[0])
     for dim, r in ((0, ar), (1, tr)):
         d = np.diff(sz[:, :, dim], axis=0)
@@ -75,47 +37,6 @@ def _size_table(ar, tr, B, base, stride, mcs=5, n=EPISODES):
         else:
             assert not d.any()
     return sz
-
-
-def _make(gpu_device, B, ar, tr, base, stride, mcs=5, member_cap=5, renew_sizes=True, **kw):
-    """A flagged handle at the ranges' maxima with generated instances base + 0..B-1, renewal on, a return log of EPISODES columns."""
-    from dcmrta_amd.batched_env import BatchedTaskEnv
-    env = BatchedTaskEnv(B, _dim(ar), _dim(tr), device=gpu_device, member_cap=member_cap, renew_sizes=renew_sizes, **kw)
-    env.generate_instances(_inst_seeds(base, B), agents_range=ar, tasks_range=tr, max_coalition_size=mcs)
-    if stride is not None:
-        env.set_instance_renewal(stride)
-    ring = env.enable_return_log(EPISODES)
-    return env, ring
-
-
-def _held(env):
-    return {k: v.cpu().numpy() for k, v in env.instances().items() if v is not None}
-
-
-def _assert_instance(held, b, sized_inst):
-    """Env b holds this (A, instance), padded as instances.generate_batch_ranges pads (xy 0, req 1, dur 0 beyond the env's T)."""
-    A, inst = sized_inst
-    t = inst["req"].shape[0]
-    assert held["n_agents"][b] == A and held["n_tasks"][b] == t, (b, held["n_agents"][b], held["n_tasks"][b], A, t)
-    assert np.array_equal(held["depot"][b], inst["depot"]), b
-    assert np.array_equal(held["task_xy"][b, :t], inst["task_xy"]) and not held["task_xy"][b, t:].any(), b
-    assert np.array_equal(held["req"][b, :t], inst["req"]) and (held["req"][b, t:] == 1).all(), b
-    assert np.array_equal(held["dur"][b, :t], inst["dur"]) and not held["dur"][b, t:].any(), b
-
-
-def _assert_after_three(env, ring, chains, steps=None):
-    """What every path must leave after three episodes: the three returns, the last episode's summary row, index 2, instance 2 with
-    its sizes, the decision count."""
-    sm, rl, idx, held = env.summary().cpu().numpy(), ring.cpu().numpy(), env.instance_index().cpu().numpy(), _held(env)
-    assert np.array_equal(env.episodes().cpu().numpy(), np.full(env.B, EPISODES))
-    for b in range(env.B):
-        eps, insts = chains[b]
-        assert np.array_equal(rl[b], np.array([e["row"][0] for e in eps])), b
-        assert np.array_equal(sm[b], eps[-1]["row"], equal_nan=True), b
-        assert idx[b] == EPISODES - 1, (b, idx[b])
-        _assert_instance(held, b, insts[-1])
-        if steps is not None:
-            assert steps[b] == sum(e["n_steps"] for e in eps), b
 
 
 # agents range, tasks range, batch, member_cap / max_coalition_size, stride (None = B), base seed: one case per kernel class of
@@ -140,12 +61,12 @@ def test_persistent_rollout_plays_new_sizes_every_episode(gpu_device, ar, tr, B,
     stride = B if stride is None else stride
     _size_table(ar, tr, B, base, stride, mcs)
     seeds = env_seeds(61, 0, B)
-    env, ring = _make(gpu_device, B, ar, tr, base, stride, mcs, member_cap)
-    if _dim(tr) == 700:
+    env, ring = R.make(gpu_device, B, ar, tr, base, stride, mcs, member_cap)
+    if R.dim(tr) == 700:
         assert env.record_bytes() > 65536
     env.reset(seeds, observe=False)
     steps = env.rollout_random(episodes=EPISODES).cpu().numpy()
-    _assert_after_three(env, ring, _chains(ar, tr, B, base, stride, seeds, mcs), steps)
+    R.assert_after(env, ring, R.chains(ar, tr, B, base, stride, seeds, mcs), steps)
 
 
 def test_split_calls_give_the_same_results(gpu_device):
@@ -155,37 +76,37 @@ def test_split_calls_give_the_same_results(gpu_device):
     ar, tr, B, base = (3, 20), (5, 50), 32, 18100
     _size_table(ar, tr, B, base, B)
     seeds = env_seeds(61, 0, B)
-    chains = _chains(ar, tr, B, base, B, seeds)
+    chains = R.chains(ar, tr, B, base, B, seeds)
     n0 = np.array([chains[b][0][0]["n_steps"] for b in range(B)], np.int64)
     n1 = np.array([chains[b][0][1]["n_steps"] for b in range(B)], np.int64)
     # three calls of one episode each
-    env, ring = _make(gpu_device, B, ar, tr, base, B)
+    env, ring = R.make(gpu_device, B, ar, tr, base, B)
     env.reset(seeds, observe=False)
     steps = sum(env.rollout_random(episodes=1).cpu().numpy() for _ in range(EPISODES))
-    _assert_after_three(env, ring, chains, steps)
+    R.assert_after(env, ring, chains, steps)
     # a budget that ends in the middle of episode 1 (every env its own), then the rest: the pending episode counts as one
-    env, ring = _make(gpu_device, B, ar, tr, base, B)
+    env, ring = R.make(gpu_device, B, ar, tr, base, B)
     env.reset(seeds, observe=False)
     s1 = env.rollout_random(episodes=EPISODES, max_decisions=n0 + n1 // 2).cpu().numpy()
     assert np.array_equal(s1, n0 + n1 // 2)
     assert np.array_equal(env.instance_index().cpu().numpy(), np.ones(B, np.int64))
-    held = _held(env)
+    held = R.held(env)
     for b in range(B):
-        _assert_instance(held, b, chains[b][1][1])
+        R.assert_instance(held, b, chains[b][1][1])
     s2 = env.rollout_random(episodes=2).cpu().numpy()
-    _assert_after_three(env, ring, chains, s1 + s2)
+    R.assert_after(env, ring, chains, s1 + s2)
     # a budget that runs out exactly at the end of episode 0: the finished episode's instance, sizes and results stay
-    env, ring = _make(gpu_device, B, ar, tr, base, B)
+    env, ring = R.make(gpu_device, B, ar, tr, base, B)
     env.reset(seeds, observe=False)
     s1 = env.rollout_random(episodes=EPISODES, max_decisions=n0).cpu().numpy()
     assert np.array_equal(s1, n0)
     assert np.array_equal(env.instance_index().cpu().numpy(), np.zeros(B, np.int64))
-    held, sm = _held(env), env.summary().cpu().numpy()
+    held, sm = R.held(env), env.summary().cpu().numpy()
     for b in range(B):
-        _assert_instance(held, b, chains[b][1][0])
+        R.assert_instance(held, b, chains[b][1][0])
         assert np.array_equal(sm[b], chains[b][0][0]["row"], equal_nan=True), b
     s2 = env.rollout_random(episodes=2).cpu().numpy()
-    _assert_after_three(env, ring, chains, s1 + s2)
+    R.assert_after(env, ring, chains, s1 + s2)
 
 
 @pytest.mark.parametrize("ar,tr,B,base", [
@@ -203,15 +124,15 @@ def test_stored_observations_after_a_size_change(gpu_device, ar, tr, B, base):
     sz = _size_table(ar, tr, B, base, B)
     assert (sz[1] > sz[0]).any() and (sz[1] < sz[0]).any()
     seeds = env_seeds(61, 0, B)
-    chains = _chains(ar, tr, B, base, B, seeds)
+    chains = R.chains(ar, tr, B, base, B, seeds)
     n0 = np.array([chains[b][0][0]["n_steps"] for b in range(B)], np.int64)
     assert all(chains[b][0][1]["n_steps"] >= J for b in range(B))
-    x, _ = _make(gpu_device, B, ar, tr, base, B)
+    x, _ = R.make(gpu_device, B, ar, tr, base, B)
     x.reset(seeds, observe=False)
     sx = x.rollout_random(episodes=EPISODES, max_decisions=n0 + J).cpu().numpy()
     assert np.array_equal(sx, n0 + J)
-    y = BatchedTaskEnv(B, _dim(ar), _dim(tr), device=gpu_device)
-    y.generate_instances(renewal_seeds(_inst_seeds(base, B), 1, B), agents_range=ar, tasks_range=tr)
+    y = BatchedTaskEnv(B, R.dim(ar), R.dim(tr), device=gpu_device)
+    y.generate_instances(renewal_seeds(R.inst_seeds(base, B), 1, B), agents_range=ar, tasks_range=tr)
     y.reset(np.array([(int(seeds[b]) + GAMMA * int(n0[b])) % M64 for b in range(B)], dtype=np.uint64), observe=False)
     sy = y.rollout_random(episodes=1, max_decisions=J).cpu().numpy()
     assert np.array_equal(sy, np.full(B, J))
@@ -222,28 +143,6 @@ def test_stored_observations_after_a_size_change(gpu_device, ar, tr, B, base):
     mask = x._mask.cpu().numpy()
     for b in range(B):
         assert (mask[b, sz[1, b, 1] + 1:] == 1).all() and (x._agents[b, sz[1, b, 0]:].cpu().numpy() == -1.0).all(), b
-
-
-def _lockstep(env, seeds, read_summary_every=0, policy=None):
-    """Step an auto-resetting handle until every env is inactive; actions from the choice protocol's host mirror."""
-    B = env.B
-    obs = env.reset(seeds)
-    dcount = np.zeros(B, np.int64)
-    for s in range(4001):
-        active = obs.active.cpu().numpy()
-        if not active.any():
-            break
-        assert s < 4000, "envs still active after 4000 steps"
-        if policy is None:
-            mk = obs.mask.cpu().numpy().astype(np.uint8)
-            act = np.array([H.host_random_action(mk[b], int(seeds[b]), int(dcount[b])) if active[b] else 0 for b in range(B)], np.int32)
-        else:
-            act = policy(obs)
-        obs = env.step(act)
-        dcount += active
-        if read_summary_every and s % read_summary_every == read_summary_every - 1:
-            env.summary()
-    return dcount
 
 
 @pytest.mark.parametrize("ar,tr,B,base,read_every", [
@@ -257,11 +156,11 @@ def test_lockstep_auto_reset_renews_sizes(gpu_device, ar, tr, B, base, read_ever
     from dcmrta_amd.choice import env_seeds
     _size_table(ar, tr, B, base, B)
     seeds = env_seeds(63, 0, B)
-    env, ring = _make(gpu_device, B, ar, tr, base, B, auto_reset=True, auto_reset_episodes=EPISODES)
-    if _dim(tr) == 700:
+    env, ring = R.make(gpu_device, B, ar, tr, base, B, auto_reset=True, auto_reset_episodes=EPISODES)
+    if R.dim(tr) == 700:
         assert env.record_bytes() > 65536
-    dcount = _lockstep(env, seeds, read_every)
-    _assert_after_three(env, ring, _chains(ar, tr, B, base, B, seeds), dcount)
+    dcount = R.lockstep_to_end(env, seeds, read_every)
+    R.assert_after(env, ring, R.chains(ar, tr, B, base, B, seeds), dcount)
     assert np.array_equal(env.status()["decisions"].cpu().numpy(), dcount)
 
 
@@ -274,7 +173,7 @@ def test_first_observation_after_a_size_renewal_is_the_new_instances(gpu_device)
     ar, tr, B, base = (3, 20), (5, 50), 64, 19600
     sz = _size_table(ar, tr, B, base, B, n=2)
     seeds = env_seeds(65, 0, B)
-    env, _ = _make(gpu_device, B, ar, tr, base, B, auto_reset=True, auto_reset_episodes=2)
+    env, _ = R.make(gpu_device, B, ar, tr, base, B, auto_reset=True, auto_reset_episodes=2)
     obs = env.reset(seeds)
     dcount, seen, got = np.zeros(B, np.int64), np.zeros(B, bool), {}
     for s in range(4000):
@@ -291,7 +190,7 @@ def test_first_observation_after_a_size_renewal_is_the_new_instances(gpu_device)
         if seen.all():
             break
     assert seen.all()
-    twin = BatchedTaskEnv(B, _dim(ar), _dim(tr), device=gpu_device).generate_instances(_inst_seeds(base + B, B), agents_range=ar, tasks_range=tr)
+    twin = BatchedTaskEnv(B, R.dim(ar), R.dim(tr), device=gpu_device).generate_instances(R.inst_seeds(base + B, B), agents_range=ar, tasks_range=tr)
     assert np.array_equal(twin.n_agents, sz[1, :, 0]) and np.array_equal(twin.n_tasks, sz[1, :, 1])
     tobs = twin.reset(np.array([(int(seeds[b]) + GAMMA * got[b][0]) % M64 for b in range(B)], dtype=np.uint64))
     ta, tt, tm, tl = tobs.agents.cpu().numpy(), tobs.tasks.cpu().numpy(), tobs.mask.cpu().numpy(), tobs.leader.cpu().numpy()
@@ -307,20 +206,20 @@ def test_captured_step_loop_renews_sizes_like_the_eager_loop(gpu_device):
     _size_table(ar, tr, B, base, B)
     seeds = env_seeds(67, 0, B)
     policy = lambda obs: torch.argmax((~obs.mask).to(torch.int32), dim=1).to(torch.int32)
-    eager, ering = _make(gpu_device, B, ar, tr, base, B, auto_reset=True, auto_reset_episodes=EPISODES)
-    _lockstep(eager, seeds, policy=policy)
-    env, ring = _make(gpu_device, B, ar, tr, base, B, auto_reset=True, auto_reset_episodes=EPISODES)
+    eager, ering = R.make(gpu_device, B, ar, tr, base, B, auto_reset=True, auto_reset_episodes=EPISODES)
+    R.lockstep_to_end(eager, seeds, policy=policy)
+    env, ring = R.make(gpu_device, B, ar, tr, base, B, auto_reset=True, auto_reset_episodes=EPISODES)
     GraphedRollout(env, policy, check_every=8).run(seeds, max_steps=4000)
     assert np.array_equal(env.episodes().cpu().numpy(), np.full(B, EPISODES))
     assert np.array_equal(ring.cpu().numpy(), ering.cpu().numpy())
     assert np.array_equal(env.summary().cpu().numpy(), eager.summary().cpu().numpy(), equal_nan=True)
     assert np.array_equal(env.instance_index().cpu().numpy(), np.full(B, EPISODES - 1))
-    a, b = _held(env), _held(eager)
+    a, b = R.held(env), R.held(eager)
     assert all(np.array_equal(a[k], b[k]) for k in a)
     # ... and the held instances are instance 2 with its sizes
     from dcmrta_amd.instances import renewal_seeds
     for e in range(B):
-        _assert_instance(a, e, _host_instance(ar, tr, int(renewal_seeds((base + e) % M64, 2, B)), 5))
+        R.assert_instance(a, e, R.host_instance(ar, tr, int(renewal_seeds((base + e) % M64, 2, B)), 5))
     assert not np.array_equal(ering.cpu().numpy()[:, 0], ering.cpu().numpy()[:, 1])
 
 
@@ -330,31 +229,31 @@ def test_clone_and_restore_carry_the_sizes(gpu_device):
     ar, tr, B, base = (3, 20), (5, 50), 16, 18100
     seeds = env_seeds(61, 0, B)
     _size_table(ar, tr, B, base, 32)
-    chains = _chains(ar, tr, B, base, 32, seeds)                   # (the first 16 envs of the B = 32 case: stride 32)
-    env, ring = _make(gpu_device, B, ar, tr, base, 32)
+    chains = R.chains(ar, tr, B, base, 32, seeds)                   # (the first 16 envs of the B = 32 case: stride 32)
+    env, ring = R.make(gpu_device, B, ar, tr, base, 32)
     env.reset(seeds, observe=False)
     s0 = env.rollout_random(episodes=1, max_decisions=5).cpu().numpy()           # in episode 0
     assert all(chains[b][0][0]["n_steps"] > 5 for b in range(B))
     snap = env.clone_state()
     # the snapshot of a flagged handle with a ragged batch holds the per-env sizes: 8 B bytes more than an unflagged handle's
-    plain = BatchedTaskEnv(B, _dim(ar), _dim(tr), device=gpu_device).generate_instances(_inst_seeds(base, B), agents_range=ar, tasks_range=tr)
+    plain = BatchedTaskEnv(B, R.dim(ar), R.dim(tr), device=gpu_device).generate_instances(R.inst_seeds(base, B), agents_range=ar, tasks_range=tr)
     plain.reset(seeds, observe=False)
     assert snap.numel() == plain.clone_state().numel() + 8 * B
     s1 = env.rollout_random(episodes=EPISODES).cpu().numpy()                     # into episode 2
-    _assert_after_three(env, ring, chains, s0 + s1)
-    first = (env.summary().clone(), ring.clone(), _held(env))
+    R.assert_after(env, ring, chains, s0 + s1)
+    first = (env.summary().clone(), ring.clone(), R.held(env))
     env.restore_state(snap)
     assert np.array_equal(env.instance_index().cpu().numpy(), np.zeros(B, np.int64))
-    held = _held(env)
+    held = R.held(env)
     for b in range(B):
-        _assert_instance(held, b, chains[b][1][0])
+        R.assert_instance(held, b, chains[b][1][0])
     ring.fill_(float("nan"))
     s2 = env.rollout_random(episodes=EPISODES).cpu().numpy()
     assert np.array_equal(s2, s1)
     assert torch.equal(env.summary().view(torch.int64), first[0].view(torch.int64)) and torch.equal(ring.view(torch.int64), first[1].view(torch.int64))
-    again = _held(env)
+    again = R.held(env)
     assert all(np.array_equal(again[k], first[2][k]) for k in again)
-    _assert_after_three(env, ring, chains, s0 + s2)
+    R.assert_after(env, ring, chains, s0 + s2)
 
 
 def test_state_rules(gpu_device):
@@ -363,7 +262,7 @@ def test_state_rules(gpu_device):
     from dcmrta_amd.choice import env_seeds
     from dcmrta_amd.instances import generate_batch_ranges, generate_batch
     ar, tr, B = (3, 12), (5, 23), 8
-    A, T = _dim(ar), _dim(tr)
+    A, T = R.dim(ar), R.dim(tr)
     seeds = env_seeds(66, 0, B)
     env = BatchedTaskEnv(B, A, T, device=gpu_device, renew_sizes=True)
     setter = lambda stride: env._lib.dcm_set_instance_renewal(env._h, stride)
@@ -386,12 +285,12 @@ def test_state_rules(gpu_device):
     assert setter(B) == ERR_STATE
 
     def two_episodes_change_nothing():
-        before = _held(env)
+        before = R.held(env)
         env.reset(seeds, observe=False)
         env.rollout_random(episodes=2)
         assert np.array_equal(env.episodes().cpu().numpy(), np.full(B, 2))
         assert np.array_equal(env.instance_index().cpu().numpy(), np.zeros(B, np.int64))
-        after = _held(env)
+        after = R.held(env)
         assert all(np.array_equal(before[k], after[k]) for k in before)
 
     # on, then a new generate_instances / load_instances turn it off
@@ -411,15 +310,15 @@ def test_state_rules(gpu_device):
     assert np.array_equal(env.instance_index().cpu().numpy(), np.ones(B, np.int64))
     env.reset(seeds, observe=False)
     assert np.array_equal(env.instance_index().cpu().numpy(), np.ones(B, np.int64))
-    held = _held(env)
+    held = R.held(env)
     for b in range(B):
-        _assert_instance(held, b, _host_instance(ar, tr, 400 + b + B, 5))
+        R.assert_instance(held, b, R.host_instance(ar, tr, 400 + b + B, 5))
     assert np.array_equal(held["n_agents"], sz[1, :, 0]) and np.array_equal(held["n_tasks"], sz[1, :, 1])
     # stride 0 after size renewals: the next two episodes stay on the held instance and sizes, index 1
     assert setter(0) == 0
     env.rollout_random(episodes=2)
     assert np.array_equal(env.instance_index().cpu().numpy(), np.ones(B, np.int64))
-    after = _held(env)
+    after = R.held(env)
     assert all(np.array_equal(held[k], after[k]) for k in held)
     # route replay still refuses a ragged batch
     env.load_routes([[[1, 0]] * A] * B)
@@ -436,13 +335,13 @@ def test_flagged_handle_with_a_uniform_batch_equals_an_unflagged_one(gpu_device)
     out = []
     for flag in (False, True):
         env = BatchedTaskEnv(B, A, T, device=gpu_device, renew_sizes=flag)
-        env.generate_instances(_inst_seeds(base, B))
+        env.generate_instances(R.inst_seeds(base, B))
         env.set_instance_renewal(B)
         ring = env.enable_return_log(EPISODES)
         env.reset(seeds, observe=False)
         steps = env.rollout_random(episodes=EPISODES)
         assert env.instances()["n_agents"] is None
-        out.append((ring.clone(), env.summary().clone(), steps.clone(), env.instance_index().clone(), _held(env)))
+        out.append((ring.clone(), env.summary().clone(), steps.clone(), env.instance_index().clone(), R.held(env)))
     (r0, s0, n0, i0, h0), (r1, s1, n1, i1, h1) = out
     assert torch.equal(r0.view(torch.int64), r1.view(torch.int64)) and torch.equal(s0.view(torch.int64), s1.view(torch.int64))
     assert torch.equal(n0, n1) and torch.equal(i0, i1) and (i1 == EPISODES - 1).all()
@@ -462,10 +361,10 @@ def test_lockstep_with_a_route_log_takes_the_general_step(gpu_device, ar, tr, B,
     sz = _size_table(ar, tr, B, base, B, mcs)
     assert (sz[2, :, 0] < sz[1, :, 0]).any()                                    # rows that held a route in episode 1 and are padding now
     seeds = env_seeds(63, 0, B)
-    env, ring = _make(gpu_device, B, ar, tr, base, B, mcs, member_cap, auto_reset=True, auto_reset_episodes=EPISODES)
+    env, ring = R.make(gpu_device, B, ar, tr, base, B, mcs, member_cap, auto_reset=True, auto_reset_episodes=EPISODES)
     env.enable_route_log(64)
-    dcount = _lockstep(env, seeds, 40)
-    _assert_after_three(env, ring, _chains(ar, tr, B, base, B, seeds, mcs), dcount)
+    dcount = R.lockstep_to_end(env, seeds, 40)
+    R.assert_after(env, ring, R.chains(ar, tr, B, base, B, seeds, mcs), dcount)
     length = env.routes()[2].cpu().numpy()
     for b in range(B):
         a = int(sz[2, b, 0])
@@ -489,14 +388,14 @@ def test_overflowed_abandonment_counts_do_not_survive_a_size_change(gpu_device):
     ar, tr, B, base, mwt, mt = (10, 20), (30, 63), 32, 19800, 3.0, 250.0
     sz = _size_table(ar, tr, B, base, B)
     seeds = env_seeds(69, 0, B)
-    env, _ = _make(gpu_device, B, ar, tr, base, B, max_waiting_time=mwt, max_time=mt)
+    env, _ = R.make(gpu_device, B, ar, tr, base, B, max_waiting_time=mwt, max_time=mt)
     env.reset(seeds, observe=False)
     d0, spilled = np.zeros(B, np.int64), np.zeros((EPISODES, B), bool)
     for k in range(EPISODES):
         steps = env.rollout_random(episodes=1).cpu().numpy()
         fin, counts = H.gpu_final(env), env.abandoned_counts().cpu().numpy().astype(np.int64)
         for b in range(B):
-            A, inst = _host_instance(ar, tr, int(renewal_seeds((base + b) % M64, k, B)), 5)
+            A, inst = R.host_instance(ar, tr, int(renewal_seeds((base + b) % M64, k, B)), 5)
             T = inst["req"].shape[0]
             assert (A, T) == tuple(sz[k, b])
             ref = oracle.OracleEnv(A, T, max_waiting_time=mwt, max_time=mt).load(inst["depot"], inst["task_xy"], inst["req"], inst["dur"]) \

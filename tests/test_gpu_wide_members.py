@@ -12,7 +12,7 @@ import numpy as np
 import pytest
 
 import helpers as H
-from test_gpu_api import _anymask_action
+from fixtures_ref import anymask_action
 
 pytestmark = pytest.mark.gpu
 
@@ -53,7 +53,7 @@ def test_mask_ignoring_policy_against_the_oracle(gpu_device, oracle_lib):
     inst = generate_batch(B, A, T, base_seed=400)
     seeds = env_seeds(13, 0, B)
     env = BatchedTaskEnv(B, A, T, device=gpu_device, member_cap=16).load_instances(**inst)
-    got = H.run_lockstep(env, seeds, lambda b, i, m, l: _anymask_action(m, int(seeds[b]), i, T))
+    got = H.run_lockstep(env, seeds, lambda b, i, m, l: anymask_action(m, int(seeds[b]), i, T))
     fin = H.gpu_final(env)
     n_wide = n_exact = 0
     for b in range(B):

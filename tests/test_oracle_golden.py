@@ -12,6 +12,7 @@ import numpy as np
 import pytest
 
 import helpers as H
+from fixtures_ref import extra_instance, random_replay_cases, schedule_cases
 
 POLICY = {"random": 0, "first": 2, "nearest": 3, "anymask": 4}   # anymask: ignores the mask (make_golden_masked.py)
 ALL_KEYS = ("leader", "action", "nfol", "followers", "now", "mask", "agents_obs", "tasks_obs", "finished", "feasible",
@@ -54,23 +55,6 @@ def test_hashed_traces(oracle_lib):
         out = e.rollout(int(meta["seed_e"]), 0, POLICY[meta["policy"]], cap_steps=8192)
         assert out["n_steps"] == meta["n_steps"], name
         assert H.digest(out) == meta["sha256"], name
-
-
-def extra_instance(meta):
-    """Instance of an entry of trace_hashes_extra.json (tests/golden/make_golden_extra.py)."""
-    from dcmrta_amd.instances import generate_instance, generate_instance_ranges
-    if meta["kind"] == "ranges":
-        A, inst = generate_instance_ranges((10, 20), (20, 50), meta["inst_seed"])
-    elif meta["kind"] == "arrays":           # hand-modified instance (coincident locations): arrays stored with the digest
-        A = meta["A"]
-        inst = dict(depot=np.array(meta["depot"]), task_xy=np.array(meta["task_xy"]), req=np.array(meta["req"], np.int32),
-                    dur=np.array(meta["dur"]))
-    else:
-        A = meta["A"]
-        inst = generate_instance(A, meta["T"], meta["inst_seed"], meta.get("max_coalition_size", 5), meta.get("max_duration", 5.0))
-    assert (A, len(inst["req"])) == (meta["A"], meta["T"])
-    assert int(inst["req"].sum()) == meta["req_sum"] and float(inst["dur"][0]) == meta["dur0"]
-    return A, inst
 
 
 def test_extra_hashed_traces(oracle_lib, golden_dir):
@@ -193,22 +177,6 @@ def test_micro_ties_have_several_groups(oracle_lib, golden_dir):
     assert e.get_unique_group(ids) == [[2], [3], [1], [0]]
 
 
-def random_replay_cases(golden_dir):
-    """tests/golden/replay_random.json: (case, instance dict) pairs; instances from the test set or the seeded generator."""
-    from dcmrta_amd.instances import generate_instance, load_instances_npz
-    cases = json.load(open(os.path.join(golden_dir, "replay_random.json")))
-    ts, _ = load_instances_npz(os.path.join(golden_dir, "instances_20A50T.npz"))
-    out = []
-    for c in cases:
-        if c["kind"] == "testset":
-            inst = {k: ts[k][c["index"]] for k in ("depot", "task_xy", "req", "dur")}
-        else:
-            inst = generate_instance(c["A"], c["T"], c["inst_seed"])
-        assert int(inst["req"].sum()) == c["req_sum"]
-        out.append((c, inst))
-    return out
-
-
 def test_random_route_replays(oracle_lib, golden_dir):
     """execute_by_route of the REFERENCE on random routes (surplus visitors that are released before they arrive, too few
     visitors, pre_set_route None, shuffled visiting order; tests/golden/make_golden_extra.py): every terminal array bit
@@ -232,18 +200,6 @@ def test_random_route_replays(oracle_lib, golden_dir):
                 exp = np.asarray(v)
                 assert np.array_equal(np.asarray(ref[k]).astype(exp.dtype), exp, equal_nan=True), (c["A"], c["T"], c["reactive"], k)
     assert seen["ok"] >= 15 and seen["type_error"] >= 10 and seen["no_termination"] >= 4
-
-
-def schedule_cases(golden_dir):
-    """tests/golden/replay_schedule.json (make_golden_schedule.py): replays of the reference with its four dynamic-arrival
-    constants substituted (env/task_env.py:567, :221) -> (case, instance dict) pairs."""
-    from dcmrta_amd.instances import generate_instance
-    out = []
-    for c in json.load(open(os.path.join(golden_dir, "replay_schedule.json"))):
-        inst = generate_instance(c["A"], c["T"], c["inst_seed"])
-        assert int(inst["req"].sum()) == c["req_sum"]
-        out.append((c, inst))
-    return out
 
 
 def test_generalised_visibility_schedule(oracle_lib, golden_dir):

@@ -3,44 +3,15 @@ requirement word, i.e. seeds at which the on-device generator (csrc/instgen.hpp,
 sequential routine.  The GPU tests that run that fall-back (tests/test_gpu_rejecting_seeds.py) rest on the fixture; this test proves
 with numpy alone that every seed rejects where the fixture says, so that a fixture seed that does not reject is a failure here and
 never a GPU case that quietly tests nothing.  Every comparison is exact."""
-import json
-import os
-
 import numpy as np
-import pytest
 
-from test_np_stream_host import _generate, shim  # noqa: F401  (the host-compiled np_stream.hpp)
+from fixtures_ref import load_rejecting_seeds, no_rejection_form, numpy_words, shim, shim_generate  # noqa: F401  (shim: a fixture)
 
 # classes the GPU cases need, with the fewest seeds each; the three 10-minute classes of the search are optional
 NEEDED = {"m13_20A50T": 3, "m13_tasks_ranged_first_block": 2, "m13_tasks_ranged_later_block": 3, "m5_20A50T": 3,
           "m5_50A200T_later_block": 3, "m5_70A130T": 3, "m5_both_ranged": 3, "m5_100A500T_third_block_on": 3}
 WINDOW = {"m13_tasks_ranged_first_block": (1, 127), "m13_tasks_ranged_later_block": (128, 299), "m5_50A200T_later_block": (128, 199),
           "m5_100A500T_third_block_on": (256, 499), "m13_tasks_ranged_buffered_half": (0, 0), "m13_tasks_ranged_word_127": (127, 127)}
-
-
-def load_fixture(golden_dir):
-    """{class: [entry, ...]} with the ranges as generate_instances takes them: an int, or a (lo, hi) tuple."""
-    tup = lambda r: tuple(r) if isinstance(r, list) else r
-    with open(os.path.join(golden_dir, "rejecting_seeds.json")) as f:
-        classes = json.load(f)["classes"]
-    return {name: [dict(e, agents_range=tup(e["agents_range"]), tasks_range=tup(e["tasks_range"])) for e in entries]
-            for name, entries in classes.items()}
-
-
-def numpy_words(seed, agents_range, tasks_range, m):
-    """np.random.default_rng(seed) up to the requirements: the sizes, random(2 + A + 2 T), then has_uint32 / uinteger of the bit
-    generator's state and its raw draws as 32-bit words in stream order, the buffered half first when there is one.
-    Returns A, T, has, words (at least 2 T of them)."""
-    g = np.random.default_rng(int(seed))
-    T = int(g.integers(tasks_range[0], tasks_range[1] + 1)) if isinstance(tasks_range, tuple) else int(tasks_range)
-    A = int(g.integers(agents_range[0], agents_range[1] + 1)) if isinstance(agents_range, tuple) else int(agents_range)
-    g.random(2 + A + 2 * T)
-    st = g.bit_generator.state
-    has = int(st["has_uint32"])
-    words = [int(st["uinteger"])] if has else []
-    for r in g.bit_generator.random_raw(T):
-        words += [int(r) & 0xFFFFFFFF, int(r) >> 32]
-    return A, T, has, words
 
 
 def lemire_rejected(words, n, bound):
@@ -56,13 +27,8 @@ def lemire_rejected(words, n, bound):
     return out
 
 
-def no_rejection_form(words, T, m):
-    """What a generator that never rejects would give: word i makes requirement i."""
-    return np.array([1 + ((w * m) >> 32) for w in words[:T]], np.int32)
-
-
 def test_fixture_has_the_classes(golden_dir):
-    fx = load_fixture(golden_dir)
+    fx = load_rejecting_seeds(golden_dir)
     for name, n in NEEDED.items():
         assert len(fx.get(name, [])) >= n, name
     seeds = [e["seed"] for entries in fx.values() for e in entries]
@@ -81,7 +47,7 @@ def test_fixture_has_the_classes(golden_dir):
 def test_every_fixture_seed_rejects_where_recorded(golden_dir, shim):  # noqa: F811
     from dcmrta_amd.instances import generate_instance, generate_instance_ranges
     n = 0
-    for name, entries in load_fixture(golden_dir).items():
+    for name, entries in load_rejecting_seeds(golden_dir).items():
         for e in entries:
             ar, tr, m, s = e["agents_range"], e["tasks_range"], e["max_coalition_size"], e["seed"]
             A, T, has, words = numpy_words(s, ar, tr, m)
@@ -100,7 +66,7 @@ def test_every_fixture_seed_rejects_where_recorded(golden_dir, shim):  # noqa: F
             assert np.array_equal(req[:w], closed[:w]) and req[w] != closed[w], (name, s)
             # ... and so is the chain of nps::bounded calls, compiled for the host
             a2, t2 = (ar if isinstance(ar, tuple) else (ar, ar)), (tr if isinstance(tr, tuple) else (tr, tr))
-            sA, sT, depot, xy, sreq = _generate(shim, s, a2, t2, m)
+            sA, sT, depot, xy, sreq = shim_generate(shim, s, a2, t2, m)
             assert (sA, sT) == (A, T) and np.array_equal(sreq[:T], req), (name, s)
             assert np.array_equal(depot, inst["depot"]) and np.array_equal(xy[:T], inst["task_xy"]), (name, s)
             n += 1

@@ -11,24 +11,7 @@ import os
 import numpy as np
 import pytest
 
-MODES = [("static", False), ("reactive", True)]
-
-
-def history(golden_dir, mode):
-    """Per fixture instance of the mode: (instance, routes, members, feasible, time_start, time_finish, current_time,
-    traj_len, traj_sha256)."""
-    z = np.load(os.path.join(golden_dir, "replay_history.npz"))
-    out = []
-    for k, i in enumerate(z[f"{mode}_idx"].tolist()):
-        n = z[f"{mode}_route_len"][k]
-        routes = [([int(x) for x in z[f"{mode}_route"][k, a, :n[a]]], [float(x) for x in z[f"{mode}_arrival"][k, a, :n[a]]])
-                  for a in range(len(n))]
-        members = [[int(x) for x in row if x >= 0] for row in z[f"{mode}_members"][k]]
-        out.append(dict(i=i, routes=routes, members=members, feasible=z[f"{mode}_feasible"][k],
-                        time_start=z[f"{mode}_time_start"][k], time_finish=z[f"{mode}_time_finish"][k],
-                        current_time=float(z[f"{mode}_current_time"][k]), traj_len=z[f"{mode}_traj_len"][k],
-                        traj_sha256=z[f"{mode}_traj_sha256"][k]))
-    return out
+from fixtures_ref import MODES, history
 
 
 def test_fixture_covers_the_test_set(golden_dir):
