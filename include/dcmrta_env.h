@@ -331,6 +331,13 @@ int dcm_set_return_log(dcm_env *env, double *returns, int32_t cap);
  * dcm_step / a further dcm_rollout_random carry on from there with identical results), and agents_out / tasks_out /
  * mask_out hold what the kernel stored for the LAST DECISION TAKEN -- which is how the parity tests compare the
  * persistent kernel's own per-decision stores with the oracle at arbitrary decision indices.
+ * Handover: the env's record in HBM is the one place where the entry points meet.  After a budget stop or a dcm_step ANY of them
+ * carries on with identical results -- dcm_step with or without injected choices, dcm_rollout_random / dcm_rollout_policy /
+ * dcm_rollout_explore with all, some or none of the observation buffers, with the rollout log, the best log or a renewal stride set,
+ * cleared or set since the last call -- whichever kernel each of them takes for the handle's shape, and in any order; an env of a
+ * DCM_PARAM_AUTO_RESET handle that a persistent launch left DONE is restarted by the next persistent launch that gives it a budget,
+ * not by dcm_step.  The rollout log is appended by the persistent launches only, each from the lengths the last one stored
+ * (dcm_set_rollout_log).  tests/test_gpu_relay.py hands one episode across every ordered pair of kernel families a shape has.
  * steps_out[B] i64: decisions taken by each env in this call. */
 int dcm_rollout_random(dcm_env *env, int32_t episodes, int64_t max_decisions, const int64_t *max_decisions_in,
                        float *agents_out, float *tasks_out, uint8_t *mask_out, int64_t *steps_out, void *stream);

@@ -1,10 +1,13 @@
 """Member removal against the oracle (test infrastructure): one episode walked through the oracle's step-wise API, which shows the
-member lists in front of and behind every task_update call, and what the removals of a batch cover."""
+member lists in front of and behind every task_update call, what the removals of a batch cover, and a handle against the walk's
+snapshot in front of a decision (assert_state, assert_obs; assert_handover: both, the header fields and the agent side)."""
 import numpy as np
 
 import helpers as H
+import oracle_ref as O
 
 MAX_TIME = 100.0
+TASK_KEYS = ("n_members", "n_abandoned", "feasible", "finished", "time_start", "time_finish")
 
 
 def walk_episode(o, req, seed_e):
@@ -89,3 +92,89 @@ def coverage(rem):
         two_tasks += sum(1 for ts in by_agent.values() if len(ts) >= 2)
     return dict(slots5=slots5, wait_skip=wait_skip, spread_multi=spread_multi, two_tasks=two_tasks,
                 calls=sum(len(r) for r in rem))
+
+
+class Lists:
+    """The member lists of one env's snapshots as a -1 padded table, kept up to date from snapshot to snapshot: walk_episode
+    replaces a list's array when the list changes and never writes to one, so only rows whose array is another one are redone."""
+
+    def __init__(self, T, cap):
+        self.table, self.seen = np.full((T, cap), -1, np.int16), [None] * T
+
+    def at(self, members):
+        for t, m in enumerate(members):
+            if m is not self.seen[t]:
+                self.table[t] = -1
+                self.table[t, :len(m)] = m
+                self.seen[t] = m
+        return self.table
+
+
+def assert_state(tag, s, lists, a, t, mem, abc, ts):
+    """the state of one env (rows of the getters) against the snapshot in front of a decision; rows beyond the env's own sizes are empty"""
+    want = lists.at(s["members"])
+    assert np.array_equal(mem[:t], want), (tag, "members", np.flatnonzero((mem[:t] != want).any(1)))
+    assert np.all(mem[t:] == -1), (tag, "members beyond T_e")
+    ab = np.zeros(abc.shape, np.int16)
+    idx, val = s["abandoned"]
+    ab[idx // t, idx % t] = val
+    assert np.array_equal(abc, ab), (tag, "abandonment counts", np.argwhere(abc != ab)[:8])
+    for k in TASK_KEYS:
+        assert np.array_equal(ts[k][:t].astype(s[k].dtype), s[k]), (tag, k, np.flatnonzero(ts[k][:t].astype(s[k].dtype) != s[k]))
+
+
+def assert_obs(tag, s, a, t, ag, tk, mk):
+    assert np.array_equal(mk[:t + 1].astype(np.uint8), s["mask"]) and np.all(mk[t + 1:] == 1), (tag, "mask")
+    assert np.array_equal(ag[:a], s["agents_obs"]) and np.all(ag[a:] == -1.0), (tag, "agents observation")
+    assert np.array_equal(tk[:t + 1], s["tasks_obs"]) and np.all(tk[t + 1:] == -1.0), (tag, "tasks observation")
+
+
+
+
+def sparse_abandoned(snaps):
+    """Replace every snapshot's dense abandonment table by (flat indices, values) of its non-zero entries: what assert_state takes."""
+    for x in snaps:
+        ab = x.pop("abandoned")
+        idx = np.flatnonzero(ab)
+        x["abandoned"] = (idx, ab.ravel()[idx].astype(np.int16))
+    return snaps
+
+
+def read_batch(env, obs=None):
+    """A batch's getters, read once: task_members, abandoned_counts, tasks_state, agents_state, status and observe() -- or, in place of
+    observe(), the Observation `obs` that the step() call just made returned."""
+    o = env.observe() if obs is None else obs
+    ag = env.agents_state()
+    return dict(mem=env.task_members().cpu().numpy(), abc=env.abandoned_counts().cpu().numpy(),
+                ts={k: v.cpu().numpy() for k, v in env.tasks_state().items()},
+                ag={k: ag[k].cpu().numpy() for k in ("sum_waiting_time", "travel_dist", "returned")},
+                st={k: v.cpu().numpy() for k, v in env.status().items()},
+                obs=tuple(x.cpu().numpy() for x in (o.agents, o.tasks, o.mask, o.leader, o.active)))
+
+
+def assert_handover(tag, got, b, d, snaps, lists, a, t, inst_one, seed, mwt):
+    """Env b of a handle (got: read_batch) against the walk's snapshot in front of decision d (snaps: the env's list; d == len(snaps): the
+    episode is over): leader, now, the decision counter and the active bit; assert_state, with nothing in the rows beyond the env's own
+    sizes; assert_obs; and the agent side against the oracle's own episode stopped in front of that decision."""
+    ag, tk, mk, ld, act = got["obs"]
+    st, abc = got["st"], got["abc"][b]
+    assert st["decisions"][b] == d, (tag, "decision counter", int(st["decisions"][b]), d)
+    if d >= len(snaps):
+        assert not act[b] and (st["flags"][b] & 1), (tag, "the episode must be over")
+    else:
+        s = snaps[d]
+        assert act[b] and not (st["flags"][b] & 1), (tag, "the episode must not be over")
+        assert int(ld[b]) == s["leader"] and st["now"][b] == s["now"], (tag, "leader / now", int(ld[b]), s["leader"], st["now"][b], s["now"])
+        assert_state(tag, s, lists, a, t, got["mem"][b], abc[:a, :t], {k: v[b] for k, v in got["ts"].items()})
+        assert not abc[a:].any() and not abc[:, t:].any(), (tag, "abandonment counts beyond the env's sizes")
+        assert_obs(tag, s, a, t, ag[b], tk[b], mk[b])
+    # dcm_get_agents / dcm_get_tasks compute the waiting sums on read, at the state the env is in; the oracle computes them when an episode
+    # ends (env/task_env.py:344-364, :421), so an episode that the cap stopped is given that one call here -- it changes nothing else
+    o, _, ended = O.play(a, t, inst_one, seed, 0, "random", d, mwt)
+    if not ended:
+        import oracle
+        oracle.lib().orc_finish_episode(o._h)
+    fin = o.final()
+    for k, v in (("agent_wait", got["ag"]["sum_waiting_time"][b, :a]), ("travel_dist", got["ag"]["travel_dist"][b, :a]),
+                 ("returned", got["ag"]["returned"][b, :a]), ("task_wait", got["ts"]["sum_waiting_time"][b, :t])):
+        assert np.array_equal(v.astype(fin[k].dtype), fin[k]), (tag, k, np.flatnonzero(v.astype(fin[k].dtype) != fin[k]))

@@ -16,12 +16,11 @@ import pytest
 
 import helpers as H
 import oracle_ref as O
-from removal_ref import coverage, walk_episode
+from removal_ref import Lists, assert_obs, assert_state, coverage, walk_episode
 
 AB_CAP = 16                 # entries of an agent's abandonment log (csrc/common.hpp); further ones go to the count table
 INST_SEED, CHOICE_SEED = 11, 5
 RAGGED_SIZES = ((70, 130), (64, 64), (65, 128), (64, 129), (70, 65), (1, 130), (20, 66), (66, 127))
-TASK_KEYS = ("n_members", "n_abandoned", "feasible", "finished", "time_start", "time_finish")
 
 # req: None = as generated (1..5), a tuple = drawn from it, an int = drawn from 1..that (wide).  kernel / chunks: what
 # rollout_random launches, <NAC,NTC> of FastG.  sim: the Sim<> instantiation behind k_step (and behind k_rollout_random).
@@ -176,43 +175,8 @@ def _env(gpu_device, name, inst):
         .load_instances(**inst)
 
 
-class _Lists:
-    """The member lists of one env's snapshots as a -1 padded table, kept up to date from snapshot to snapshot: walk_episode
-    replaces a list's array when the list changes and never writes to one, so only rows whose array is another one are redone."""
-
-    def __init__(self, T, cap):
-        self.table, self.seen = np.full((T, cap), -1, np.int16), [None] * T
-
-    def at(self, members):
-        for t, m in enumerate(members):
-            if m is not self.seen[t]:
-                self.table[t] = -1
-                self.table[t, :len(m)] = m
-                self.seen[t] = m
-        return self.table
-
-
 def _state(env):
     return (env.task_members().cpu().numpy(), env.abandoned_counts().cpu().numpy(), {k: v.cpu().numpy() for k, v in env.tasks_state().items()})
-
-
-def _assert_state(tag, s, lists, a, t, mem, abc, ts):
-    """the state of one env (rows of the getters) against the snapshot in front of a decision; rows beyond the env's own sizes are empty"""
-    want = lists.at(s["members"])
-    assert np.array_equal(mem[:t], want), (tag, "members", np.flatnonzero((mem[:t] != want).any(1)))
-    assert np.all(mem[t:] == -1), (tag, "members beyond T_e")
-    ab = np.zeros(abc.shape, np.int16)
-    idx, val = s["abandoned"]
-    ab[idx // t, idx % t] = val
-    assert np.array_equal(abc, ab), (tag, "abandonment counts", np.argwhere(abc != ab)[:8])
-    for k in TASK_KEYS:
-        assert np.array_equal(ts[k][:t].astype(s[k].dtype), s[k]), (tag, k, np.flatnonzero(ts[k][:t].astype(s[k].dtype) != s[k]))
-
-
-def _assert_obs(tag, s, a, t, ag, tk, mk):
-    assert np.array_equal(mk[:t + 1].astype(np.uint8), s["mask"]) and np.all(mk[t + 1:] == 1), (tag, "mask")
-    assert np.array_equal(ag[:a], s["agents_obs"]) and np.all(ag[a:] == -1.0), (tag, "agents observation")
-    assert np.array_equal(tk[:t + 1], s["tasks_obs"]) and np.all(tk[t + 1:] == -1.0), (tag, "tasks observation")
 
 
 def _assert_final(env, name, eps):
@@ -235,7 +199,7 @@ def test_lockstep_after_every_decision(gpu_device, oracle_lib, name):
     B, T, limit = c["B"], c["T"], c["lockstep"] or 1 << 30
     inst, seeds, snaps, _, eps = walks(oracle_lib, name)
     n = np.array([len(s) for s in snaps])
-    lists = [_Lists(sizes(name, b)[1], c.get("member_cap", 5)) for b in range(B)]
+    lists = [Lists(sizes(name, b)[1], c.get("member_cap", 5)) for b in range(B)]
     env = _env(gpu_device, name, inst)
     obs = env.reset(seeds)
     count = np.zeros(B, np.int64)
@@ -257,9 +221,9 @@ def test_lockstep_after_every_decision(gpu_device, oracle_lib, name):
             tag = f"{name} env {b} decision {count[b]}"
             a, t = sizes(name, b)
             assert int(ld[b]) == s["leader"] and now[b] == s["now"], (tag, "leader / now")
-            _assert_state(tag, s, lists[b], a, t, mem[b], abc[b, :a, :t], {k: v[b] for k, v in ts.items()})
+            assert_state(tag, s, lists[b], a, t, mem[b], abc[b, :a, :t], {k: v[b] for k, v in ts.items()})
             assert not abc[b, a:].any() and not abc[b, :, t:].any(), (tag, "abandonment counts beyond the env's sizes")
-            _assert_obs(tag, s, a, t, ag[b], tk[b], mk[b])
+            assert_obs(tag, s, a, t, ag[b], tk[b], mk[b])
         count += active
         obs = env.step(torch.from_numpy(actions).to(gpu_device))
     else:
@@ -281,7 +245,7 @@ def test_persistent_kernel_under_decision_budgets(gpu_device, oracle_lib, name):
     B, top = c["B"], c["budget"]
     inst, seeds, snaps, _, eps = walks(oracle_lib, name)
     n = np.array([len(s) for s in snaps], np.int64)
-    lists = [_Lists(sizes(name, b)[1], c.get("member_cap", 5)) for b in range(B)]
+    lists = [Lists(sizes(name, b)[1], c.get("member_cap", 5)) for b in range(B)]
     rng = np.random.default_rng(c["A"] * 1000 + c["T"])
     env = _env(gpu_device, name, inst)
     env.reset(seeds, observe=False)
@@ -297,7 +261,7 @@ def test_persistent_kernel_under_decision_budgets(gpu_device, oracle_lib, name):
         stored = env.obs()
         ag, tk, mk = (x.cpu().numpy() for x in (stored.agents, stored.tasks, stored.mask))   # the kernel's own stores: read before observe()
         for b in np.flatnonzero(ran):
-            _assert_obs(f"{name} env {b}: stored observation of decision {taken[b] - 1}", snaps[b][taken[b] - 1], *sizes(name, b), ag[b], tk[b], mk[b])
+            assert_obs(f"{name} env {b}: stored observation of decision {taken[b] - 1}", snaps[b][taken[b] - 1], *sizes(name, b), ag[b], tk[b], mk[b])
         mem, abc, ts = _state(env)
         st = {k: v.cpu().numpy() for k, v in env.status().items()}
         o2 = env.observe()
@@ -311,9 +275,9 @@ def test_persistent_kernel_under_decision_budgets(gpu_device, oracle_lib, name):
             s = snaps[b][taken[b]]
             a, t = sizes(name, b)
             assert act[b] and int(ld[b]) == s["leader"] and st["now"][b] == s["now"], (tag, "leader / now")
-            _assert_state(tag, s, lists[b], a, t, mem[b], abc[b, :a, :t], {k: v[b] for k, v in ts.items()})
+            assert_state(tag, s, lists[b], a, t, mem[b], abc[b, :a, :t], {k: v[b] for k, v in ts.items()})
             assert not abc[b, a:].any() and not abc[b, :, t:].any(), (tag, "abandonment counts beyond the env's sizes")
-            _assert_obs(tag, s, a, t, ag[b], tk[b], mk[b])
+            assert_obs(tag, s, a, t, ag[b], tk[b], mk[b])
     else:
         raise AssertionError("the episodes did not end")
     _assert_final(env, name, eps)
