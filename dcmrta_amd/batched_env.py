@@ -525,6 +525,40 @@ class BatchedTaskEnv:
         one = lambda e: [[t + 1 for t in r] for r, _ in route_lists(task[e], arrival[e], length[e], "enable_rollout_log(cap)")]
         return one(b) if b is not None else [one(e) for e in range(self.B)]
 
+    def reduce_best(self, group=None, routes=True):
+        """The best log reduced over groups of envs on the device (dcm_reduce_best): envs [g * group, (g + 1) * group) are group g
+        (group=None: all B envs, one group; the last group may be short), and each group's winner is the env with the most finished
+        tasks, then the largest reward, then the lowest index.  Returns a dict of device tensors allocated by this call -- env[G]
+        (int32, -1 = no env of the group keeps an episode), summary[G,8], episode[G] and, with routes, len[G,A], task[G,A,cap],
+        arrival[G,A,cap]: the winner's rows of best_summary / best_episode / best_routes, the route rows filled with -2 / 0.0 behind
+        [0, min(len, cap)).  N instances x K envs each in one handle: reduce_best(group=K) gives the N plans (group_plan) and only
+        those leave the device.  Stream-ordered, no synchronisation; changes nothing in the handle."""
+        if group is not None and int(group) < 1:
+            raise ValueError("reduce_best: group must be >= 1")
+        best = self._best_log()
+        group = self.B if group is None else int(group)
+        G, A, dev, cap = -(-self.B // group), self.A, self.device, best[0].shape[2]
+        red = dict(env=torch.full((G,), -1, dtype=torch.int32, device=dev),
+                   summary=torch.full((G, 8), float("nan"), dtype=torch.float64, device=dev),
+                   episode=torch.full((G,), -1, dtype=torch.int32, device=dev))
+        if routes:
+            red.update(len=torch.zeros((G, A), dtype=torch.int32, device=dev),
+                       task=torch.full((G, A, cap), -2, dtype=torch.int16, device=dev),
+                       arrival=torch.zeros((G, A, cap), dtype=torch.float64, device=dev))
+        with torch.cuda.device(self.device):
+            check(self._lib.dcm_reduce_best(self._h, group, _ptr(red["env"]), _ptr(red["summary"]), _ptr(red["episode"]),
+                                            _ptr(red.get("len")), _ptr(red.get("task")), _ptr(red.get("arrival")), self._stream()))
+        return red
+
+    @staticmethod
+    def group_plan(red, g):
+        """best_plan's nested lists for the winner of group g of a reduce_best() result (with routes): plan[a] = [action, ...] with
+        0 = depot, k = task k-1; empty lists for a group without a winner.  ValueError, like route_lists, when a kept route is longer
+        than the log's cap."""
+        from .trajectory import route_lists
+        task, arrival, length = (red[k][g].cpu().numpy() for k in ("task", "arrival", "len"))
+        return [[t + 1 for t in r] for r, _ in route_lists(task, arrival, length, "enable_rollout_log(cap)")]
+
     # ------------------------------------------------------------------ route replay (env/task_env.py:562-599)
     def load_routes(self, routes, member_cap=8):
         """routes[b][a] = list of actions (0 = depot, k = task k-1) or None (pre_set_route stays None)."""
@@ -634,6 +668,9 @@ class BatchedTaskEnv:
         n = C.c_size_t()
         check(self._lib.dcm_record_bytes(self._h, C.byref(n)))
         return n.value
+
+
+group_plan = BatchedTaskEnv.group_plan    # needs the reduced buffers only, no handle
 
 
 def device_distance(a_xy, b_xy, device="cuda:0"):

@@ -1446,6 +1446,9 @@ __device__ __forceinline__ int env_of_workgroup() {
 }
 
 #include "instgen.hpp"
+#ifndef DCM_DEVICE_ONLY_TU   // k_reduce_best: the host API's unit only (the form units hold their forms and nothing else)
+#include "best_reduce.hpp"
+#endif
 
 __global__ __launch_bounds__(WAVE) void k_load_instances(int A, int T, int PA, int PT, int PC, unsigned char* state, const double* depot,
                                                         const double* task_xy, const int32_t* req, const double* dur,
@@ -2475,6 +2478,31 @@ int dcm_set_best_log(dcm_env* env, int16_t* best_task, double* best_arrival, int
     if (!off && (!best_task || !best_arrival || !best_len || !best_summary || !best_episode))
         return fail(DCM_ERR_INVALID, "dcm_set_best_log: give all five arrays, or all NULL");
     env->best_log = dcm::BestLog{best_task, best_arrival, best_len, best_summary, best_episode};
+    return DCM_OK;
+}
+
+int dcm_reduce_best(dcm_env* env, int32_t group, int32_t* win_env, double* win_summary, int32_t* win_episode, int32_t* win_len,
+                    int16_t* win_task, double* win_arrival, void* stream) {
+    CHECK_ENV(env);
+    if (!env->best_log.episode)
+        return fail(DCM_ERR_STATE, "dcm_reduce_best: the best log is not set: call dcm_set_best_log (and play some episodes) first");
+    if (group < 1) return fail(DCM_ERR_INVALID, "dcm_reduce_best: group must be >= 1");
+    if (!win_env) return fail(DCM_ERR_INVALID, "dcm_reduce_best: null win_env");
+    const bool routes = win_len && win_task && win_arrival;
+    if (!routes && (win_len || win_task || win_arrival))
+        return fail(DCM_ERR_INVALID, "dcm_reduce_best: give win_len, win_task and win_arrival together, or all three NULL");
+    // the best log's rows have the cap of the rollout log they are copied from
+    if (routes && !env->rollout_log.len)
+        return fail(DCM_ERR_STATE, "dcm_reduce_best: the rollout log is not set, so the best log's rows have no cap: call dcm_set_rollout_log "
+                                   "first, or pass win_len, win_task and win_arrival as NULL");
+    const int B = env->p.n_envs;
+    const unsigned G = (unsigned)(((int64_t)B + group - 1) / group);
+    const int64_t threads = ((int64_t)group + WAVE - 1) / WAVE * WAVE;
+    const dcm::BestLog& bl = env->best_log;
+    hipLaunchKernelGGL(k_reduce_best, dim3(G), dim3((unsigned)(threads < 1024 ? threads : 1024)), 0, (hipStream_t)stream, B, (int)group, env->A,
+                       (int)env->rollout_log.cap, (const int16_t*)bl.task, (const double*)bl.arrival, (const int32_t*)bl.len,
+                       (const double*)bl.summary, (const int32_t*)bl.episode, win_env, win_summary, win_episode, win_len, win_task, win_arrival);
+    LAUNCH_OK();
     return DCM_OK;
 }
 

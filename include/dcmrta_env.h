@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define DCM_ABI_VERSION 5 /* v3: dcm_build_id, dcm_set_visibility, dcm_load_instances validates req on the device; v4: dcm_set_replay_placement; v5: DCM_PARAM_WIDE_MEMBERS; still v5, additions only: dcm_generate_instances, dcm_get_instances, dcm_generator_draws, dcm_set_instance_renewal, dcm_instance_index, DCM_PARAM_RENEW_SIZES, dcm_set_rollout_log, dcm_set_best_log */
+#define DCM_ABI_VERSION 5 /* v3: dcm_build_id, dcm_set_visibility, dcm_load_instances validates req on the device; v4: dcm_set_replay_placement; v5: DCM_PARAM_WIDE_MEMBERS; still v5, additions only: dcm_generate_instances, dcm_get_instances, dcm_generator_draws, dcm_set_instance_renewal, dcm_instance_index, DCM_PARAM_RENEW_SIZES, dcm_set_rollout_log, dcm_set_best_log, dcm_reduce_best */
 
 typedef struct dcm_env dcm_env; /* opaque */
 
@@ -297,6 +297,29 @@ int dcm_set_rollout_log(dcm_env *env, int16_t *route_task, double *route_arrival
  * Host-side setter; not part of dcm_clone_state / dcm_restore_state. */
 int dcm_set_best_log(dcm_env *env, int16_t *best_task, double *best_arrival, int32_t *best_len, double *best_summary,
                      int32_t *best_episode);
+
+/* The best log reduced over groups of envs, on the device: envs [g * group, (g + 1) * group) are one group (K samples of one
+ * instance, say), G = ceil(B / group) groups, the last one possibly short.  One kernel launch finds every group's winner and gathers
+ * the winner's rows of the best log into compact caller-owned device buffers, so that N instances x K samples in ONE handle give N
+ * plans and only those have to leave the device:
+ *   win_env[G] i32          the winner's env index, -1 for a group in which no env keeps an episode
+ *   win_summary[G,8] f64    its best_summary row (NaN for such a group); may be NULL
+ *   win_episode[G] i32      its best_episode (-1); may be NULL
+ *   win_len[G,A] i32        its best_len row (0)
+ *   win_task[G,A,cap] i16, win_arrival[G,A,cap] f64   entries [0, min(len, cap)) of each of its agent rows, and behind them the fill
+ *                           the logs start from, -2 / 0.0 (all fill): every element is written
+ * A and cap are those of the logs that are set.  win_len, win_task and win_arrival may be NULL together (summaries only).
+ *   Order: an env is a candidate iff best_episode != -1.  The winner has the most finished tasks (best_summary column 1), among those
+ *     the largest reward (column 0), among those the LOWEST env index -- exact in fp64, 0.0 and -0.0 tie: it is the env a sequential
+ *     scan of the group in env order would keep under dcm_set_best_log's strict replace rule.  Kept rows hold no NaN by that log's
+ *     contract; no order is defined for one.
+ *   Refusals, nothing launched: the best log not set, DCM_ERR_STATE (call dcm_set_best_log first); the three route arrays given while
+ *     the rollout log, whose cap the rows have, is not set, DCM_ERR_STATE; group < 1, win_env NULL, or some but not all of win_len /
+ *     win_task / win_arrival, DCM_ERR_INVALID.
+ * Stream-ordered behind the launches that wrote the best log; no host synchronisation, legal under stream capture.  It reads the
+ * best log and writes the win_* buffers, nothing else: no handle state changes, and a launch after it returns what it would have. */
+int dcm_reduce_best(dcm_env *env, int32_t group, int32_t *win_env, double *win_summary, int32_t *win_episode,
+                    int32_t *win_len, int16_t *win_task, double *win_arrival, void *stream);
 
 /* Optional history of route replay: what execute_by_route leaves for generate_traj / plot_animation (env/task_env.py:375-418,
  * 589-590) -- agent['route'] / ['arrival_time'], task['members'] and task['feasible_assignment'].  When set, dcm_execute_routes

@@ -1,17 +1,21 @@
 #!/usr/bin/env python3
-"""A plan by sampling: play one instance many times under the epsilon-greedy `nearest` policy and keep the best episode.
+"""Plans by sampling: play an instance many times under the epsilon-greedy `nearest` policy and keep the best episode -- for N instances
+in ONE handle and one launch.
 
-    python tools/sample_plan.py [--agents 20 --tasks 50 --instance-seed 7000 | --golden I] [--envs 4096] [--eps 0.05] [--seed 11]
-                                [--episodes 1] [--cap 64] [--out plan.yaml]
+    python tools/sample_plan.py [--agents 20 --tasks 50 --instance-seed 7000 | --golden I] [--instances 1] [--envs 4096] [--eps 0.05]
+                                [--seed 11] [--episodes 1] [--cap 64] [--out plan.yaml]
 
-The instance -- generate_instance(agents, tasks, instance_seed), or the I-th of tests/golden/instances_20A50T.npz -- is replicated over
-`envs` envs with seeds env_seed(seed, b).  Every env plays ONE episode of rollout("nearest", explore=eps) with the rollout log set; the
-best env is the one with the largest pair (number of finished tasks, reward = -makespan).  Prints that pair next to the pair of the
-pure `nearest` policy (one env: every episode of it on an instance ends alike) as one JSON line, and writes the best env's routes with
-routes_to_yaml (the file Worker.generate_route writes, which load_routes / execute_routes replay).
-With --episodes E > 1 every env plays E episodes in the ONE launch -- the decision counter keeps running across restarts, so they
-differ -- with the best log set (enable_best_log): each env keeps its best episode on the device, the best env is picked from
-best_summary, its best_plan is written, and the JSON line also carries `episodes` and the kept episode's ordinal `best_episode`.
+Instance n -- generate_instance(agents, tasks, instance_seed + n), or the (I + n)-th of tests/golden/instances_20A50T.npz -- is
+replicated over `envs` envs with seeds env_seed(seed, b), b < envs: envs [n * envs, (n + 1) * envs) of one handle of N * envs envs.
+Every env plays `episodes` episodes of rollout("nearest", explore=eps) in the one launch (the decision counter keeps running across
+restarts, so they differ) with the rollout log and the best log set: each env keeps its best episode on the device -- the largest pair
+(number of finished tasks, reward = -makespan) -- and reduce_best(group=envs) picks each instance's best env and gathers its routes
+there too.  Only the reduced buffers are read back: N summary rows and N plans, not the best log of N * envs envs.
+Prints one JSON line: each instance's pair next to the pair of the pure `nearest` policy (one env: every episode of it on an instance
+ends alike), and writes each winner's routes as the file Worker.generate_route writes, which load_routes / execute_routes replay.
+With one instance the line has the scalar entries it always had and the file is --out; with N > 1 `instance`, `nearest`, `sampled`,
+`distinct_returns`, `out` (and `best_episode`) are lists of N and the files are plan_<n>.yaml next to --out.  With --episodes E > 1 the
+line also carries `episodes` and the kept episode's ordinal `best_episode`.
 Needs a HIP device."""
 import argparse
 import json
@@ -19,13 +23,14 @@ import os
 import sys
 
 import numpy as np
+import torch
+import yaml
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
-from dcmrta_amd.batched_env import BatchedTaskEnv  # noqa: E402
+from dcmrta_amd.batched_env import BatchedTaskEnv, group_plan  # noqa: E402
 from dcmrta_amd.choice import env_seeds, explore_q32  # noqa: E402
 from dcmrta_amd.instances import generate_instance  # noqa: E402
-from dcmrta_amd.trajectory import routes_to_yaml  # noqa: E402
 
 
 def main():
@@ -34,51 +39,65 @@ def main():
     ap.add_argument("--tasks", type=int, default=50)
     ap.add_argument("--instance-seed", type=int, default=7000)
     ap.add_argument("--golden", type=int, default=None, help="take the I-th instance of tests/golden/instances_20A50T.npz instead")
-    ap.add_argument("--envs", type=int, default=4096)
+    ap.add_argument("--instances", type=int, default=1, help="N instances (instance seed / golden index + n), each on its own --envs envs of the one handle")
+    ap.add_argument("--envs", type=int, default=4096, help="envs per instance")
     ap.add_argument("--eps", type=float, default=0.05)
     ap.add_argument("--seed", type=int, default=11, help="base of the env seeds env_seed(seed, b)")
-    ap.add_argument("--episodes", type=int, default=1, help="episodes per env in the one launch; > 1 keeps each env's best on the device")
+    ap.add_argument("--episodes", type=int, default=1, help="episodes per env in the one launch; every env keeps its best on the device")
     ap.add_argument("--cap", type=int, default=64, help="entries per agent of the rollout log")
-    ap.add_argument("--out", default="plan.yaml")
+    ap.add_argument("--out", default="plan.yaml", help="the plan file; with --instances N > 1, plan_<n>.yaml in its directory")
     ap.add_argument("--device", default="cuda:0")
     args = ap.parse_args()
     if args.envs < 1:
         ap.error("--envs must be >= 1")
     if args.episodes < 1:
         ap.error("--episodes must be >= 1")
+    if args.instances < 1:
+        ap.error("--instances must be >= 1")
+    N, K = args.instances, args.envs
     if args.golden is not None:
         z = np.load(os.path.join(ROOT, "tests", "golden", "instances_20A50T.npz"))
-        if not 0 <= args.golden < len(z["depot"]):
-            ap.error("--golden must be in 0..%d" % (len(z["depot"]) - 1))
-        inst = {k: z[k][args.golden] for k in ("depot", "task_xy", "req", "dur")}
-        A, T, source = int(z["A"]), inst["task_xy"].shape[0], "golden %d" % args.golden
+        if not 0 <= args.golden <= len(z["depot"]) - N:
+            ap.error("--golden must be in 0..%d" % (len(z["depot"]) - N))
+        insts = [{k: z[k][args.golden + n] for k in ("depot", "task_xy", "req", "dur")} for n in range(N)]
+        A, T, sources = int(z["A"]), insts[0]["task_xy"].shape[0], ["golden %d" % (args.golden + n) for n in range(N)]
     else:
-        inst = generate_instance(args.agents, args.tasks, args.instance_seed)
-        A, T, source = args.agents, args.tasks, "generate_instance(%d, %d, %d)" % (args.agents, args.tasks, args.instance_seed)
-    rep = lambda n: [np.stack([np.asarray(inst[k])] * n) for k in ("depot", "task_xy", "req", "dur")]
+        insts = [generate_instance(args.agents, args.tasks, args.instance_seed + n) for n in range(N)]
+        A, T = args.agents, args.tasks
+        sources = ["generate_instance(%d, %d, %d)" % (A, T, args.instance_seed + n) for n in range(N)]
+    # every instance `times` times, instance by instance
+    rep = lambda times: [np.stack([np.asarray(inst[k]) for inst in insts for _ in range(times)]) for k in ("depot", "task_xy", "req", "dur")]
     pair = lambda row: (int(row[1]), float(row[0]))                             # (finished tasks, reward) of a summary row
 
-    greedy = BatchedTaskEnv(1, A, T, device=args.device).load_instances(*rep(1))
-    greedy.reset(env_seeds(args.seed, 0, 1), observe=False)
+    greedy = BatchedTaskEnv(N, A, T, device=args.device).load_instances(*rep(1))
+    greedy.reset(np.tile(env_seeds(args.seed, 0, 1), N), observe=False)
     greedy.rollout("nearest", episodes=1, write_obs=False)
-    g = pair(greedy.summary().cpu().numpy()[0])
+    g = [pair(row) for row in greedy.summary().cpu().numpy()]
 
-    env = BatchedTaskEnv(args.envs, A, T, device=args.device).load_instances(*rep(args.envs))
+    env = BatchedTaskEnv(N * K, A, T, device=args.device).load_instances(*rep(K))
     env.enable_rollout_log(args.cap)
-    many = args.episodes > 1
-    if many:
-        env.enable_best_log()
-    env.reset(env_seeds(args.seed, 0, args.envs), observe=False)
+    env.enable_best_log()
+    env.reset(np.tile(env_seeds(args.seed, 0, K), N), observe=False)
     steps = env.rollout("nearest", episodes=args.episodes, write_obs=False, explore=args.eps)
-    sm = (env.best_summary() if many else env.summary()).cpu().numpy()
-    best = max(range(args.envs), key=lambda b: pair(sm[b]))
-    routes_to_yaml(env, args.out, best, log="best" if many else "rollout")      # ValueError if a route is longer than --cap
-    s = pair(sm[best])
-    line = dict(instance=source, envs=args.envs, eps=args.eps, explore_q32=explore_q32(args.eps), decisions=int(steps.sum()),
-                nearest=dict(finished=g[0], reward=g[1]), sampled=dict(finished=s[0], reward=s[1], env=int(best)),
-                distinct_returns=int(len(set(sm[:, 0].tolist()))), out=args.out)
-    if many:
-        line.update(episodes=args.episodes, best_episode=int(env.best_episode()[best]))
+    red = env.reduce_best(group=K)                                              # [N, ...]: all that leaves the device
+    distinct = [int(torch.unique(env.best_summary()[n * K:(n + 1) * K, 0]).numel()) for n in range(N)]
+    red = {k: v.cpu() for k, v in red.items()}
+    winners, kept, sm = red["env"].tolist(), red["episode"].tolist(), red["summary"].numpy()
+    if min(winners) < 0:
+        sys.exit("no env of instance %d finished an episode without an error flag" % winners.index(min(winners)))
+    outs = [args.out] if N == 1 else [os.path.join(os.path.dirname(args.out), "plan_%d.yaml" % n) for n in range(N)]
+    for n, path in enumerate(outs):
+        with open(path, "w") as f:                                              # group_plan: ValueError if a route is longer than --cap
+            yaml.dump({a: r for a, r in enumerate(group_plan(red, n))}, f, sort_keys=False)   # worker.py:246-248
+    sampled = [dict(finished=pair(sm[n])[0], reward=pair(sm[n])[1], env=int(winners[n]) - n * K) for n in range(N)]
+    nearest = [dict(finished=f, reward=r) for f, r in g]
+    one = lambda xs: xs[0] if N == 1 else xs
+    line = dict(instance=one(sources), envs=K, eps=args.eps, explore_q32=explore_q32(args.eps), decisions=int(steps.sum()),
+                nearest=one(nearest), sampled=one(sampled), distinct_returns=one(distinct), out=one(outs))
+    if N > 1:
+        line.update(instances=N)
+    if args.episodes > 1:
+        line.update(episodes=args.episodes, best_episode=one([int(k) for k in kept]))
     print(json.dumps(line))
 
 
