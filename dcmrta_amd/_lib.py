@@ -73,6 +73,7 @@ SIGNATURES = {
     "dcm_set_rollout_log": (C.c_int, [_vp, _vp, _vp, _vp, _i32]),   # as dcm_set_route_log, for the persistent launches
     "dcm_set_best_log": (C.c_int, [_vp] * 6),   # env, best_task, best_arrival, best_len, best_summary, best_episode
     "dcm_reduce_best": (C.c_int, [_vp, _i32] + [_vp] * 7),   # env, group, win_env, win_summary, win_episode, win_len, win_task, win_arrival, stream
+    "dcm_fork_envs": (C.c_int, [_vp] * 6),   # dst, src, src_index, seeds_in, ok_out, stream
     "dcm_set_replay_log": (C.c_int, [_vp, _vp, _vp, _vp, _i32, _vp, _i32, _vp]),
     "dcm_load_routes": (C.c_int, [_vp, _vp, _vp, _i32, _i32, _vp]),
     "dcm_execute_routes": (C.c_int, [_vp, _i32] + [_vp] * 11),

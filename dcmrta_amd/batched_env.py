@@ -76,6 +76,7 @@ class BatchedTaskEnv:
         flags = (1 if individual_selection else 0) | (2 if auto_reset else 0) | (4 if strict_mask else 0) | \
                 (_lib.PARAM_WIDE_MEMBERS if self.member_cap > _lib.MAX_MEMBERS else 0) | (_lib.PARAM_RENEW_SIZES if renew_sizes else 0)
         self.renew_sizes = bool(renew_sizes)
+        self.individual_selection, self.auto_reset, self.strict_mask = bool(individual_selection), bool(auto_reset), bool(strict_mask)
         # auto_reset_episodes: an env stops restarting after that many finished episodes (0 = never)
         p = DcmParams(self.B, self.A, self.T, idx, self.max_waiting_time, self.max_time, flags, int(auto_reset_episodes))
         h = C.c_void_p()
@@ -663,6 +664,53 @@ class BatchedTaskEnv:
                            "(taken from another env, or before the batch changed between uniform and ragged)")
         with torch.cuda.device(self.device):
             check(self._lib.dcm_restore_state(self._h, _ptr(buf), self._stream()))
+
+    # ------------------------------------------------------------------ per-env copy (dcm_fork_envs)
+    def fork_from(self, src, index, seeds=None, check=False):
+        """Env b of this handle becomes env index[b] of `src` (dcm_fork_envs): the record with its instance, clock, decision counter
+        and episode count, the summary row and the abandonment tables.  index: int32[B] (numpy/torch), -1 = leave env b alone.
+        seeds: uint64[B] -- the copied envs draw from seeds[b] from here on; None -- a copy keeps its source's seed and plays exactly what
+        the source would.  src may be this handle: a source must then be its own source (index[index[b]] == index[b]).  Envs whose index
+        breaks that rule or lies outside [-1, src.B) are left untouched; check=True reads the device's verdict back and raises
+        DcmError for them (otherwise the call does not synchronise).  Both handles need the same n_agents, n_tasks and member_cap, a
+        uniform batch that has been loaded and reset, and no renewal stride.  The logs (enable_route_log / enable_rollout_log /
+        enable_best_log / enable_return_log) are not copied: they stay this handle's.  Returns self."""
+        if not isinstance(src, BatchedTaskEnv):
+            raise DcmError("fork_from: src must be a BatchedTaskEnv")
+        if (src.A, src.T, src.member_cap) != (self.A, self.T, self.member_cap):
+            raise DcmError(f"fork_from: src is a {src.A}A/{src.T}T env with member_cap {src.member_cap}, this one {self.A}A/{self.T}T "
+                           f"with {self.member_cap}: the record layouts must be identical")
+        n = index.numel() if isinstance(index, torch.Tensor) else np.asarray(index).size
+        if n != self.B:
+            raise DcmError(f"fork_from: index must be int32[{self.B}], one entry per env of this handle")
+        if seeds is not None:
+            if isinstance(seeds, torch.Tensor):
+                if seeds.dtype not in (torch.int64, torch.uint64):
+                    raise DcmError("fork_from: seeds must be a uint64 / int64 tensor")
+                ns = seeds.numel()
+            else:
+                seeds = np.ascontiguousarray(seeds, dtype=np.uint64)
+                ns = seeds.size
+            if ns != self.B:
+                raise DcmError(f"fork_from: seeds must be uint64[{self.B}], one entry per env of this handle")
+        if src.device != self.device:
+            raise DcmError("fork_from: the two handles are on different devices")
+        if src._h is None or self._h is None:
+            raise DcmError("fork_from: a handle is closed")
+        idx = self._dev(index, torch.int32).reshape(-1)
+        s = None
+        if seeds is not None:
+            s = seeds.to(self.device).contiguous() if isinstance(seeds, torch.Tensor) else torch.from_numpy(seeds.view(np.int64)).to(self.device)
+        ok = torch.empty((self.B,), dtype=torch.uint8, device=self.device) if check else None
+        with torch.cuda.device(self.device):
+            _lib.check(self._lib.dcm_fork_envs(self._h, src._h, _ptr(idx), _ptr(s), _ptr(ok), self._stream()))
+        self._fork_args = (idx, s)      # keep alive until the kernel ran
+        if check:
+            bad = torch.nonzero(ok == 0).flatten().cpu().numpy()
+            if len(bad):
+                raise DcmError(f"fork_from: {len(bad)} env(s) were refused and left untouched (first: env {int(bad[0])}, index "
+                               f"{int(idx[int(bad[0])])}): the index is outside [-1, {src.B}) or, in place, its source is not its own source")
+        return self
 
     def record_bytes(self):
         n = C.c_size_t()

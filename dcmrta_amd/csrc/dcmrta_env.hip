@@ -1449,6 +1449,9 @@ __device__ __forceinline__ int env_of_workgroup() {
 #ifndef DCM_DEVICE_ONLY_TU   // k_reduce_best: the host API's unit only (the form units hold their forms and nothing else)
 #include "best_reduce.hpp"
 #endif
+#ifndef DCM_DEVICE_ONLY_TU   // k_fork_envs: likewise
+#include "fork_envs.hpp"
+#endif
 
 __global__ __launch_bounds__(WAVE) void k_load_instances(int A, int T, int PA, int PT, int PC, unsigned char* state, const double* depot,
                                                         const double* task_xy, const int32_t* req, const double* dur,
@@ -2503,6 +2506,43 @@ int dcm_reduce_best(dcm_env* env, int32_t group, int32_t* win_env, double* win_s
                        (int)env->rollout_log.cap, (const int16_t*)bl.task, (const double*)bl.arrival, (const int32_t*)bl.len,
                        (const double*)bl.summary, (const int32_t*)bl.episode, win_env, win_summary, win_episode, win_len, win_task, win_arrival);
     LAUNCH_OK();
+    return DCM_OK;
+}
+
+int dcm_fork_envs(dcm_env* dst, dcm_env* src, const int32_t* src_index, const uint64_t* seeds_in, uint8_t* ok_out, void* stream) {
+    if (!dst || !src) return fail(DCM_ERR_INVALID, "dcm_fork_envs: null env handle");
+    if (dst->p.device != src->p.device) return fail(DCM_ERR_INVALID, "dcm_fork_envs: the two handles are on different devices");
+    int cur = -1;
+    if (hipGetDevice(&cur) != hipSuccess || cur != dst->p.device)
+        return fail(DCM_ERR_STATE, "dcm_fork_envs: the current HIP device is not the device the handles were created on");
+    // one record layout: the dims and the member slots decide every offset in a record and the pitch of the side rows
+    if (dst->A != src->A || dst->T != src->T || (dst->p.flags & DCM_PARAM_WIDE_MEMBERS) != (src->p.flags & DCM_PARAM_WIDE_MEMBERS))
+        return fail(DCM_ERR_INVALID, "dcm_fork_envs: n_agents, n_tasks and DCM_PARAM_WIDE_MEMBERS must be the same on both handles (one record layout)");
+    if (!src_index) return fail(DCM_ERR_INVALID, "dcm_fork_envs: null src_index");
+    for (const dcm_env* e : {dst, src}) {
+        const char* which = e == dst ? "dst" : "src";
+        // (dst too, although the call would fill it: no kernel is ever pointed at a record nobody wrote, and src_index may hold -1)
+        if (!e->loaded || !e->reset_done)
+            return fail(DCM_ERR_STATE, "dcm_fork_envs: %s has not been loaded and reset: call dcm_load_instances / dcm_generate_instances and dcm_reset first", which);
+        if (e->sizes)
+            return fail(DCM_ERR_STATE, "dcm_fork_envs: %s holds a ragged batch: the per-env sizes have a host copy that a device-side map cannot keep in step", which);
+        if (e->renew_stride != 0)
+            return fail(DCM_ERR_STATE, "dcm_fork_envs: %s has a renewal stride set: clear it with dcm_set_instance_renewal(env, 0) first", which);
+    }
+    // a deferred terminal snapshot must not land on a copied summary row later (nor a source row be read before it is computed)
+    DCM_TRY(dcm::flush_pending(src, stream));
+    if (dst != src) DCM_TRY(dcm::flush_pending(dst, stream));
+    const Lay& L = dst->L;
+    const uint32_t log_bytes = (uint32_t)dst->A * AB_CAP * sizeof(uint16_t), cnt_bytes = (uint32_t)abcnt_pitch(dst->A, dst->T);
+    // (the count tables follow the logs of ALL of a handle's envs: the two handles' tables start at different offsets)
+    unsigned char* const cnt_dst = (unsigned char*)dst->ablog + (size_t)dst->p.n_envs * log_bytes;
+    const unsigned char* const cnt_src = (const unsigned char*)src->ablog + (size_t)src->p.n_envs * log_bytes;
+    hipLaunchKernelGGL(k_fork_envs, GRID(dst), 0, (hipStream_t)stream, src->p.n_envs, dst == src, L.rec_bytes() / 16, log_bytes / 16, cnt_bytes / 16,
+                       dst->state, (const unsigned char*)src->state, dst->summary, (const double*)src->summary, (unsigned char*)dst->ablog,
+                       (const unsigned char*)src->ablog, cnt_dst, cnt_src, src_index, seeds_in, ok_out);
+    LAUNCH_OK();
+    dst->init_valid = false;          // the restart image of k_step_fast belongs to the old instances
+    renewal_off(dst, false);          // the records no longer match dst's inst_seeds: not a generated batch any more
     return DCM_OK;
 }
 

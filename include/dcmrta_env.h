@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define DCM_ABI_VERSION 5 /* v3: dcm_build_id, dcm_set_visibility, dcm_load_instances validates req on the device; v4: dcm_set_replay_placement; v5: DCM_PARAM_WIDE_MEMBERS; still v5, additions only: dcm_generate_instances, dcm_get_instances, dcm_generator_draws, dcm_set_instance_renewal, dcm_instance_index, DCM_PARAM_RENEW_SIZES, dcm_set_rollout_log, dcm_set_best_log, dcm_reduce_best */
+#define DCM_ABI_VERSION 5 /* v3: dcm_build_id, dcm_set_visibility, dcm_load_instances validates req on the device; v4: dcm_set_replay_placement; v5: DCM_PARAM_WIDE_MEMBERS; still v5, additions only: dcm_generate_instances, dcm_get_instances, dcm_generator_draws, dcm_set_instance_renewal, dcm_instance_index, DCM_PARAM_RENEW_SIZES, dcm_set_rollout_log, dcm_set_best_log, dcm_reduce_best, dcm_fork_envs */
 
 typedef struct dcm_env dcm_env; /* opaque */
 
@@ -447,6 +447,38 @@ int dcm_get_abandoned(dcm_env *env, uint16_t *counts_out, void *stream);
 int dcm_state_bytes(dcm_env *env, size_t *bytes_out);
 int dcm_clone_state(dcm_env *env, void *dst, void *stream);
 int dcm_restore_state(dcm_env *env, const void *src, void *stream);
+
+/* Per-env copy between handles, on the device: for every env b of dst, s = src_index[b] (i32[B_dst], device):
+ *   s == -1   env b is left alone.
+ *   otherwise env b of dst BECOMES env s of src: the whole record -- header, mutable part and instance part, so the current time, the
+ *             decision counter, the episode count and the instance index come with it --, the dcm_summary row, the abandonment log
+ *             and its overflow counts.  Per env it is what dcm_clone_state / dcm_restore_state move for the whole batch, without the
+ *             two extra copies, between handles of any two batch sizes: B envs fan out to B x K branches in one launch.
+ *   seeds_in  u64[B_dst], device, or NULL.  Given, the choice-protocol seed in the header of every env that was copied becomes
+ *             seeds_in[b]; the decision counter is not touched.  NULL: the copy keeps the source's seed and, the protocol being a pure
+ *             function of (seed, decision counter, slot), behaves exactly as the source would have under any later sequence of calls
+ *             -- each handle under its own parameters (max_waiting_time, max_time).
+ *   ok_out    u8[B_dst], device, or NULL: 1 for every env that was copied or left alone, 0 for one that was refused (below).
+ * dst may be src.  In place the call is race-free by contract and by check: a source must be its own source,
+ * src_index[src_index[b]] == src_index[b], which the kernel tests with one more 4-byte load.  An env whose index breaks that rule, or
+ * -- in place or not -- lies outside [-1, B_src), is left untouched and gets ok_out[b] = 0; every other env gets 1, s == b in place
+ * included, where only the seed may change.  Between two handles the rule does not apply (nothing is read from dst).
+ * All writes are plain stores, there is no host synchronisation, and the call is legal under stream capture.
+ *   Refusals on the host, nothing launched and nothing changed, every message names dcm_fork_envs.  DCM_ERR_INVALID: n_agents,
+ *     n_tasks or DCM_PARAM_WIDE_MEMBERS differ between the handles (the record layouts must be identical); the handles are on different
+ *     devices; src_index NULL.  DCM_ERR_STATE: either handle has not been loaded and reset (also dst, although the call would fill
+ *     it: a kernel is never pointed at a record nobody wrote); either handle holds a ragged batch (the per-env sizes have a host copy
+ *     that a device-side map cannot keep in step); either handle has a renewal stride set; the current device is not the handles'.
+ *   Host bookkeeping on success: deferred terminal metrics of both handles are computed first (a parked snapshot must not land on a
+ *     copied summary row later); dst drops the restart image of its lockstep kernel (it belongs to the old instances; DCM_PARAM_AUTO_RESET
+ *     restarts then recompute the first event, with the same results); dst no longer counts as made by dcm_generate_instances (its
+ *     records no longer match its inst_seeds), so dcm_set_instance_renewal(dst, stride != 0) is refused until it is generated again.
+ *   NOT copied: the caller-owned logs -- the buffers of dcm_set_route_log, dcm_set_rollout_log, dcm_set_best_log and
+ *     dcm_set_return_log are not touched and stay dst's own lineage.  The episode count IS copied, so later return-log slots and
+ *     best_episode ordinals of dst continue from the source's count; a caller who wants a source's log rows in the copy gathers them
+ *     in their own memory.  Neither are the handle's parameters, seeds of dcm_generate_instances, routes or visibility schedule. */
+int dcm_fork_envs(dcm_env *dst, dcm_env *src, const int32_t *src_index, const uint64_t *seeds_in, uint8_t *ok_out,
+                  void *stream);
 
 /* calculate_eulidean_distance (env/task_env.py:161-163) and travel time (:315) on the device, for the
  * known-answer test of the fp64 sqrt/divide path: dist_out[n], time_out[n] (nullable). */
