@@ -1574,8 +1574,8 @@ constexpr uint32_t ROLLOUT_ERR = DCM_FLAG_BAD_ACTION | DCM_FLAG_OVERFLOW | DCM_F
 // this launch; when the budget runs out the env stays at the decision point it has reached (a later call -- dcm_rollout_random,
 // dcm_observe or dcm_step -- carries on from it) and the observation buffers hold what the last decision TAKEN saw.
 // Returns the decisions left in this launch: a 32-bit countdown is the only loop-carried counter (steps = budget - left afterwards).
+constexpr int NO_BUDGET = 0x7FFFFFFF;
 __device__ __forceinline__ int rollout_budget(int e, int64_t budget_all, const int64_t* budget_in) {
-    constexpr int NO_BUDGET = 0x7FFFFFFF;
     const int64_t bud = budget_in ? budget_in[e] : budget_all;
     return uni((int)((bud < 0 || bud >= NO_BUDGET) ? NO_BUDGET : bud));
 }

@@ -136,7 +136,28 @@ __global__ __launch_bounds__(WAVE, 4) void KNAME(int A, int T, int PA, int PT, K
         }
         if (need_adv) {
             CNT(15);
+#if defined(KEXPLORES) || defined(DCM_POLICY)
+            // The best-keeping form reads the row of every finished episode (keep_best).  The epsilon-greedy and greedy forms keep
+            // terminal() because the rule below costs their decision loops: k_ex_ 1257 -> 1356 instructions, k_hp_ 1175 -> 1180.
             S.advance(h, P, lane, row PH_PASS);
+#else
+            // An episode that ends here with another one of this call to follow leaves a summary row nobody can read: the next
+            // terminal() rewrites the row and the metrics' scratch, the restart clears the flags.  It takes the metric-free terminal
+            // (flags, episode count, return log).  Not under a budget -- the next episode may stop half way, and the row must then
+            // be the last FINISHED episode's -- and not for a flagged env, which stops at the restart.  Forms with the rule: plain,
+            // renewing, logging and renewing-logging, each with compile-time sizes.
+            // The runtime-size forms keep terminal(): with the second terminal in them their decision loops come out 1 - 3 instructions
+            // longer and one of them a VGPR larger (tests/test_episode_boundary_host.py), so they compile to the code they had.
+            if constexpr (RS) S.advance(h, P, lane, row PH_PASS);
+            else {
+                const bool no_metrics = left0 == NO_BUDGET && ep + 1 < episodes && !(h.flags & ROLLOUT_ERR);
+                S.advance(h, P, lane, row PH_PASS, false, false, no_metrics);
+#ifdef DCM_COUNT_PATHS
+                if (h.flags & DCM_FLAG_DONE) { if (h.flags & SimT::FLAG_DEFERRED) CNT(19); else CNT(18); }
+#endif
+                h.flags &= ~SimT::FLAG_DEFERRED;                                  // internal: never stored, never seen by the loop
+            }
+#endif
             need_adv = false;
             // wave-uniform by construction; tell the compiler so (scalar branches in the fast loop)
             h.now = uni(h.now); h.flags = uni(h.flags); h.cur_group = uni(h.cur_group); h.n_groups = uni(h.n_groups);

@@ -58,7 +58,10 @@ __global__ __launch_bounds__(WAVE, DCM_MC_WAVES) void KNAME(int A, int T, int PA
             }
         }
         if (need_adv) {
-            S.advance(h, P, lane, row PH_PASS);
+            // no terminal metrics for an episode whose summary row the next one of this call rewrites (see k_rollout_fast.inc)
+            const bool no_metrics = left0 == NO_BUDGET && ep + 1 < episodes && !(h.flags & ROLLOUT_ERR);
+            S.advance(h, P, lane, row PH_PASS, false, false, no_metrics);
+            h.flags &= ~SimT::FLAG_DEFERRED;
             need_adv = false;
             h.now = uni(h.now); h.flags = uni(h.flags); h.cur_group = uni(h.cur_group); h.n_groups = uni(h.n_groups);
             h.empty_passes = uni(h.empty_passes);

@@ -409,7 +409,10 @@ int dcm_rollout_explore(dcm_env *env, int32_t policy, uint64_t explore_q32, int3
 
 /* Terminal results of the last finished episode (worker.py:87,103-108):
  * out[B,8] f64 = reward(-makespan), n_finished_tasks, success_rate, makespan, time_cost,
- *                waiting_time, travel_dist, efficiency. Rows of envs not yet done are NaN. */
+ *                waiting_time, travel_dist, efficiency. Rows of envs not yet done are NaN.
+ * For an env that stops with an error flag (DCM_FLAG_BAD_*, DCM_FLAG_OVERFLOW) inside a multi-episode rollout call without a decision
+ * budget, the row is that of some earlier finished episode of the call (or what it held before), not necessarily the latest: such a
+ * call computes the metrics of the episode it ends with, and of every episode while a budget is set. */
 int dcm_summary(dcm_env *env, double *out, void *stream);
 
 /* Per-env flags (DCM_FLAG_*), decision counters and current time. Any pointer may be NULL. */
