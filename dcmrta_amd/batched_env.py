@@ -304,7 +304,7 @@ class BatchedTaskEnv:
 
     POLICIES = {"random": _lib.POLICY_RANDOM, "first": _lib.POLICY_FIRST, "nearest": _lib.POLICY_NEAREST}
 
-    def rollout(self, policy="random", episodes=1, write_obs=True, max_decisions=-1, *, explore=None, explore_q32=None):
+    def rollout(self, policy="random", episodes=1, write_obs=True, max_decisions=-1, *, explore=None, explore_q32=None, lookahead=False):
         """`episodes` full episodes per env in one persistent launch under a device policy (dcm_rollout_policy): "random" (uniform
         over the unmasked tasks: the config-2 hot path), "first" (the lowest unmasked task) or "nearest" (the unmasked task closest
         to the deciding agent, ties to the lowest index).
@@ -314,9 +314,18 @@ class BatchedTaskEnv:
         "first" / "nearest" (dcm_rollout_explore) -- a decision takes the random policy's action with probability epsilon, decided by
         the choice protocol's explore word (choice.explores), and the base policy's pick otherwise.  Give at most one of the two;
         with neither the call is the plain one.
+        lookahead=True: every decision is chosen by one-step lookahead over the base `policy` (any of the three), on the device and
+        inside the same persistent launch (dcm_rollout_lookahead): the env's wave values each unmasked action by the episode in which
+        the leader takes it now and `policy` plays every later decision, and takes the action with the largest (finished tasks,
+        reward), ties to the lowest index -- Lookahead.values() + best_actions() of lookahead.py, bit for bit, with no branch handle
+        and no host round trip.  episodes, max_decisions (outer decisions only), the rollout log, the return log, instance renewal
+        and ragged batches work as in every other call; the handle needs max_waiting_time > 0 and no best log, and explore /
+        explore_q32 cannot be combined with it.
         Returns steps int64[B] (device tensor)."""
         if policy not in self.POLICIES:
             raise DcmError("policy must be one of %s" % ", ".join(repr(p) for p in self.POLICIES))
+        if lookahead and (explore is not None or explore_q32 is not None):
+            raise DcmError("lookahead=True takes the base policy's own decisions inside its rollouts: it cannot be combined with explore / explore_q32")
         q32 = None
         if explore is not None or explore_q32 is not None:
             if explore is not None and explore_q32 is not None:
@@ -341,7 +350,10 @@ class BatchedTaskEnv:
                 raise DcmError("max_decisions must be an int or int64[B]")
             max_decisions = -1
         with torch.cuda.device(self.device):
-            if q32 is None:
+            if lookahead:
+                check(self._lib.dcm_rollout_lookahead(self._h, self.POLICIES[policy], int(episodes), int(max_decisions), _ptr(per_env),
+                                                      *[_ptr(x) for x in o], _ptr(steps), self._stream()))
+            elif q32 is None:
                 check(self._lib.dcm_rollout_policy(self._h, self.POLICIES[policy], int(episodes), int(max_decisions), _ptr(per_env),
                                                    *[_ptr(x) for x in o], _ptr(steps), self._stream()))
             else:

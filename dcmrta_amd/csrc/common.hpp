@@ -590,6 +590,7 @@ struct dcm_env {
     bool init_valid = false, init_failed = false;
     int steps_since_flush = 0;
     bool maybe_pending = false, side_failed = false;
+    unsigned char* la_snap = nullptr;   // dcm_rollout_lookahead: [B][rec_bytes + 64 + 32 A + abcnt_pitch] the envs' snapshots, allocated at its first launch
     bool captured = false;           // a dcm_step of this handle was captured into a graph: every later step computes its metrics inline
     static constexpr int FLUSH_EVERY = 32;
 };

@@ -30,7 +30,7 @@
 
 using namespace dcm;
 
-// Translation units (Makefile).  The library is built from this file six times; every unit but the main one holds device code and
+// Translation units (Makefile).  The library is built from this file seven times; every unit but the main one holds device code and
 // its launchers only, and the main unit reaches them through the dcm::launch_rollout_* functions declared below.
 //   unit    macro          holds                                                          options
 //   env     -DDCM_SPLIT_G  the host API and every kernel that is not in a unit below      SPLIT SCHED
@@ -39,11 +39,12 @@ using namespace dcm;
 //   env_l   -DDCM_TU_L     the logging forms k_lg_* / k_lgrn_* (rollout_log.hpp)          SPLIT SCHED
 //   env_e   -DDCM_TU_E     the epsilon-greedy forms k_ex_* / k_exrn_* (rollout_explore.hpp)  SPLIT SCHED
 //   env_b   -DDCM_TU_B     the best-keeping form k_bs_* (rollout_best.hpp)                 SPLIT SCHED
+//   env_a   -DDCM_TU_A     the lookahead form k_la_* / k_larn_* (rollout_lookahead.hpp)    SPLIT SCHED
 // SPLIT (-mllvm -phi-elim-split-all-critical-edges=1) costs k_rollout_fast_g 4 % (8.19 -> 8.53 ms per 4096 x 70A/130T launch) while it
 // buys the one-chunk and the 50A/200T kernel 2.1 % / 1.3 %: hence env_g.  The form units exist so that every kernel that was there
 // before them compiles from the text, and to the code, it had without them.  With none of the macros (the developer tools'
 // one-command builds) everything is in one unit.
-#if defined(DCM_TU_G) || defined(DCM_TU_P) || defined(DCM_TU_L) || defined(DCM_TU_E) || defined(DCM_TU_B)
+#if defined(DCM_TU_G) || defined(DCM_TU_P) || defined(DCM_TU_L) || defined(DCM_TU_E) || defined(DCM_TU_B) || defined(DCM_TU_A)
 #define DCM_DEVICE_ONLY_TU 1
 #elif !defined(DCM_SPLIT_G)
 #define DCM_ONE_UNIT 1
@@ -62,6 +63,9 @@ using namespace dcm;
 #endif
 #if defined(DCM_TU_B) || defined(DCM_ONE_UNIT)
 #define DCM_HAVE_BEST 1       // ... the best-keeping form and its launcher
+#endif
+#if defined(DCM_TU_A) || defined(DCM_ONE_UNIT)
+#define DCM_HAVE_LOOKAHEAD 1  // ... the lookahead form and its launcher
 #endif
 namespace dcm {
 #if !defined(DCM_DEVICE_ONLY_TU)
@@ -93,6 +97,7 @@ struct RolloutArgs {
     RouteLog lg{nullptr, nullptr, nullptr, 0};   // last argument of the logging forms (k_lg_*, k_lgrn_*), behind `policy`
     uint64_t explore_q32 = 0;          // the epsilon-greedy forms (k_ex_*, k_exrn_*): between `policy` and the log
     BestLog best{nullptr, nullptr, nullptr, nullptr, nullptr};   // the best-keeping form (k_bs_*): behind the epsilon-greedy forms' arguments
+    unsigned char* snap = nullptr;     // the lookahead form (k_la_*, k_larn_*): the handle's snapshot buffer, behind `policy` and the log
 };
 // k_rollout_fast_g<NAC, NTC, OBS> / k_rn_rollout_fast_g / k_rs_rollout_fast_g (rollout_fast_g.hpp, its own translation unit)
 void launch_rollout_fast_g(int nac, int ntc, bool obs, unsigned grid, Lay L, hipStream_t stream, const RolloutArgs& a);
@@ -104,11 +109,14 @@ void launch_rollout_fast_g(int nac, int ntc, bool obs, unsigned grid, Lay L, hip
 // Return 0, or -1 when `kind` has no one-chunk kernel (the caller asked plan::form_rollout_kind, so it has).
 // allow_lds_*: the form's share of dcm_create's dynamic-LDS limit (see there).
 using FormLauncher = int(plan::SimKind kind, bool fast, bool obs, unsigned grid, Lay L, hipStream_t stream, const RolloutArgs& a);
-FormLauncher launch_rollout_policy, launch_rollout_log, launch_rollout_explore, launch_rollout_best;
+// The lookahead form (k_la_* / k_larn_*) takes a.policy (any of the three), a.lg (set or not) and a.snap; it exists for the general
+// kernel text alone: `fast` and `obs` are ignored.
+FormLauncher launch_rollout_policy, launch_rollout_log, launch_rollout_explore, launch_rollout_best, launch_rollout_lookahead;
 void allow_lds_policy(int lds);
 void allow_lds_log(int lds);
 void allow_lds_explore(int lds);
 void allow_lds_best(int lds);
+void allow_lds_lookahead(int lds);
 }  // namespace dcm
 
 namespace {
@@ -350,6 +358,22 @@ struct Sim {
             copy16(rec, base, l.marr(), lane);
             copy16(rec + l.mids(), base + l.mids() - MSH, l.mut_bytes() - l.mids(), lane);
         } else copy16(rec, base, l.mut_bytes(), lane);
+    }
+    // ... and back: the mutable part of a record image `img` that store_record wrote -> the LDS image (the lookahead form's restore;
+    // the instance part of the LDS image stays).  MG: the member arrival times are not in LDS, see snapshot_marr / restore_marr.
+    __device__ __forceinline__ void load_mutable(const unsigned char* img, int lane) const {
+        const Lay l = L();
+        if constexpr (MG) {
+            copy16_in(base, img, l.marr(), lane);
+            copy16_in(base + l.mids() - MSH, img + l.mids(), l.mut_bytes() - l.mids(), lane);
+        } else copy16_in(base, img, l.mut_bytes(), lane);
+    }
+    // MG: the member arrival times live in the env's HBM record (gm): HBM -> HBM between the record and a record image
+    __device__ __forceinline__ void snapshot_marr(unsigned char* img, int lane) const {
+        if constexpr (MG) copy16_in(img + L().marr(), (const unsigned char*)gm, MSH, lane);
+    }
+    __device__ __forceinline__ void restore_marr(const unsigned char* img, int lane) const {
+        if constexpr (MG) copy16_in((unsigned char*)gm, img + L().marr(), MSH, lane);
     }
 
     // optional return log (dcm_set_return_log): this env's ring of `cap` episode returns; pointer kept in the LDS image
@@ -914,6 +938,14 @@ struct Sim {
         h.cur_group = 0;
     }
 
+    // The end of an INNER episode of the lookahead form (k_la_*): the episode is over and nothing else happens -- no metrics, no
+    // summary row, no episode count, no return log.  Its value is read off the state: (finished tasks, -now), which is what
+    // terminal_metrics would have put into entries 1 and 0 of the row.
+    __device__ __forceinline__ void terminal_inner(HdrRegs& h) const {
+        h.flags |= DCM_FLAG_DONE;
+        h.cur_group = 0;
+    }
+
     // What terminal() does without the metrics (k_step_fast with a snapshot buffer, see dcm_env::side): the caller parks the record,
     // k_terminal_flush computes reward + metrics from it later.  The informational WAIT_ORDER flag is not kept: the env restarts
     // in this very launch, which clears the flags anyway.
@@ -935,6 +967,8 @@ struct Sim {
     // (worker.py:50-51).  Returns at the next decision point or after terminal().
     // no_grouping: every deciding agent forms ONE group (individual selection, worker.py:159-198 iterates the deciders without
     // get_unique_group); lockstep API only.
+    // INNER: an inner episode of the lookahead form, which ends in terminal_inner.
+    template <bool INNER = false>
     __device__ __forceinline__ void advance(HdrRegs& h, const KP& P, int lane, double* __restrict__ row PH_ARGS,
                                             bool no_grouping = false, bool track = false, bool defer = false) const {
         const int A_ = A();
@@ -971,7 +1005,8 @@ struct Sim {
             }
             if (finished) h.flags |= DCM_FLAG_FINISHED;
             if (finished || h.now >= P.max_time) {                           // worker.py:45
-                if (defer) terminal_deferred(h, lane); else terminal(h, P, lane, row);
+                if constexpr (INNER) terminal_inner(h);
+                else if (defer) terminal_deferred(h, lane); else terminal(h, P, lane, row);
                 return;
             }
             // ---- A: new event
@@ -1048,7 +1083,8 @@ struct Sim {
             if (!any) {
                 if (++h.empty_passes > 4) {
                     h.flags |= DCM_FLAG_TRUNCATED;
-                    if (defer) terminal_deferred(h, lane); else terminal(h, P, lane, row);
+                    if constexpr (INNER) terminal_inner(h);
+                    else if (defer) terminal_deferred(h, lane); else terminal(h, P, lane, row);
                     return;
                 }
                 continue;
@@ -1256,7 +1292,8 @@ struct Sim {
     // DEV: the action comes from the device's own valid-action policy on a validated instance (persistent kernel): the error
     // exits below cannot be taken and are compiled out -- each `return` in the middle of the step costs the structured control
     // flow of the whole function scalar bookkeeping at every decision.
-    template <bool DEV = false>
+    // INNER: advance<INNER>, see there.
+    template <bool DEV = false, bool INNER = false>
     __device__ __forceinline__ void apply_and_advance(HdrRegs& h, const KP& P, int lane, int leader, const AMask& gm0,
                                                       int action, uint64_t k1, int nfol_in,
                                                       const int16_t* __restrict__ fol_in, double* __restrict__ row PH_ARGS,
@@ -1401,7 +1438,7 @@ struct Sim {
         PH_MARK(5);
         if (rlen > 0) return;                                                 // worker.py:53 same group, next leader
         if (h.cur_group < h.n_groups) { h.cur_group++; return; }              // worker.py:52 next group
-        advance(h, P, lane, row PH_PASS, no_grouping, track);                 // worker.py:85 -> :45
+        advance<INNER>(h, P, lane, row PH_PASS, no_grouping, track);          // worker.py:85 -> :45
         PH_MARK(9);
     }
 
@@ -1629,6 +1666,9 @@ constexpr uint32_t rollout_random_lds_bytes(Lay L) {
 #endif
 #ifdef DCM_HAVE_BEST
 #include "rollout_best.hpp"
+#endif
+#ifdef DCM_HAVE_LOOKAHEAD
+#include "rollout_lookahead.hpp"
 #endif
 
 __global__ __launch_bounds__(WAVE) void k_env_status(int PA, int PT, int PC, const unsigned char* state, int B, uint32_t* flags_out,
@@ -1927,6 +1967,25 @@ DCM_PLAIN_FORM_LAUNCHERS(best, k_bs_, a.policy, a.explore_q32, a.lg, a.best)
 #undef DCM_FORM_LAUNCHERS_
 #undef DCM_PLAIN_FORM_LAUNCHERS
 #undef DCM_FORM_LAUNCHERS
+// The lookahead form has the general family alone (no k_la_rollout_fast): written out instead of a third shape of the macro above
+#ifdef DCM_HAVE_LOOKAHEAD
+namespace {
+struct lookahead_general { DCM_FORMS(k_la_rollout_random, k_larn_rollout_random) };
+}
+int dcm::launch_rollout_lookahead(plan::SimKind kind, bool, bool, unsigned grid, Lay L, hipStream_t stream, const RolloutArgs& a) {
+    return with_sim(kind, [&](auto s) {
+        using S = decltype(s);
+        return launch_family<lookahead_general, false, SIM_ARGS(S), S::MC>(a.form, grid, rollout_random_lds_bytes<SIM_ARGS(S)>(L), stream,
+                                                                           a.kernel_args(), a.rn, a.policy, a.lg, a.snap);
+    });
+}
+void dcm::allow_lds_lookahead(int lds) {
+    for_each_sim([&](auto s) {
+        using S = decltype(s);
+        allow_lds(lds, lookahead_general::plain<SIM_ARGS(S), S::MC>(), lookahead_general::renewing<SIM_ARGS(S), S::MC>());
+    });
+}
+#endif
 #undef DCM_FORMS
 #undef DCM_FORM
 
@@ -2032,7 +2091,9 @@ dcm::RolloutArgs rollout_args(const dcm_env* env, plan::RenewForm form, int32_t 
 
 // A greedy, logging or epsilon-greedy form to the host: its launcher, and what `fn` says when a size-renewing launch asks for it
 // (keeps_best: the best-keeping form, which rollout_form also refuses without the rollout log and while any renewal stride is set)
-struct RolloutForm { dcm::FormLauncher* launch; const char* no_sizes_form; bool keeps_best = false; };
+// (lookahead: the lookahead form, which has no one-chunk kernels -- every shape takes the general text -- and whose snapshot buffer
+//  rollout_form allocates at the first launch)
+struct RolloutForm { dcm::FormLauncher* launch; const char* no_sizes_form; bool keeps_best = false; bool lookahead = false; };
 const RolloutForm FORM_POLICY{dcm::launch_rollout_policy,
     "%s: no greedy policy while a ragged batch renews its sizes (DCM_PARAM_RENEW_SIZES with a stride set): "
     "clear the stride with dcm_set_instance_renewal(env, 0), or use DCM_POLICY_RANDOM"};
@@ -2045,6 +2106,9 @@ const RolloutForm FORM_EXPLORE{dcm::launch_rollout_explore,
 const RolloutForm FORM_BEST{dcm::launch_rollout_best,
     "%s: no best log while instances are renewed (the best episode of different instances means nothing): clear the stride with "
     "dcm_set_instance_renewal(env, 0), or clear the best log with dcm_set_best_log(env, NULL, NULL, NULL, NULL, NULL)", true};
+const RolloutForm FORM_LOOKAHEAD{dcm::launch_rollout_lookahead,
+    "%s: no lookahead while a ragged batch renews its sizes (DCM_PARAM_RENEW_SIZES with a stride set): clear the stride with "
+    "dcm_set_instance_renewal(env, 0)", false, true};
 // the form an entry point takes: the best-keeping one while dcm_set_best_log is set, else its own
 const RolloutForm& form_of(const dcm_env* env, const RolloutForm& own) { return env->best_log.episode ? FORM_BEST : own; }
 
@@ -2062,6 +2126,19 @@ int rollout_form(dcm_env* env, const char* fn, const RolloutForm& form, int32_t 
         if (env->renew_stride != 0) return fail(DCM_ERR_STATE, form.no_sizes_form, fn);
     }
     if (!plan::form_ok(launch_form(env))) return fail(DCM_ERR_STATE, form.no_sizes_form, fn);
+    if (form.lookahead && !env->la_snap) {
+        // per env one env's share of the dcm_clone_state blob: record, 64 B, abandonment rows, overflow counts.  Allocated here, at
+        // the first lookahead launch, behind every refusal: hipMalloc is not allowed while the stream is capturing
+        if (stream_capturing(stream))
+            return fail(DCM_ERR_STATE, "%s: the first call on a handle allocates the snapshot buffer and cannot be captured into a graph: "
+                                       "call it once outside the capture", fn);
+        const size_t pitch = (size_t)env->L.rec_bytes() + 64u + 2u * AB_CAP * (size_t)env->A + abcnt_pitch(env->A, env->T);
+        if (hipMalloc((void**)&env->la_snap, (size_t)env->p.n_envs * pitch) != hipSuccess) {
+            (void)hipGetLastError();
+            env->la_snap = nullptr;
+            return fail(DCM_ERR_HIP, "%s: hipMalloc of the snapshot buffer failed", fn);
+        }
+    }
     DCM_TRY(dcm::flush_pending(env, stream));
     dcm::RolloutArgs ra = rollout_args(env, renewing_launch(env, stream), episodes, max_decisions, max_decisions_in, agents_out, tasks_out,
                                        mask_out, steps_out);
@@ -2069,9 +2146,10 @@ int rollout_form(dcm_env* env, const char* fn, const RolloutForm& form, int32_t 
     ra.explore_q32 = explore_q32;
     ra.lg = env->rollout_log;          // (the epsilon-greedy forms take it set or not: one set of forms)
     ra.best = env->best_log;
+    ra.snap = env->la_snap;
     const bool all_obs = agents_out && tasks_out && mask_out, no_obs = !agents_out && !tasks_out && !mask_out;
     const plan::Shape shape = shape_of(env);
-    const bool fast = plan::form_rollout_kind(shape, all_obs || no_obs) == plan::Rollout::Fast;
+    const bool fast = !form.lookahead && plan::form_rollout_kind(shape, all_obs || no_obs) == plan::Rollout::Fast;
     return launched(form.launch(plan::sim_kind(shape), fast, all_obs, (unsigned)env->p.n_envs, env->L, (hipStream_t)stream, ra));
 }
 
@@ -2181,6 +2259,7 @@ int dcm_create(const dcm_params* params, dcm_env** out) {
     dcm::allow_lds_log(lds);
     dcm::allow_lds_explore(lds);
     dcm::allow_lds_best(lds);
+    dcm::allow_lds_lookahead(lds);
     allow_lds(lds, k_get_tasks<M>, k_get_agents<M>, k_get_tasks<MW>, k_get_agents<MW>);
     return DCM_OK;
 }
@@ -2189,7 +2268,7 @@ int dcm_destroy(dcm_env* env) {
     if (!env) return DCM_OK;
     DeviceGuard guard(env->p.device);
     void* const owned[] = {env->state, env->summary, env->ablog, env->gscratch, env->routes, env->route_len,
-                           env->rmarr, env->sizes, env->side, env->pendq, env->init, env->inst_seeds};
+                           env->rmarr, env->sizes, env->side, env->pendq, env->init, env->inst_seeds, env->la_snap};
     for (void* p : owned)
         if (p) (void)hipFree(p);
     delete env;
@@ -2626,6 +2705,25 @@ int dcm_rollout_explore(dcm_env* env, int32_t policy, uint64_t explore_q32, int3
     if (episodes < 1) return fail(DCM_ERR_INVALID, "dcm_rollout_explore: episodes must be >= 1");
     DCM_TRY(need_budget(env, "dcm_rollout_explore", max_decisions, max_decisions_in));
     return rollout_form(env, "dcm_rollout_explore", form_of(env, FORM_EXPLORE), policy, explore_q32, episodes, max_decisions, max_decisions_in, agents_out,
+                        tasks_out, mask_out, steps_out, stream);
+}
+
+int dcm_rollout_lookahead(dcm_env* env, int32_t base_policy, int32_t episodes, int64_t max_decisions, const int64_t* max_decisions_in,
+                          float* agents_out, float* tasks_out, uint8_t* mask_out, int64_t* steps_out, void* stream) {
+    CHECK_ENV(env);
+    if (base_policy != DCM_POLICY_RANDOM && base_policy != DCM_POLICY_FIRST && base_policy != DCM_POLICY_NEAREST)
+        return fail(DCM_ERR_INVALID, "dcm_rollout_lookahead: unknown base policy (DCM_POLICY_RANDOM, DCM_POLICY_FIRST, DCM_POLICY_NEAREST)");
+    if (episodes < 1) return fail(DCM_ERR_INVALID, "dcm_rollout_lookahead: episodes must be >= 1");
+    // every inner episode must end by itself; a decision budget bounds the outer decisions only
+    if (!(env->kp.mwt > 0.0))
+        return fail(DCM_ERR_INVALID, "dcm_rollout_lookahead: the handle has max_waiting_time <= 0, where a base policy does not end its episodes "
+                                     "(a dropped member takes the same task again at the same time): an action has no episode to be valued by, "
+                                     "with or without a decision budget");
+    if (!env->reset_done) return fail(DCM_ERR_STATE, "dcm_rollout_lookahead: call dcm_reset first");
+    if (env->best_log.episode)
+        return fail(DCM_ERR_STATE, "dcm_rollout_lookahead: the best log is set and there is no best-keeping lookahead form: clear it with "
+                                   "dcm_set_best_log(env, NULL, NULL, NULL, NULL, NULL)");
+    return rollout_form(env, "dcm_rollout_lookahead", FORM_LOOKAHEAD, base_policy, 0, episodes, max_decisions, max_decisions_in, agents_out,
                         tasks_out, mask_out, steps_out, stream);
 }
 

@@ -5,7 +5,8 @@
 //     #define KPOLICY_FORMS 1            only if it has the forms of the second table
 //     #include "k_form.inc"
 // in front of its kernel, declares it as KNAME(..., KSIZES, ... int retcap KRENEW_PARAM KPOLICY_PARAM), and ends with
-// #include "k_form_end.inc".  Whoever includes the text sets DCM_RENEW and at most one of DCM_POLICY, DCM_LOG, DCM_EXPLORE, DCM_BEST.
+// #include "k_form_end.inc".  Whoever includes the text sets DCM_RENEW and at most one of DCM_POLICY, DCM_LOG, DCM_EXPLORE, DCM_BEST,
+// DCM_LOOKAHEAD.
 //
 //   DCM_RENEW   KNAME          launched                                            KRENEW_PARAM   KSIZES
 //   0           k_<base>       without a renewal stride                            --             const int32_t* sizes
@@ -21,6 +22,7 @@
 //   DCM_LOG       k_lg_<base> / k_lgrn_<base>    either, dcm_set_rollout_log set      , int policy, RouteLog lg
 //   DCM_EXPLORE   k_ex_<base> / k_exrn_<base>    dcm_rollout_explore                  , int policy, uint64_t explore_q32, RouteLog lg
 //   DCM_BEST      k_bs_<base> / --               any of the three, dcm_set_best_log   , int policy, uint64_t explore_q32, RouteLog lg, BestLog best
+//   DCM_LOOKAHEAD k_la_<base> / k_larn_<base>    dcm_rollout_lookahead                , int policy, RouteLog lg, unsigned char* snap
 // Greedy: the action comes from `policy` (wave-uniform) instead of protocol slot 1.  Logging: `policy` covers all three policies
 // (DCM_POLICY_RANDOM takes slot 1 as the plain form does) and every agent_step is appended to the log.  Epsilon-greedy: the logging
 // form with explore_q32; the log may be unset there (lg.len null).  These forms exist for k_rollout_fast and k_rollout_random only,
@@ -30,6 +32,9 @@
 // form (explore_q32 = 0 under dcm_rollout_random / dcm_rollout_policy: their k_lg_* decisions and budget rule), plus ONE hook where the
 // text sees a freshly finished episode: keep_best (rollout_best.hpp) copies the env's summary row and its rows of the log to the best
 // log if the episode beats the kept one.  No renewing form at all: the host refuses a best-keeping launch while a stride is set.
+// Lookahead (rollout_lookahead.hpp): every decision is chosen by one-step lookahead over the base `policy` (any of the three) -- the
+// wave snapshots its env into its slice of `snap`, plays one inner episode per unmasked action and restores -- and the logging code
+// rides along as in the epsilon-greedy forms (lg.len null: no log).  k_rollout_random only; no size-renewing form.
 // KEXPLORES (defined here, for the texts): the form draws explore words -- DCM_EXPLORE or DCM_BEST.
 //
 // Two kernels from one text leave the first as it was: a form holds nothing of the others and compiles to the code it had before
@@ -38,11 +43,17 @@
 #ifndef KBASE
 #error "k_form.inc: the including text sets KBASE"
 #endif
-#if defined(DCM_POLICY) + defined(DCM_LOG) + defined(DCM_EXPLORE) + defined(DCM_BEST) > 1
-#error "at most one of DCM_POLICY, DCM_LOG, DCM_EXPLORE, DCM_BEST"
+#if defined(DCM_POLICY) + defined(DCM_LOG) + defined(DCM_EXPLORE) + defined(DCM_BEST) + defined(DCM_LOOKAHEAD) > 1
+#error "at most one of DCM_POLICY, DCM_LOG, DCM_EXPLORE, DCM_BEST, DCM_LOOKAHEAD"
 #endif
 #if (defined(DCM_POLICY) || defined(DCM_LOG) || defined(DCM_EXPLORE) || defined(DCM_BEST)) && !defined(KPOLICY_FORMS)
 #error "this kernel text has no greedy, logging, epsilon-greedy or best-keeping form"
+#endif
+#if defined(DCM_LOOKAHEAD) && !defined(KLOOKAHEAD_FORM)
+#error "the lookahead form exists for k_rollout_random only"
+#endif
+#if defined(DCM_LOOKAHEAD) && DCM_RENEW == 2
+#error "no size-renewing lookahead form"
 #endif
 #if defined(DCM_BEST) && DCM_RENEW != 0
 #error "no renewing best-keeping form"
@@ -79,6 +90,9 @@
 #elif defined(DCM_BEST)
 #define KPREFIX k_bs_
 #define KPOLICY_PARAM , int policy, uint64_t explore_q32, RouteLog lg, BestLog best
+#elif defined(DCM_LOOKAHEAD)
+#define KPREFIX KFORM_PICK(k_la_, k_larn_)
+#define KPOLICY_PARAM , int policy, RouteLog lg, unsigned char* snap
 #elif DCM_RENEW == 2
 #define KPREFIX k_rs_
 #define KPOLICY_PARAM

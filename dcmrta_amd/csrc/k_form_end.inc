@@ -9,4 +9,5 @@
 #undef KRENEW_PARAM
 #undef KFORM_PICK
 #undef KPOLICY_FORMS
+#undef KLOOKAHEAD_FORM
 #undef KBASE

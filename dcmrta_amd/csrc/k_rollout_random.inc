@@ -1,13 +1,18 @@
 // k_rollout_random.inc -- the kernel k_rollout_random and all its forms (k_form.inc), compiled once per form: the plain, renewing and
-// size-renewing ones by dcmrta_env.hip, the others by rollout_policy.hpp, rollout_log.hpp, rollout_explore.hpp and rollout_best.hpp.
+// size-renewing ones by dcmrta_env.hip, the others by rollout_policy.hpp, rollout_log.hpp, rollout_explore.hpp, rollout_best.hpp and
+// rollout_lookahead.hpp.
 // Logging forms: apply_and_advance appends to the log, and the env zeroes its lengths when it restarts an episode.
 // Epsilon-greedy forms: a decision whose explore word (mix64(key_1 ^ EXPLORE_SALT) >> 32) is below explore_q32 takes
 // pick_random_action, every other one pick_policy_action of the base policy (FIRST / NEAREST).  The budget is the greedy forms'
 // (rollout_budget_policy).
 // Best-keeping form (rollout_best.hpp): the epsilon-greedy decision with `policy` covering DCM_POLICY_RANDOM and the budget rule of the
 // logging forms (explore_q32 = 0 there: the k_lg_* launch), plus keep_best behind the decision loop of a finished episode.
+// Lookahead form (rollout_lookahead.hpp): the logging form's loop -- budget rule, restart, observation rows, log, all of them the OUTER
+// decisions' -- with lookahead_action in the place of the policy's pick: the wave plays one inner episode per unmasked action
+// between two snapshots of its env and takes the action whose episode ends best.
 #define KBASE rollout_random
 #define KPOLICY_FORMS 1
+#define KLOOKAHEAD_FORM 1
 #include "k_form.inc"
 template <int CA, int CT, bool RS, int MC = M>
 __global__ __launch_bounds__(WAVE, 3) void KNAME(int A, int T, int PA, int PT, KP P, unsigned char* state, int episodes,
@@ -43,7 +48,7 @@ __global__ __launch_bounds__(WAVE, 3) void KNAME(int A, int T, int PA, int PT, K
     double* row = summary + (size_t)e * 8;
 #if defined(DCM_POLICY) || defined(DCM_EXPLORE)
     const int left0 = rollout_budget_policy(e, budget_all, budget_in, P);
-#elif defined(DCM_LOG) || defined(DCM_BEST)
+#elif defined(DCM_LOG) || defined(DCM_BEST) || defined(DCM_LOOKAHEAD)
     const int left0 = policy == DCM_POLICY_RANDOM ? rollout_budget(e, budget_all, budget_in) : rollout_budget_policy(e, budget_all, budget_in, P);
 #else
     const int left0 = rollout_budget(e, budget_all, budget_in);
@@ -64,7 +69,7 @@ __global__ __launch_bounds__(WAVE, 3) void KNAME(int A, int T, int PA, int PT, K
 #elif DCM_RENEW
             wave_renew_instance_call(S, rec, rn, e, lane, xy);
 #endif
-#ifdef KEXPLORES
+#if defined(KEXPLORES) || defined(DCM_LOOKAHEAD)
             if (lg.len) for (int a = lane; a < S.A(); a += WAVE) lg.len[(size_t)e * BA + a] = 0;   // the log, if set, is the new episode's
 #elif defined(DCM_LOG)
             for (int a = lane; a < S.A(); a += WAVE) lg.len[(size_t)e * BA + a] = 0;   // the log is the new episode's (as k_step's restart)
@@ -93,6 +98,8 @@ __global__ __launch_bounds__(WAVE, 3) void KNAME(int A, int T, int PA, int PT, K
 #else
             const int action = explores ? S.pick_random_action(lane, k1) : S.pick_policy_action(lane, leader, policy, xy);
 #endif
+#elif defined(DCM_LOOKAHEAD)
+            const int action = lookahead_action(S, h, P, lane, leader, gm, k1, gd, policy, xy, snap, e, BA, BT PH_PASS);
 #elif defined(DCM_POLICY)
             const int action = S.pick_policy_action(lane, leader, policy, xy);
 #elif defined(DCM_LOG)
@@ -101,7 +108,7 @@ __global__ __launch_bounds__(WAVE, 3) void KNAME(int A, int T, int PA, int PT, K
             const int action = S.pick_random_action(lane, k1);
 #endif
             PH_MARK(2);
-#if defined(DCM_LOG) || defined(KEXPLORES)
+#if defined(DCM_LOG) || defined(KEXPLORES) || defined(DCM_LOOKAHEAD)
             S.template apply_and_advance<true>(h, P, lane, leader, gm, action, k1, -1, nullptr, row PH_PASS, lg, e * BA, false, 0, true, false, &xy);
 #else
             S.template apply_and_advance<true>(h, P, lane, leader, gm, action, k1, -1, nullptr, row PH_PASS, RouteLog{nullptr, nullptr, nullptr, 0}, 0, false, 0, true, false, &xy);

@@ -89,6 +89,8 @@ inline Rollout rollout_kind(const Shape& s, bool obs_all_or_none) {
 // while dcm_set_rollout_log is set, under any of the three policies) and epsilon-greedy (dcm_rollout_explore).  They exist for the
 // one-chunk register-resident kernel and for the general one only: where rollout_kind says FastMc or FastG (50A/200T, the mid sizes)
 // such a launch takes the general kernel.
+// The lookahead form (dcm_rollout_lookahead) exists for the general kernel only: its launches do not ask this function, every shape
+// takes k_la_rollout_random.
 inline Rollout form_rollout_kind(const Shape& s, bool obs_all_or_none) {
     return rollout_kind(s, obs_all_or_none) == Rollout::Fast ? Rollout::Fast : Rollout::General;
 }

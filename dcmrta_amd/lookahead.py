@@ -14,7 +14,9 @@ protocol is a pure function of (seed, decision counter, slot), so the values are
 base policy itself picks is the result of the base policy's own episode, and plan(), which always takes the action with the largest
 (finished tasks, reward), never ends below the base policy started from the same state.
 All T + 1 actions get a branch, the masked ones too (they run the env's lowest unmasked action and their values are dropped):
-compacting the branches to the unmasked actions would make the fan-out data dependent."""
+compacting the branches to the unmasked actions would make the fan-out data dependent.
+The same decisions without a branch handle and without the host: BatchedTaskEnv.rollout(policy, lookahead=True), the device form, in
+which every env's wave values its own actions one after the other inside one persistent launch."""
 import torch
 
 from ._lib import DcmError

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define DCM_ABI_VERSION 5 /* v3: dcm_build_id, dcm_set_visibility, dcm_load_instances validates req on the device; v4: dcm_set_replay_placement; v5: DCM_PARAM_WIDE_MEMBERS; still v5, additions only: dcm_generate_instances, dcm_get_instances, dcm_generator_draws, dcm_set_instance_renewal, dcm_instance_index, DCM_PARAM_RENEW_SIZES, dcm_set_rollout_log, dcm_set_best_log, dcm_reduce_best, dcm_fork_envs */
+#define DCM_ABI_VERSION 5 /* v3: dcm_build_id, dcm_set_visibility, dcm_load_instances validates req on the device; v4: dcm_set_replay_placement; v5: DCM_PARAM_WIDE_MEMBERS; still v5, additions only: dcm_generate_instances, dcm_get_instances, dcm_generator_draws, dcm_set_instance_renewal, dcm_instance_index, DCM_PARAM_RENEW_SIZES, dcm_set_rollout_log, dcm_set_best_log, dcm_reduce_best, dcm_fork_envs, dcm_rollout_lookahead */
 
 typedef struct dcm_env dcm_env; /* opaque */
 
@@ -406,6 +406,38 @@ int dcm_rollout_policy(dcm_env *env, int32_t policy, int32_t episodes, int64_t m
 int dcm_rollout_explore(dcm_env *env, int32_t policy, uint64_t explore_q32, int32_t episodes, int64_t max_decisions,
                         const int64_t *max_decisions_in, float *agents_out, float *tasks_out, uint8_t *mask_out,
                         int64_t *steps_out, void *stream);
+
+/* The same persistent launch with every decision chosen by ONE-STEP LOOKAHEAD over a base policy: the rollout algorithm, on the device.
+ * Every argument other than base_policy means what it means in dcm_rollout_policy; base_policy is any of DCM_POLICY_RANDOM,
+ * DCM_POLICY_FIRST, DCM_POLICY_NEAREST.
+ * The rule: an env in front of decision d, with leader and mask drawn as always, values every action a the mask allows by
+ *     v(a) = (finished tasks, reward)   -- entries 1 and 0 of the summary row
+ * of the episode in which decision d takes a -- with this leader and the followers of protocol slots 2+j of decision d -- and the
+ * base policy takes every later decision d+1, d+2, ... (same seed, running counter) until the episode ends.  Decision d then takes the
+ * action with the largest v: finished tasks first, then reward, a tie to the lowest index; the depot when no task is unmasked.  The
+ * choice protocol is a pure function of (seed, decision counter, slot), so the values are exact and the episode never ends below the
+ * base policy's from the same state.
+ * One wave owns one env and values its own actions one after the other between two snapshots of the env; masked actions cost
+ * nothing, no second handle exists and nothing returns to the host.  The inner episodes leave NOTHING behind: the decision counter,
+ * the episode count, the flags, the summary row, the return log, the rollout log, the abandonment log and its overflow counts,
+ * steps_out and the observation buffers are what a launch leaves that only ever took the chosen actions.  steps_out, the decision
+ * budget and the decision counter count the chosen (outer) decisions only; agents_out / tasks_out / mask_out hold the outer
+ * decisions' rows; the rollout log (dcm_set_rollout_log, set or not) is appended by the outer decisions only and holds the plan.
+ * episodes, budgets and the stop at a decision point, the restart between episodes, dcm_set_instance_renewal on a uniform generated
+ * batch, ragged batches and DCM_PARAM_WIDE_MEMBERS handles work as in dcm_rollout_policy.  An inner episode that ends under the
+ * zero-decider guard or at max_time is valued by (finished tasks, -now) like any other -- its summary row's entries.
+ * The snapshots live in a device buffer the handle owns: per env its share of the dcm_clone_state blob (record + 64 B + 32 n_agents
+ * + the overflow count table).  It is allocated by the FIRST call on a handle, not by dcm_create, so the first call cannot be
+ * captured into a HIP graph (DCM_ERR_STATE under stream capture); later calls can.  Cost: about (unmasked actions) x (decisions
+ * left in the episode) base-policy decisions per outer decision, serial in one wave: a 20A/50T launch takes some hundred milliseconds
+ * whatever the batch size up to a full machine (DESIGN.md 6 has the measured times against the host-driven fan-out).
+ * Refusals, before anything is launched or changed, every message names dcm_rollout_lookahead.  DCM_ERR_INVALID: a base policy
+ * outside the three; episodes < 1; a handle with max_waiting_time <= 0 -- also with a decision budget, which bounds the outer
+ * decisions only while every inner episode must end by itself.  DCM_ERR_STATE: no dcm_reset yet; the best log set (there is no
+ * best-keeping lookahead form); a launch that would renew a ragged batch's SIZES. */
+int dcm_rollout_lookahead(dcm_env *env, int32_t base_policy, int32_t episodes, int64_t max_decisions,
+                          const int64_t *max_decisions_in, float *agents_out, float *tasks_out, uint8_t *mask_out,
+                          int64_t *steps_out, void *stream);
 
 /* Terminal results of the last finished episode (worker.py:87,103-108):
  * out[B,8] f64 = reward(-makespan), n_finished_tasks, success_rate, makespan, time_cost,

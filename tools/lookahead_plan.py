@@ -3,7 +3,7 @@
 and take the best -- for N instances in one handle.
 
     python tools/lookahead_plan.py [--agents 20 --tasks 50 --instance-seed 7000 | --golden I] [--instances 4] [--seed 11] [--cap 64]
-                                   [--out plan.yaml]
+                                   [--out plan.yaml] [--device]
 
 Instance n -- generate_instance(agents, tasks, instance_seed + n), or the (I + n)-th of tests/golden/instances_20A50T.npz -- is env n
 of one handle of N envs, all with the seed env_seed(seed, 0), as in tools/sample_plan.py.  Lookahead.plan() forks the N envs into
@@ -13,7 +13,12 @@ handle's route log holds the plan.  The choice protocol makes this exact: a plan
 Prints one JSON line: each instance's (finished, reward) under `nearest` and under the lookahead plan, the number of lookahead
 launches (one fork + one step + one persistent launch of N (T + 1) envs each) and the decisions those launches played -- what to
 give the sampler of tools/sample_plan.py for a comparison at equal decisions spent -- and writes each plan as the file
-Worker.generate_route writes (--out with one instance, plan_<n>.yaml next to it otherwise).  Needs a HIP device."""
+Worker.generate_route writes (--out with one instance, plan_<n>.yaml next to it otherwise).  Needs a HIP device.
+--device (bare, no value): the same plans from ONE persistent launch, rollout("nearest", lookahead=True) (dcm_rollout_lookahead): every
+env's wave values its own actions one after the other and takes the best, nothing returns to the host, and the plan is read from the
+rollout log.  Same rewards, same plan files; the JSON line then has lookahead_launches = 1, branches = 0 and decisions = the decisions
+of the plan itself (the inner episodes' are not counted on the device).  `--device cuda:N` with a value keeps its old meaning, the GPU
+of the host-driven run; --torch-device names the GPU for either."""
 import argparse
 import json
 import os
@@ -41,10 +46,14 @@ def main():
     ap.add_argument("--seed", type=int, default=11, help="base of the env seed env_seed(seed, 0)")
     ap.add_argument("--cap", type=int, default=64, help="entries per agent of the route log")
     ap.add_argument("--out", default="plan.yaml", help="the plan file; with --instances N > 1, plan_<n>.yaml in its directory")
-    ap.add_argument("--device", default="cuda:0")
+    ap.add_argument("--device", nargs="?", default=None, const=True,
+                    help="bare: plan with one persistent launch (the device form); with a value: the GPU, as --torch-device")
+    ap.add_argument("--torch-device", default="cuda:0")
     args = ap.parse_args()
     if args.instances < 1:
         ap.error("--instances must be >= 1")
+    on_device = args.device is True
+    args.device = args.torch_device if args.device in (None, True) else args.device
     N = args.instances
     if args.golden is not None:
         z = np.load(os.path.join(ROOT, "tests", "golden", "instances_20A50T.npz"))
@@ -66,12 +75,21 @@ def main():
     nearest = [pair(row) for row in greedy.summary().cpu().numpy()]
 
     env = BatchedTaskEnv(N, A, T, device=args.device).load_instances(*batch)
-    env.enable_route_log(args.cap)
-    env.reset(seeds, observe=False)
-    la = Lookahead(env, "nearest")
-    launches = la.plan()
+    if on_device:
+        env.enable_rollout_log(args.cap)
+        env.reset(seeds, observe=False)
+        launches, branches = 1, 0
+        decisions = int(env.rollout("nearest", episodes=1, write_obs=False, lookahead=True).sum())
+        routes_of = env.rollout_routes
+    else:
+        env.enable_route_log(args.cap)
+        env.reset(seeds, observe=False)
+        la = Lookahead(env, "nearest")
+        launches, branches = la.plan(), N * (T + 1)
+        decisions = int(la.decisions)
+        routes_of = env.routes
     plan = [pair(row) for row in env.summary().cpu().numpy()]
-    task, arrival, length = (x.cpu().numpy() for x in env.routes())
+    task, arrival, length = (x.cpu().numpy() for x in routes_of())
     outs = [args.out] if N == 1 else [os.path.join(os.path.dirname(args.out), "plan_%d.yaml" % n) for n in range(N)]
     for n, path in enumerate(outs):
         with open(path, "w") as f:                                              # route_lists: ValueError if a route is longer than --cap
@@ -79,7 +97,7 @@ def main():
             yaml.dump({a: r for a, r in enumerate(routes)}, f, sort_keys=False)  # worker.py:246-248
     one = lambda xs: xs[0] if N == 1 else xs
     print(json.dumps(dict(instance=one(sources), instances=N, nearest=one(nearest), lookahead=one(plan), lookahead_launches=launches,
-                          branches=N * (T + 1), decisions=int(la.decisions), improved=sum((p["finished"], p["reward"]) > (g["finished"], g["reward"])
+                          branches=branches, decisions=decisions, improved=sum((p["finished"], p["reward"]) > (g["finished"], g["reward"])
                                                                                   for p, g in zip(plan, nearest)), out=one(outs))))
 
 
