@@ -144,6 +144,29 @@ def rollout_kernel_name(A, T):
     return "k_rollout_random"
 
 
+SIM_KINDS = ("<20,50,false>", "<20,50,true>", "<64,64,true>", "<50,200,false>", "<100,500,false>", "<128,256,true>", "<0,0,false>",
+             "<0,0,false,MW>")
+
+
+def sim_kind_name(A, T, ragged=False, wide=False):
+    """The Sim<CA, CT, RS[, MC]> template arguments the general kernels (k_rollout_random and its forms, k_step) are instantiated
+    with for a handle of these batch dims: one of SIM_KINDS, in the order of enum plan::SimKind.  Mirrors plan::sim_kind of
+    csrc/plan.hpp (tests/test_host.py compares the two)."""
+    if wide:
+        return SIM_KINDS[7]
+    if A <= 20 and T <= 50:
+        return SIM_KINDS[0] if (not ragged and (A, T) == (20, 50)) else SIM_KINDS[1]
+    if A <= 64 and T <= 64:
+        return SIM_KINDS[2]
+    if not ragged and (A, T) == (50, 200):
+        return SIM_KINDS[3]
+    if not ragged and (A, T) == (100, 500):
+        return SIM_KINDS[4]
+    if A <= 128 and T <= 256:
+        return SIM_KINDS[5]
+    return SIM_KINDS[6]
+
+
 def replay_kernel_name(A, T, member_cap, reactive, vis_cap):
     """Which kernel dcm_execute_routes launches (default placement): the register-resident one when the agents, the LIVE tasks (all
     of them without dynamic arrivals, tasks 1..cap with them) and the member slots fit it, the general one otherwise.  Mirrors

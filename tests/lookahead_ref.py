@@ -67,7 +67,8 @@ def walk(a, t, inst_one, seed, action_of, mwt=10.0, switch=None, stop=None):
     switch = (d_s, seed_2): decisions d >= d_s draw leader, action and followers from seed_2 -- a copy of the env made in front of
     decision d_s and given that seed.  stop: walk only the first `stop` decisions.
     Returns dict(leader, action, nfol, followers[n, a], mask: the mask in front of every decision taken, n_steps, ended,
-    seed_of) -- the choices in the form OracleEnv.rollout injects."""
+    seed_of) -- the choices in the form OracleEnv.rollout injects -- and o, the OracleEnv where the walk left it (a walk that `stop`
+    cut: in front of decision `stop`)."""
     import oracle
     from dcmrta_amd.choice import below, draw
     seed_of = (lambda d: seed) if switch is None else (lambda d: switch[1] if d >= switch[0] else seed)
@@ -119,7 +120,7 @@ def walk(a, t, inst_one, seed, action_of, mwt=10.0, switch=None, stop=None):
     n = len(actions)
     return dict(leader=np.array(leaders, np.int32), action=np.array(actions, np.int32), nfol=np.array(nfols, np.int32),
                 followers=np.array(fols, np.int16).reshape(n, a), mask=np.array(masks, np.uint8).reshape(n, t + 1),
-                n_steps=n, ended=not cut, seed_of=seed_of)
+                n_steps=n, ended=not cut, seed_of=seed_of, o=o)
 
 
 def result(a, t, inst_one, w, mwt=10.0):

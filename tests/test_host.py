@@ -346,6 +346,16 @@ int p_replay(int A, int T, int member_cap, int reactive, int vis_cap, int placem
         for T in range(1, 1024):
             assert ROLLOUT[P.p_rollout(A, T, 0, 0, 1, 1)] == rollout_kernel_name(A, T), (A, T)
             assert ("k_step_fast" if P.p_step(A, T, 0, 0, 1) else "k_step") == step_kernel_name(A, T), (A, T)
+    # the instantiation of the general kernels, ragged and wide handles too
+    from dcmrta_amd.roofline import SIM_KINDS, sim_kind_name
+    assert SIM_KINDS == SIM
+    for A in range(1, 129):
+        for T in range(1, 1024, 1 if A in (20, 50, 64, 65, 100, 128) else 7):
+            for ragged, wide in ((0, 0), (1, 0), (0, 1), (1, 1)):
+                assert SIM[P.p_sim(A, T, ragged, wide, 1)] == sim_kind_name(A, T, bool(ragged), bool(wide)), (A, T, ragged, wide)
+    for T in (50, 51, 64, 65, 200, 256, 257, 500):
+        for A in (20, 21, 50, 64, 65, 100, 128):
+            assert SIM[P.p_sim(A, T, 0, 0, 1)] == sim_kind_name(A, T) and SIM[P.p_sim(A, T, 1, 0, 1)] == sim_kind_name(A, T, ragged=True), (A, T)
     # ... and every replay of the default placement whose fast-kernel LDS need is within its limit
     for A in (1, 20, 64, 100, 128):
         for T in (1, 50, 128, 129, 500, 1023):
