@@ -375,6 +375,22 @@ __device__ __forceinline__ bool lane_of(uint64_t m) {
     return false;
 #endif
 }
+// Wave-uniform conditions.  THE MIRROR RULE: a wave-uniform condition lives on the scalar unit as a condition code or a 32-bit word,
+// never as a lane mask.  The compiler keeps every bool that crosses a basic block as a 64-bit lane mask (s_cselect_b64 s[..], -1, 0)
+// and re-forms the condition at each use (s_and_b64 / s_andn2_b64 vcc, exec, s[..] + s_cbranch_vccnz) where s_cmp + s_cbranch_scc
+// would do; a bool turned into a number (`c ? 1 : 0` of such a bool) even goes through the vector unit (v_cndmask_b32 +
+// v_readfirstlane_b32).  So, in Fast<> and the loop of k_rollout_fast.inc:
+//   * a mask is tested where it is used: `m != 0` is s_cmp_lg_u64.  A condition that several blocks need is carried as the MASK or
+//     NUMBER it is a test of (Fast::unsettled, `more`, `turn`), not as the bool;
+//   * a flag that crosses a basic block is an int in an SGPR, and every test of it takes an opaque copy, asm("" : "+s"(c)), or uni():
+//     the compiler merges equal compares of one value into ONE bool and carries that.  The copy is made in a block all lanes reach and
+//     from a value the compiler holds in SGPRs -- of a value it has in a VGPR (a bool made a number, a PHI behind a lane loop) the copy
+//     does not compile ("illegal VGPR to SGPR copy"), which is the check that the value is where it should be;
+//   * a select between uniform values is s_cselect_b32 / s_cselect_b64 on that condition, in the block that forms it; 0/1 arithmetic is
+//     written on numbers with unsigned wrap-around ((0u - x) >> 31), which the compiler cannot turn back into a compare;
+//   * a constant mask that is ANDed more than once is an SGPR pair (an opaque copy once per kernel): as a folded literal each AND is an
+//     s_and_b32 of one half and a copy of the other.
+// tests/test_uniform_flags_host.py reads the decision loops for the lane-mask form.
 // value of a per-chunk register array at the wave-uniform position (chunk, lane): every chunk's lane is read, scalar selects pick
 // (branches around two v_readlane cost more than the reads)
 __device__ __forceinline__ uint32_t sel(bool c, uint32_t a, uint32_t b) { return c ? a : b; }

@@ -78,7 +78,17 @@ __global__ __launch_bounds__(WAVE, 4) void KNAME(int A, int T, int PA, int PT, K
     FPH_START(f);
     PH_DECL;
     int ep = 0;
-    bool need_adv = false;       // the general event code has to run on the (flushed) LDS image before the next decision
+    // the general event code has to run on the (flushed) LDS image before the next decision: a 0/1 word, pinned where the episode loop
+    // tests it behind the decision loop -- as a bool it is a lane mask that the decision loop copies and inverts at its latch in every
+    // trip.  (The epsilon-greedy and best-keeping forms keep the bool and the loop's three exits: with the word or with the one exit
+    // they spill more SGPRs outside the loop, 113 VGPRs for 111.)
+#ifdef KEXPLORES
+    bool need_adv = 0;
+#define NEED_ADV_PIN
+#else
+    int need_adv = 0;
+#define NEED_ADV_PIN asm("" : "+s"(need_adv))
+#endif
     // Wave priority = longest remaining work first (s_setprio).  A launch that fills the machine by itself ends with its slowest env
     // (430 of a mean 360 decisions at 20A/50T x 3 episodes) while the SIMDs it shares with envs that finished early idle; the waves
     // with the most tasks still to serve -- episodes to come x T + the unmasked tasks of the last decision, in sixths of the launch's
@@ -102,7 +112,7 @@ __global__ __launch_bounds__(WAVE, 4) void KNAME(int A, int T, int PA, int PT, K
     };
     if constexpr (use_prio) __builtin_amdgcn_s_setprio(3);
     for (;;) {
-        if (!need_adv) {         // head of an episode slot (the `for ep` of k_rollout_random)
+        if (need_adv == 0) {     // head of an episode slot (the `for ep` of k_rollout_random)
             if (ep >= episodes) break;
             if (h.flags & DCM_FLAG_DONE) {   // restart from the loaded instance; d keeps running
                 if (h.flags & ROLLOUT_ERR) break;
@@ -131,10 +141,10 @@ __global__ __launch_bounds__(WAVE, 4) void KNAME(int A, int T, int PA, int PT, K
 #if defined(DCM_LOG) || defined(KEXPLORES)
                 fl.len = 0;                                                       // the log is the new episode's
 #endif
-                need_adv = true;
+                need_adv = 1;
             }
         }
-        if (need_adv) {
+        if (need_adv != 0) {
             CNT(15);
 #if defined(KEXPLORES) || defined(DCM_POLICY)
             // The best-keeping form reads the row of every finished episode (keep_best).  The epsilon-greedy and greedy forms keep
@@ -158,7 +168,7 @@ __global__ __launch_bounds__(WAVE, 4) void KNAME(int A, int T, int PA, int PT, K
                 h.flags &= ~SimT::FLAG_DEFERRED;                                  // internal: never stored, never seen by the loop
             }
 #endif
-            need_adv = false;
+            need_adv = 0;
             // wave-uniform by construction; tell the compiler so (scalar branches in the fast loop)
             h.now = uni(h.now); h.flags = uni(h.flags); h.cur_group = uni(h.cur_group); h.n_groups = uni(h.n_groups);
             h.empty_passes = uni(h.empty_passes);
@@ -182,7 +192,18 @@ __global__ __launch_bounds__(WAVE, 4) void KNAME(int A, int T, int PA, int PT, K
 #else
                 const int rlen = f.decide(r, h, P, lane, k1, agrow, tkrow, mkp, &k2, use_prio ? &nv_last : nullptr);
 #endif
+#ifdef KEXPLORES
                 if (h.flags & DCM_FLAG_DONE) break;
+#else
+                // ONE exit, at the foot, on `more` (the decisions left; 0 also for a finished episode and for an event that needs the
+                // general code): with several exits the compiler gives the loop a lane mask per exit and merges them at the latch
+                int more = 0;
+                // (the flag bit as a number behind an opaque copy: `flags & 1` alone is a truncation to a bool, which the compiler
+                //  branches on through a lane mask and vcc)
+                uint32_t done = h.flags & DCM_FLAG_DONE;
+                asm("" : "+s"(done));
+                if (done == 0u) {
+#endif
                 gd += GAMMA;
 #ifdef KEXPLORES
                 if (++ki == WAVE) { kv = mix64(gd + GAMMA * (uint64_t)lane); kv2 = mix64(kv + GAMMA); xv = (uint32_t)(mix64(kv ^ EXPLORE_SALT) >> 32); ki = 0; }
@@ -193,19 +214,36 @@ __global__ __launch_bounds__(WAVE, 4) void KNAME(int A, int T, int PA, int PT, K
                 // worker.py:53 else same group, next leader.  The next-group step is an add, not a branch: as an arm of an
                 // if / else-if beside next_event() it shared a latch block with the event, whose task_update / agent_update results
                 // were then computed in shadow registers and copied back (11 v_mov behind every event, 8 of them 64-bit).
-                const bool more_groups = h.cur_group < h.n_groups;
+                // The latch's conditions are numbers on the scalar unit (common.hpp, the rule of the uniform conditions): `room`, the
+                // groups still to come, and `turn` = room once the group is through, else 1 -- the next group if turn > 0 with the
+                // group through, the next event if turn <= 0.  As bools (`rlen == 0`, `more_groups` and their three combinations) each
+                // was a lane mask: 3 s_cselect_b64, 2 s_and / s_or_b64, a vcc formation and a vcc branch.
+                const int room = h.n_groups - h.cur_group;
 #ifdef DCM_COUNT_PATHS
-                if (rlen == 0) { CNT(8); if (more_groups) CNT(9); }
+                if (rlen == 0) { CNT(8); if (room > 0) CNT(9); }
 #endif
-                h.cur_group += (rlen == 0 && more_groups) ? 1 : 0;                // worker.py:52 next group
-                if (rlen == 0 && !more_groups) {
-                    if (!f.next_event(r, h, P, lane)) { need_adv = true; break; }   // worker.py:85 -> :45
+                int turn = rlen == 0 ? room : 1, ahead = rlen == 0 ? room : 0;
+                asm("" : "+s"(turn), "+s"(ahead));
+                h.cur_group += (int)((0u - (uint32_t)ahead) >> 31);                 // worker.py:52 next group (1 iff ahead > 0: the sign of -ahead)
+#ifdef KEXPLORES
+                if (turn <= 0) {
+                    if (!f.next_event(r, h, P, lane)) { need_adv = 1; break; }      // worker.py:85 -> :45
                 }
                 if (left == 0) break;
+#else
+                more = left;
+                if (turn <= 0) {
+                    if (!f.next_event(r, h, P, lane)) { need_adv = 1; more = 0; }   // worker.py:85 -> :45
+                }
+                }
+                asm("" : "+s"(more));
+                if (more == 0) break;
+#endif
             }
             f.flush(r);
             FPHK(f, 12);
-            if (need_adv) continue;
+            NEED_ADV_PIN;
+            if (need_adv != 0) continue;
         }
 #ifdef DCM_BEST
         // a finished episode, its restart (fl.len = 0) still to come: keep it if it beats the kept one.  Also reached by an episode
@@ -239,4 +277,5 @@ __global__ __launch_bounds__(WAVE, 4) void KNAME(int A, int T, int PA, int PT, K
     WSYNC();
     S.store_record(rec, lane);
 }
+#undef NEED_ADV_PIN
 #include "k_form_end.inc"

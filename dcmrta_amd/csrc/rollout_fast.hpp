@@ -60,7 +60,8 @@ struct Fast {
     mutable uint64_t dt_join = 0, dt_times = 0;        // TRK only: the tasks whose ids / arrival rows (a join) and time_start / time_finish
                                                        // (became feasible) the fast path has changed: the write-back sends their 64-byte
                                                        // pieces of those sections instead of the sections
-    mutable bool calm = false;                         // the last task_update call left every task at a fixed point for its `now`
+    mutable uint64_t unsettled = ~0ull;                // 0: the last task_update call left every task at a fixed point for its `now` ("calm");
+                                                       // a mask tested where it is used, not a bool (common.hpp, the rule of the uniform conditions)
     FPH_MEMBERS;
     uint64_t am, tm;                                   // lanes that own an agent / a task (wave-uniform masks)
     // per-lane constants
@@ -81,6 +82,9 @@ struct Fast {
         const int A_ = S.A(), T_ = S.T();
         am = A_ >= 64 ? ~0ull : ((1ull << A_) - 1ull);
         tm = (1ull << T_) - 1ull;
+        // (a constant mask that is ANDed more than once is an SGPR pair: folded as a literal, `ballot & tm` is s_and_b32 of the high
+        //  half and a copy of the low one)
+        asm("" : "+s"(tm));
         inA = lane < A_; inT = lane < T_; isD = lane == DL;
         la = inA ? lane : 0; lt = inT ? lane : 0;
     }
@@ -103,7 +107,7 @@ struct Fast {
         r.ab = S.ablog() + la * AB_CAP;
     }
     __device__ __forceinline__ void reload(R& r) const {
-        calm = false;                                  // nothing is known about the general code's last call
+        unsettled = ~0ull;                             // nothing is known about the general code's last call
         r.ax = S.ax()[la]; r.ay = S.ay()[la]; r.arr = S.arr()[la]; r.nd = S.nd()[la]; r.td = S.tdist()[la];
         r.cur = S.cur()[la]; r.ai = S.ainfo()[la];
         const int K = r.cur < 0 ? 0 : r.cur;
@@ -267,17 +271,18 @@ struct Fast {
         info = feas0 ? info_f : info_i;
         r.ti = info;
         if (inT) S.tinfo()[lt] = info;
-        bool over_already = false;
+        uint64_t over_already = 0ull;                                            // the tasks that became feasible and are over at `now`
         if (bec) {
             r.ts = nts; r.tf = ntf;
             if (inT) { S.ts()[lt] = nts; S.tf()[lt] = ntf; }
             if constexpr (TRK) { dirty |= SimT::DIRTY_TIMES; dt_times |= bec; }
-            over_already = (bec & __ballot(now >= ntf)) != 0ull;
+            over_already = bec & __ballot(now >= ntf);
         }
         const bool all_feasible = (__ballot((info & T_FEAS) == 0u) & tm) == 0ull;
         // (see Sim::task_update: a call can only change a task again at the same `now` if this one removed members or made a task
         //  feasible that is already over)
-        calm = dmask == 0ull && !over_already;
+        // (one test of one mask, selected into a 0/1 word where it is formed: a bool here is a lane mask from call to call)
+        unsettled = dmask | over_already;
         WSYNC();
         if (all_feasible) {                                                      // depot :277-280
             CNT(16);
@@ -340,6 +345,21 @@ struct Fast {
         if (glen == 0) return -1;
         return nth(gm, below((uint32_t)(k1 >> 32), glen));
     }
+    // The same for the decisions of the persistent kernels, which have no exit in their middle (see decide): an empty group flags the
+    // env DCM_FLAG_BAD_LEADER | DCM_FLAG_DONE and goes on with leader 0 and group mask 1.  The group's length is a number on the
+    // scalar unit and the fix-up is arithmetic on it (common.hpp, the rule of the uniform conditions) -- `bad` is all ones iff the
+    // length is 0, its low bit is the mask's bit 0 and the length 1 (nth(1, 0) = 0 is the leader by itself), its flag bits the flags:
+    // no compare, no select, no lane mask.  (The opaque copy keeps the compiler from turning `bad` back into `glen == 0`, which it
+    // holds as a lane mask across the observation to the place where the flags are merged.)
+    __device__ __forceinline__ int pick_leader_flagged(const R& r, HdrRegs& h, uint64_t k1, uint64_t& gm) const {
+        const uint64_t g = __ballot((int)((r.ai >> 8) & 0xFFu) == h.cur_group) & am;
+        int glen = __popcll(g);
+        asm("" : "+s"(glen));
+        const uint32_t bad = (uint32_t)((glen - 1) >> 31);
+        gm = g | (uint64_t)(bad & 1u);
+        h.flags |= bad & (uint32_t)(DCM_FLAG_BAD_LEADER | DCM_FLAG_DONE);
+        return nth(gm, below((uint32_t)(k1 >> 32), glen + (int)(bad & 1u)));
+    }
     // k2p: the decision's second key mix64(k1 + GAMMA) (the first two follower draws) if the caller has it, else nullptr
     // nvp: receives the number of unmasked tasks the decision saw (the launch's wave-priority estimate of the work left)
     __device__ __forceinline__ int decide(R& r, HdrRegs& h, const KP& P, int lane, uint64_t k1, float* agrow, float* tkrow, uint8_t* mkp,
@@ -348,15 +368,18 @@ struct Fast {
         // (no early return: an exit from the middle of a decision would keep the whole register set of the agent / task state alive
         //  in a second copy -- 15 v_mov per decision at the loop latch.  An empty group is unreachable; if it ever happened the env
         //  is flagged and stops at the loop's ordinary exit test, its state no longer meaningful.)
-        int leader = pick_leader(r, h, k1, gm);
-        if (leader < 0) { h.flags |= DCM_FLAG_BAD_LEADER | DCM_FLAG_DONE; leader = 0; gm = 1ull; }
+        const int leader = pick_leader_flagged(r, h, k1, gm);
         FPH(0);
         const uint64_t bm = observe(r, h.now, leader, agrow, tkrow, mkp);
         FPH(1);
         // uniform-random valid action (protocol slot 1)
-        const int nv = __popcll(bm);
+        int nv = __popcll(bm);
+        asm("" : "+s"(nv));                                                      // (tested as a number: not as observe()'s `bm == 0`, kept as a lane mask)
         if (nvp) *nvp = nv;
-        const int action = nv ? nth(bm, below((uint32_t)k1, nv)) + 1 : 0;
+        // (the draw is made whether or not there is a task to draw -- nth() of an empty mask is harmless -- and the depot selected behind
+        //  it: as `nv ? draw : 0` the draw sits in a branch of its own, whose condition waits as a lane mask across the task rows' stores)
+        const int drawn = nth(bm, below((uint32_t)k1, nv)) + 1;
+        const int action = nv ? drawn : 0;
         FPH(2);
         return apply(r, h, P, lane, k1, gm, leader, action, k2p);
     }
@@ -368,8 +391,7 @@ struct Fast {
     __device__ __forceinline__ int decide_policy(R& r, HdrRegs& h, const KP& P, int lane, uint64_t k1, float* agrow, float* tkrow, uint8_t* mkp,
                                                  const uint64_t* k2p, int policy) const {
         uint64_t gm;
-        int leader = pick_leader(r, h, k1, gm);
-        if (leader < 0) { h.flags |= DCM_FLAG_BAD_LEADER | DCM_FLAG_DONE; leader = 0; gm = 1ull; }
+        const int leader = pick_leader_flagged(r, h, k1, gm);
         FPH(0);
         const uint64_t bm = observe(r, h.now, leader, agrow, tkrow, mkp);
         FPH(1);
@@ -391,26 +413,28 @@ struct Fast {
     __device__ __forceinline__ int decide_logged(R& r, HdrRegs& h, const KP& P, int lane, uint64_t k1, float* agrow, float* tkrow, uint8_t* mkp,
                                                  const uint64_t* k2p, int policy, FastLog& lg) const {
         uint64_t gm;
-        int leader = pick_leader(r, h, k1, gm);
-        if (leader < 0) { h.flags |= DCM_FLAG_BAD_LEADER | DCM_FLAG_DONE; leader = 0; gm = 1ull; }
+        const int leader = pick_leader_flagged(r, h, k1, gm);
         FPH(0);
         const uint64_t bm = observe(r, h.now, leader, agrow, tkrow, mkp);
         FPH(1);
-        int action;
-        if (policy == DCM_POLICY_RANDOM) {
-            const int nv = __popcll(bm);
-            action = nv ? nth(bm, below((uint32_t)k1, nv)) + 1 : 0;
-        } else {
-            uint64_t pick = bm;
-            if (policy == DCM_POLICY_NEAREST) {
-                const double lx = rl(r.ax, leader), ly = rl(r.ay, leader);
-                const double dd = dist2(lx, ly, r.tx, r.ty);
-                const bool open = lane_of(bm);
-                const double m = wave_nanmin_n<CT>(open ? dd : __builtin_nan(""));
-                pick = bm & __ballot(dd == m);
-            }
-            action = __ffsll((unsigned long long)pick);
+        // Both candidates are made -- the greedy pick behind its one wave-uniform branch (NEAREST), the random draw unconditionally as in
+        // decide() -- and one scalar select on `policy` takes the action: as if / else arms the policy tests meet again as lane masks
+        // where the arms join.
+        int nv = __popcll(bm);
+        asm("" : "+s"(nv));
+        const int drawn = nth(bm, below((uint32_t)k1, nv)) + 1;
+        uint64_t pick = bm;
+        if (policy == DCM_POLICY_NEAREST) {
+            const double lx = rl(r.ax, leader), ly = rl(r.ay, leader);
+            const double dd = dist2(lx, ly, r.tx, r.ty);
+            const bool open = lane_of(bm);
+            const double m = wave_nanmin_n<CT>(open ? dd : __builtin_nan(""));
+            pick = bm & __ballot(dd == m);
         }
+        const int greedy = __ffsll((unsigned long long)pick);
+        int pol = policy;
+        asm("" : "+s"(pol));
+        const int action = pol == DCM_POLICY_RANDOM ? (nv ? drawn : 0) : greedy;
         FPH(2);
         return apply<true>(r, h, P, lane, k1, gm, leader, action, k2p, &lg);
     }
@@ -432,9 +456,12 @@ struct Fast {
         asm("" : "+s"(task));
         int act_ = action;                                                       // (an opaque copy for the `action != 0` tests)
         asm("" : "+s"(act_));
-        const bool go = act_ != 0;                                               // a task, not the depot
-        const int tl = go ? task : DL;                                           // lane that owns the target
-        if (!go) {                                                               // vacancy = len(group) :327 (Q9)
+        // a task, not the depot?  A number on the scalar unit, compared where it is used: every test takes a fresh opaque copy, or the
+        // compiler forms `act_ != 0` once and carries it from block to block as a lane mask (common.hpp, the rule of the uniform conditions)
+        auto go = [&]() __attribute__((always_inline)) { int c = act_; asm("" : "+s"(c)); return c != 0; };
+        static_assert(DL == 63, "task & DL");
+        const int tl = task & DL;                                                // lane that owns the target: the task's, or (-1 & 63) the depot's
+        if (!go()) {                                                               // vacancy = len(group) :327 (Q9)
             CNT(2);
             mm |= rest; nm += rlen; rlen = 0;
         } else if (rlen != 0) {
@@ -472,7 +499,7 @@ struct Fast {
         const bool mem = lane_of(mm);
         uint64_t ids = 0ull; uint32_t kinfo = 0; int n = 0;
         int slot = 0;
-        if (go) {
+        if (go()) {
             // :321-322 members.append unless already listed (Q4: a re-joining agent keeps its slot, its arrival is overwritten)
             kinfo = (uint32_t)__builtin_amdgcn_readlane((int)r.ti, tl);
             ids = rl(r.ids, tl);
@@ -505,7 +532,7 @@ struct Fast {
             r.arr = arrv;
             r.ax = tx_; r.ay = ty_;                                              // :320
             r.cur = task;                                                        // :314
-            r.ai = (r.ai & ~(A_GRP | A_MEMBER)) | (go ? A_MEMBER : A_INDEPOT);
+            r.ai = (r.ai & ~(A_GRP | A_MEMBER)) | (go() ? A_MEMBER : A_INDEPOT);
             if constexpr (LOG) {
                 // route.append / arrival_time += (:314,:318): one 16-bit and one 64-bit store behind the env's wave-uniform bases, at
                 // the lane's 32-bit entry index; the length never leaves the lane's register
@@ -519,23 +546,25 @@ struct Fast {
         }
         // (the members' arrival slots, under a mask of its own: as a uniform `if (go)` inside the members' block the compiler inverts
         //  the condition through a 0/1 VGPR)
-        if (lane_of(go ? mm : 0ull)) S.marr()[slot * CT + tl] = arrv;
+        if (lane_of(go() ? mm : 0ull)) S.marr()[slot * CT + tl] = arrv;
         // A QUIET join: the task still lacks members after it (status = requirement - len(members) > 0) and the previous
         // task_update call -- at this same `now` -- left every task at a fixed point.  task_update (:245-281) then changes
         // nothing but this task's status: not enough members -> not feasible (:254); the joining members have not waited
         // (arrival >= now, :269); everybody else was evaluated at this `now` by the previous call.  The pass over the tasks is
         // skipped and the task's lane takes the new status itself.
         const int status_k = (int)(kinfo & 0xFFu) - n;
-        const bool quiet = go && calm && status_k > 0;
-        if (go && lane == tl) {
+        // (the depot has status_k = 0; the target's lane is `task`, which is -1, no lane, for the depot: neither needs `go`)
+        const uint64_t loud = status_k > 0 ? unsettled : ~0ull;                  // 0: quiet
+        auto quiet = [&]() __attribute__((always_inline)) { uint64_t c = loud; asm("" : "+s"(c)); return c == 0ull; };
+        if (lane == task) {
             r.ids = ids; r.lm |= mm;
-            r.ti = quiet ? ((kinfo & (T_FEAS | T_FIN | 0xFFu)) | ((uint32_t)(status_k & 0xFF) << 8) | ((uint32_t)n << 16))
+            r.ti = quiet() ? ((kinfo & (T_FEAS | T_FIN | 0xFFu)) | ((uint32_t)(status_k & 0xFF) << 8) | ((uint32_t)n << 16))
                          : ((kinfo & ~0x00FF0000u) | ((uint32_t)n << 16));
-            if (quiet) S.tinfo()[lt] = r.ti;                                     // (written through like task_update does)
+            if (quiet()) S.tinfo()[lt] = r.ti;                                     // (written through like task_update does)
         }
         WSYNC();
         FPH(5);
-        if (!quiet) { CNT(5); task_update(r, now, P.mwt, lane); } else CNT(4);         // worker.py:74
+        if (!quiet()) { CNT(5); task_update(r, now, P.mwt, lane); } else CNT(4);         // worker.py:74
         FPH(6);
         agent_update(r, now, P.mwt);                                                 // worker.py:76
         FPH(7);
@@ -557,13 +586,14 @@ struct Fast {
         const bool dec = (ndv == tmin);                                          // :288 exact ==
         const uint64_t dm = __ballot(dec);
         const int first = __ffsll((unsigned long long)dm) - 1;
-        bool same = true;
+        uint64_t apart = 0ull;                                                   // the deciders that are not on the first one's point
         if (dm & (dm - 1ull)) {                                                  // more than one decider: all on one point?
             CNT(12);
             const double x0 = rl(r.ax, first), y0 = rl(r.ay, first);
-            same = (dm & (__ballot(r.ax != x0) | __ballot(r.ay != y0))) == 0ull;   // (!= is true on NaN, like !(a == x && b == y))
+            apart = dm & (__ballot(r.ax != x0) | __ballot(r.ay != y0));          // (!= is true on NaN, like !(a == x && b == y))
         }
-        if (same) {
+        asm("" : "+s"(apart));                                                   // (ONE test of the mask, here: or the lone decider's path carries a lane mask to it)
+        if (apart == 0ull) {
             r.ai = (r.ai & ~A_GRP) | (dec ? (1u << 8) : 0u);
             h.n_groups = 1;
         } else {
