@@ -58,6 +58,8 @@ SIGNATURES = {
     "dcm_rollout_policy": (C.c_int, [_vp, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),   # env, policy, then as dcm_rollout_random
     "dcm_rollout_explore": (C.c_int, [_vp, _i32, C.c_uint64, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),   # env, base policy, explore_q32, then as dcm_rollout_random
     "dcm_rollout_lookahead": (C.c_int, [_vp, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),   # env, base policy, then as dcm_rollout_random
+    # env, base policy, width, then as dcm_rollout_random up to steps_out; inner_out, stream
+    "dcm_rollout_lookahead_width": (C.c_int, [_vp, _i32, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "dcm_summary": (C.c_int, [_vp] * 3),
     "dcm_env_status": (C.c_int, [_vp] * 5),
     "dcm_get_tasks": (C.c_int, [_vp] * 10),

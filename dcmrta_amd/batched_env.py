@@ -304,7 +304,8 @@ class BatchedTaskEnv:
 
     POLICIES = {"random": _lib.POLICY_RANDOM, "first": _lib.POLICY_FIRST, "nearest": _lib.POLICY_NEAREST}
 
-    def rollout(self, policy="random", episodes=1, write_obs=True, max_decisions=-1, *, explore=None, explore_q32=None, lookahead=False):
+    def rollout(self, policy="random", episodes=1, write_obs=True, max_decisions=-1, *, explore=None, explore_q32=None, lookahead=False,
+                width=0, return_inner=False):
         """`episodes` full episodes per env in one persistent launch under a device policy (dcm_rollout_policy): "random" (uniform
         over the unmasked tasks: the config-2 hot path), "first" (the lowest unmasked task) or "nearest" (the unmasked task closest
         to the deciding agent, ties to the lowest index).
@@ -321,11 +322,20 @@ class BatchedTaskEnv:
         and no host round trip.  episodes, max_decisions (outer decisions only), the rollout log, the return log, instance renewal
         and ragged batches work as in every other call; the handle needs max_waiting_time > 0 and no best log, and explore /
         explore_q32 cannot be combined with it.
-        Returns steps int64[B] (device tensor)."""
+        width (with lookahead=True; dcm_rollout_lookahead_width): a decision values only the `width` unmasked tasks nearest to the
+        leader -- "nearest"'s own order, ties to the lowest index, whatever the base policy -- instead of all of them; 0 (the default)
+        values all, 1 is "nearest" itself.  The best (finished tasks, reward) wins, a tie to the lowest action index.
+        return_inner=True (with lookahead=True): also return inner int64[B], the base-policy decisions each env took inside inner
+        episodes during this call -- what the launch cost beside its outer decisions.
+        Returns steps int64[B] (device tensor), or (steps, inner) with return_inner=True."""
         if policy not in self.POLICIES:
             raise DcmError("policy must be one of %s" % ", ".join(repr(p) for p in self.POLICIES))
         if lookahead and (explore is not None or explore_q32 is not None):
             raise DcmError("lookahead=True takes the base policy's own decisions inside its rollouts: it cannot be combined with explore / explore_q32")
+        if isinstance(width, (bool, np.bool_)) or not isinstance(width, (int, np.integer)) or width < 0:
+            raise DcmError("width must be an integer >= 0 (0: every unmasked action is valued)")
+        if not lookahead and (width != 0 or return_inner):
+            raise DcmError("width / return_inner belong to the lookahead form: give lookahead=True")
         q32 = None
         if explore is not None or explore_q32 is not None:
             if explore is not None and explore_q32 is not None:
@@ -349,8 +359,14 @@ class BatchedTaskEnv:
             if per_env.numel() != self.B:
                 raise DcmError("max_decisions must be an int or int64[B]")
             max_decisions = -1
+        inner = torch.empty((self.B,), dtype=torch.int64, device=self.device) if return_inner else None
         with torch.cuda.device(self.device):
-            if lookahead:
+            if lookahead and (width != 0 or return_inner):
+                check(self._lib.dcm_rollout_lookahead_width(self._h, self.POLICIES[policy], int(width), int(episodes), int(max_decisions),
+                                                            _ptr(per_env), *[_ptr(x) for x in o], _ptr(steps), _ptr(inner), self._stream()))
+                if return_inner:
+                    return steps, inner
+            elif lookahead:
                 check(self._lib.dcm_rollout_lookahead(self._h, self.POLICIES[policy], int(episodes), int(max_decisions), _ptr(per_env),
                                                       *[_ptr(x) for x in o], _ptr(steps), self._stream()))
             elif q32 is None:

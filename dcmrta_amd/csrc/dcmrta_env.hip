@@ -98,6 +98,8 @@ struct RolloutArgs {
     uint64_t explore_q32 = 0;          // the epsilon-greedy forms (k_ex_*, k_exrn_*): between `policy` and the log
     BestLog best{nullptr, nullptr, nullptr, nullptr, nullptr};   // the best-keeping form (k_bs_*): behind the epsilon-greedy forms' arguments
     unsigned char* snap = nullptr;     // the lookahead form (k_la_*, k_larn_*): the handle's snapshot buffer, behind `policy` and the log
+    int width = 0;                     // ... then the number of nearest actions a decision values (0: every unmasked one)
+    int64_t* inner_out = nullptr;      // ... and, per env, the decisions of the inner episodes (null: not wanted)
 };
 // k_rollout_fast_g<NAC, NTC, OBS> / k_rn_rollout_fast_g / k_rs_rollout_fast_g (rollout_fast_g.hpp, its own translation unit)
 void launch_rollout_fast_g(int nac, int ntc, bool obs, unsigned grid, Lay L, hipStream_t stream, const RolloutArgs& a);
@@ -109,8 +111,8 @@ void launch_rollout_fast_g(int nac, int ntc, bool obs, unsigned grid, Lay L, hip
 // Return 0, or -1 when `kind` has no one-chunk kernel (the caller asked plan::form_rollout_kind, so it has).
 // allow_lds_*: the form's share of dcm_create's dynamic-LDS limit (see there).
 using FormLauncher = int(plan::SimKind kind, bool fast, bool obs, unsigned grid, Lay L, hipStream_t stream, const RolloutArgs& a);
-// The lookahead form (k_la_* / k_larn_*) takes a.policy (any of the three), a.lg (set or not) and a.snap; it exists for the general
-// kernel text alone: `fast` and `obs` are ignored.
+// The lookahead form (k_la_* / k_larn_*) takes a.policy (any of the three), a.lg (set or not), a.snap, a.width and a.inner_out; it
+// exists for the general kernel text alone: `fast` and `obs` are ignored.
 FormLauncher launch_rollout_policy, launch_rollout_log, launch_rollout_explore, launch_rollout_best, launch_rollout_lookahead;
 void allow_lds_policy(int lds);
 void allow_lds_log(int lds);
@@ -1287,6 +1289,53 @@ struct Sim {
         }
     }
 
+    // NEAREST's next pick behind a cursor (the width-limited lookahead form's candidate list, rollout_lookahead.hpp): the unmasked task
+    // with the smallest (rounded fp64 distance from the leader, index) among those with d > pd || (d == pd && t > pt) -- what
+    // pick_policy_action(NEAREST) would return if every task up to the cursor, in that order, were masked.  (pd, pt) wave-uniform;
+    // (-1, -1) is in front of every task.  The same walk and reduction: lane l keeps its first minimum BEHIND THE CURSOR (a lane that
+    // owns two tasks at one distance moves on from the first to the second), the wave minimum of the distances, then the lowest
+    // index among the lanes that hold it.  Returns the task (wave-uniform, its distance in `dist`), or -1 when no unmasked task lies
+    // behind the cursor.  Instantiated by the lookahead form only.
+    __device__ __forceinline__ int next_nearest_task(int lane, int leader, double pd, int pt, const XY& xy, double& dist) const {
+        const int T_ = T();
+        const double lx = ax()[leader], ly = ay()[leader];
+        double bd = __builtin_nan("");
+        int bt = 0x7FFFFFFF;
+        auto visit = [&](int t, int c) {                      // t = c * 64 + lane; every lane calls (keeps the fp64 work on all lanes)
+            const bool in = t < T_;
+            const int ts_ = in ? t : 0;
+            const uint32_t info = tinfo()[ts_];
+            const bool open = in && !(info & T_FEAS) && ((int)(int8_t)((info >> 8) & 0xFF) > 0);
+            double x, y;
+            if constexpr (IRB) {
+                x = 0.; y = 0.;
+#pragma unroll
+                for (int k = 0; k < NTC; k++) if (k == c) { x = xy.x[k]; y = xy.y[k]; }
+            } else { x = tx()[ts_]; y = ty()[ts_]; }
+            const double dd = dist2(lx, ly, x, y);
+            const bool behind = dd > pd || (dd == pd && t > pt);
+            const bool better = open && behind && (bt == 0x7FFFFFFF || dd < bd);
+            bd = better ? dd : bd;
+            bt = better ? t : bt;
+        };
+        if constexpr (CT != 0) {
+#pragma unroll
+            for (int c = 0; c < NTC; c++) visit(c * WAVE + lane, c);
+        } else {
+            for (int t0 = 0, c = 0; t0 < T_; t0 += WAVE, c++) visit(t0 + lane, c);
+        }
+        const bool have = bt != 0x7FFFFFFF;
+        if (__ballot(have) == 0ull) return -1;
+        const double m = wave_nanmin(have ? bd : __builtin_nan(""));
+        const bool cand = have && bd == m;
+        dist = m;
+        if constexpr (CT != 0 && CT <= 64) {
+            return __ffsll((unsigned long long)__ballot(cand)) - 1;      // one chunk: lane = task
+        } else {
+            return (int)wave_nanmin(cand ? (double)bt : __builtin_nan(""));   // (indices below 2^10: exact in fp64)
+        }
+    }
+
     // TaskEnv.step (env/task_env.py:326-342) + agent_step (:300-324) for leader + followers, then
     // task_update / agent_update (worker.py:74-76) and the move to the next decision point.
     // DEV: the action comes from the device's own valid-action policy on a validated instance (persistent kernel): the error
@@ -1976,7 +2025,8 @@ int dcm::launch_rollout_lookahead(plan::SimKind kind, bool, bool, unsigned grid,
     return with_sim(kind, [&](auto s) {
         using S = decltype(s);
         return launch_family<lookahead_general, false, SIM_ARGS(S), S::MC>(a.form, grid, rollout_random_lds_bytes<SIM_ARGS(S)>(L), stream,
-                                                                           a.kernel_args(), a.rn, a.policy, a.lg, a.snap);
+                                                                           a.kernel_args(), a.rn, a.policy, a.lg, a.snap, a.width,
+                                                                           a.inner_out);
     });
 }
 void dcm::allow_lds_lookahead(int lds) {
@@ -2118,7 +2168,7 @@ const RolloutForm& form_of(const dcm_env* env, const RolloutForm& own) { return 
 // While dcm_set_best_log is set every one of them comes here with FORM_BEST (form_of), which needs the rollout log and no stride.
 int rollout_form(dcm_env* env, const char* fn, const RolloutForm& form, int32_t policy, uint64_t explore_q32, int32_t episodes,
                  int64_t max_decisions, const int64_t* max_decisions_in, float* agents_out, float* tasks_out, uint8_t* mask_out,
-                 int64_t* steps_out, void* stream) {
+                 int64_t* steps_out, void* stream, int32_t width = 0, int64_t* inner_out = nullptr) {
     if (form.keeps_best) {
         if (!env->rollout_log.len)
             return fail(DCM_ERR_STATE, "%s: the best log is set and the rollout log is not: the kept episode is copied from it; call "
@@ -2147,6 +2197,8 @@ int rollout_form(dcm_env* env, const char* fn, const RolloutForm& form, int32_t 
     ra.lg = env->rollout_log;          // (the epsilon-greedy forms take it set or not: one set of forms)
     ra.best = env->best_log;
     ra.snap = env->la_snap;
+    ra.width = width;                  // (the lookahead form alone: dcm_rollout_lookahead_width)
+    ra.inner_out = inner_out;
     const bool all_obs = agents_out && tasks_out && mask_out, no_obs = !agents_out && !tasks_out && !mask_out;
     const plan::Shape shape = shape_of(env);
     const bool fast = !form.lookahead && plan::form_rollout_kind(shape, all_obs || no_obs) == plan::Rollout::Fast;
@@ -2159,6 +2211,28 @@ int need_budget(const dcm_env* env, const char* fn, int64_t max_decisions, const
         return fail(DCM_ERR_INVALID, "%s: with max_waiting_time <= 0 a greedy policy does not end its episodes (a dropped member takes "
                                      "the same task again at the same time): give a decision budget", fn);
     return DCM_OK;
+}
+
+// dcm_rollout_lookahead (width 0, no inner_out) and dcm_rollout_lookahead_width: one set of refusals, each message under the name `fn`
+int rollout_lookahead(dcm_env* env, const char* fn, int32_t base_policy, int32_t width, int32_t episodes, int64_t max_decisions,
+                      const int64_t* max_decisions_in, float* agents_out, float* tasks_out, uint8_t* mask_out, int64_t* steps_out,
+                      int64_t* inner_out, void* stream) {
+    CHECK_ENV(env);
+    if (base_policy != DCM_POLICY_RANDOM && base_policy != DCM_POLICY_FIRST && base_policy != DCM_POLICY_NEAREST)
+        return fail(DCM_ERR_INVALID, "%s: unknown base policy (DCM_POLICY_RANDOM, DCM_POLICY_FIRST, DCM_POLICY_NEAREST)", fn);
+    if (width < 0) return fail(DCM_ERR_INVALID, "%s: width must be >= 0 (0: every unmasked action is valued)", fn);
+    if (episodes < 1) return fail(DCM_ERR_INVALID, "%s: episodes must be >= 1", fn);
+    // every inner episode must end by itself; a decision budget bounds the outer decisions only
+    if (!(env->kp.mwt > 0.0))
+        return fail(DCM_ERR_INVALID, "%s: the handle has max_waiting_time <= 0, where a base policy does not end its episodes "
+                                     "(a dropped member takes the same task again at the same time): an action has no episode to be valued by, "
+                                     "with or without a decision budget", fn);
+    if (!env->reset_done) return fail(DCM_ERR_STATE, "%s: call dcm_reset first", fn);
+    if (env->best_log.episode)
+        return fail(DCM_ERR_STATE, "%s: the best log is set and there is no best-keeping lookahead form: clear it with "
+                                   "dcm_set_best_log(env, NULL, NULL, NULL, NULL, NULL)", fn);
+    return rollout_form(env, fn, FORM_LOOKAHEAD, base_policy, 0, episodes, max_decisions, max_decisions_in, agents_out, tasks_out, mask_out,
+                        steps_out, stream, width, inner_out);
 }
 }  // namespace
 
@@ -2710,21 +2784,15 @@ int dcm_rollout_explore(dcm_env* env, int32_t policy, uint64_t explore_q32, int3
 
 int dcm_rollout_lookahead(dcm_env* env, int32_t base_policy, int32_t episodes, int64_t max_decisions, const int64_t* max_decisions_in,
                           float* agents_out, float* tasks_out, uint8_t* mask_out, int64_t* steps_out, void* stream) {
-    CHECK_ENV(env);
-    if (base_policy != DCM_POLICY_RANDOM && base_policy != DCM_POLICY_FIRST && base_policy != DCM_POLICY_NEAREST)
-        return fail(DCM_ERR_INVALID, "dcm_rollout_lookahead: unknown base policy (DCM_POLICY_RANDOM, DCM_POLICY_FIRST, DCM_POLICY_NEAREST)");
-    if (episodes < 1) return fail(DCM_ERR_INVALID, "dcm_rollout_lookahead: episodes must be >= 1");
-    // every inner episode must end by itself; a decision budget bounds the outer decisions only
-    if (!(env->kp.mwt > 0.0))
-        return fail(DCM_ERR_INVALID, "dcm_rollout_lookahead: the handle has max_waiting_time <= 0, where a base policy does not end its episodes "
-                                     "(a dropped member takes the same task again at the same time): an action has no episode to be valued by, "
-                                     "with or without a decision budget");
-    if (!env->reset_done) return fail(DCM_ERR_STATE, "dcm_rollout_lookahead: call dcm_reset first");
-    if (env->best_log.episode)
-        return fail(DCM_ERR_STATE, "dcm_rollout_lookahead: the best log is set and there is no best-keeping lookahead form: clear it with "
-                                   "dcm_set_best_log(env, NULL, NULL, NULL, NULL, NULL)");
-    return rollout_form(env, "dcm_rollout_lookahead", FORM_LOOKAHEAD, base_policy, 0, episodes, max_decisions, max_decisions_in, agents_out,
-                        tasks_out, mask_out, steps_out, stream);
+    return rollout_lookahead(env, "dcm_rollout_lookahead", base_policy, 0, episodes, max_decisions, max_decisions_in, agents_out, tasks_out,
+                             mask_out, steps_out, nullptr, stream);
+}
+
+int dcm_rollout_lookahead_width(dcm_env* env, int32_t base_policy, int32_t width, int32_t episodes, int64_t max_decisions,
+                                const int64_t* max_decisions_in, float* agents_out, float* tasks_out, uint8_t* mask_out,
+                                int64_t* steps_out, int64_t* inner_out, void* stream) {
+    return rollout_lookahead(env, "dcm_rollout_lookahead_width", base_policy, width, episodes, max_decisions, max_decisions_in, agents_out,
+                             tasks_out, mask_out, steps_out, inner_out, stream);
 }
 
 int dcm_summary(dcm_env* env, double* out, void* stream) {

@@ -22,7 +22,8 @@
 //   DCM_LOG       k_lg_<base> / k_lgrn_<base>    either, dcm_set_rollout_log set      , int policy, RouteLog lg
 //   DCM_EXPLORE   k_ex_<base> / k_exrn_<base>    dcm_rollout_explore                  , int policy, uint64_t explore_q32, RouteLog lg
 //   DCM_BEST      k_bs_<base> / --               any of the three, dcm_set_best_log   , int policy, uint64_t explore_q32, RouteLog lg, BestLog best
-//   DCM_LOOKAHEAD k_la_<base> / k_larn_<base>    dcm_rollout_lookahead                , int policy, RouteLog lg, unsigned char* snap
+//   DCM_LOOKAHEAD k_la_<base> / k_larn_<base>    dcm_rollout_lookahead[_width]        , int policy, RouteLog lg, unsigned char* snap,
+//                                                                                       int width, int64_t* inner_out
 // Greedy: the action comes from `policy` (wave-uniform) instead of protocol slot 1.  Logging: `policy` covers all three policies
 // (DCM_POLICY_RANDOM takes slot 1 as the plain form does) and every agent_step is appended to the log.  Epsilon-greedy: the logging
 // form with explore_q32; the log may be unset there (lg.len null).  These forms exist for k_rollout_fast and k_rollout_random only,
@@ -34,7 +35,8 @@
 // log if the episode beats the kept one.  No renewing form at all: the host refuses a best-keeping launch while a stride is set.
 // Lookahead (rollout_lookahead.hpp): every decision is chosen by one-step lookahead over the base `policy` (any of the three) -- the
 // wave snapshots its env into its slice of `snap`, plays one inner episode per unmasked action and restores -- and the logging code
-// rides along as in the epsilon-greedy forms (lg.len null: no log).  k_rollout_random only; no size-renewing form.
+// rides along as in the epsilon-greedy forms (lg.len null: no log).  `width` (0: all) limits the valued actions to the nearest ones;
+// `inner_out` (null: not wanted) takes per env the inner episodes' decisions.  k_rollout_random only; no size-renewing form.
 // KEXPLORES (defined here, for the texts): the form draws explore words -- DCM_EXPLORE or DCM_BEST.
 //
 // Two kernels from one text leave the first as it was: a form holds nothing of the others and compiles to the code it had before
@@ -92,7 +94,7 @@
 #define KPOLICY_PARAM , int policy, uint64_t explore_q32, RouteLog lg, BestLog best
 #elif defined(DCM_LOOKAHEAD)
 #define KPREFIX KFORM_PICK(k_la_, k_larn_)
-#define KPOLICY_PARAM , int policy, RouteLog lg, unsigned char* snap
+#define KPOLICY_PARAM , int policy, RouteLog lg, unsigned char* snap, int width, int64_t* inner_out
 #elif DCM_RENEW == 2
 #define KPREFIX k_rs_
 #define KPOLICY_PARAM

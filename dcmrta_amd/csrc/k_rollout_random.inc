@@ -9,7 +9,8 @@
 // logging forms (explore_q32 = 0 there: the k_lg_* launch), plus keep_best behind the decision loop of a finished episode.
 // Lookahead form (rollout_lookahead.hpp): the logging form's loop -- budget rule, restart, observation rows, log, all of them the OUTER
 // decisions' -- with lookahead_action in the place of the policy's pick: the wave plays one inner episode per unmasked action
-// between two snapshots of its env and takes the action whose episode ends best.
+// between two snapshots of its env and takes the action whose episode ends best.  `width` limits the valued actions to the nearest
+// ones (0: all of them), and `inner_out`, if set, takes the env's count of the inner episodes' decisions beside steps_out.
 #define KBASE rollout_random
 #define KPOLICY_FORMS 1
 #define KLOOKAHEAD_FORM 1
@@ -54,6 +55,9 @@ __global__ __launch_bounds__(WAVE, 3) void KNAME(int A, int T, int PA, int PT, K
     const int left0 = rollout_budget(e, budget_all, budget_in);
 #endif
     int left = left0;
+#ifdef DCM_LOOKAHEAD
+    int64_t inner = 0;   // base-policy decisions inside inner episodes (wave-uniform): inner_out
+#endif
     PH_DECL;
     // key_1 = mix64(seed + GAMMA (d+1)): the argument is carried and advanced by GAMMA per decision (no 64-bit multiply,
     // and neither seed nor d stay live in the loop: d = d0 + steps afterwards)
@@ -99,7 +103,7 @@ __global__ __launch_bounds__(WAVE, 3) void KNAME(int A, int T, int PA, int PT, K
             const int action = explores ? S.pick_random_action(lane, k1) : S.pick_policy_action(lane, leader, policy, xy);
 #endif
 #elif defined(DCM_LOOKAHEAD)
-            const int action = lookahead_action(S, h, P, lane, leader, gm, k1, gd, policy, xy, snap, e, BA, BT PH_PASS);
+            const int action = lookahead_action(S, h, P, lane, leader, gm, k1, gd, policy, xy, snap, e, BA, BT, width, inner PH_PASS);
 #elif defined(DCM_POLICY)
             const int action = S.pick_policy_action(lane, leader, policy, xy);
 #elif defined(DCM_LOG)
@@ -126,6 +130,9 @@ __global__ __launch_bounds__(WAVE, 3) void KNAME(int A, int T, int PA, int PT, K
     PH_FLUSH(lane);
     const int64_t steps = (int64_t)(left0 - left);
     if (lane == 0 && steps_out) steps_out[e] = steps;
+#ifdef DCM_LOOKAHEAD
+    if (lane == 0 && inner_out) inner_out[e] = inner;
+#endif
     h.d = d0 + (uint64_t)steps;   // every decision of this kernel is valid, so apply_and_advance counted exactly `steps`
     {   // Hdr::max_arrival: this kernel only takes valid actions, under which every arrival list is monotone, so the maximum of
         // the agents' last arrivals IS the running maximum of the episode so far -- folded in once per launch for a later

@@ -32,8 +32,17 @@
 //      an earlier episode -- the one case in which the two could differ, and not reachable with the device's own valid actions;
 //   4. the env is put back: overflow counts, abandonment rows, record image (and, MG, the member arrival times in the HBM record);
 //      the incremental task_update is told that it knows nothing of the previous call, as at the head of a launch.
-// The best value wins -- more finished tasks, then the larger reward, strict and exact in fp64, so a tie keeps the lowest action.
+// The best value wins -- more finished tasks, then the larger reward, exact in fp64, and a tie goes to the lowest action index.
 // No unmasked task: the depot (0), the one allowed action; exactly one: that task; neither costs a snapshot or an inner episode.
+// `width` (dcm_rollout_lookahead_width; 0 = every unmasked task, the rule above) values only the `width` unmasked tasks NEAREST would
+// pick one after the other if each pick were masked for the next: the `width` smallest by (rounded fp64 dist2 from the leader, task
+// index).  T goes up to 1023, so the list is never stored: after every inner episode the env is back bit for bit, mask and distances
+// included, and Sim::next_nearest_task finds the next candidate behind a wave-uniform cursor (the last one's distance and index).
+// The candidates are valued in that order, hence the explicit index tie-break of the best-pair compare; width >= the number of
+// unmasked tasks takes the ascending loop of width 0, inner episode for inner episode; width == 1 is NEAREST's pick itself, with no
+// snapshot and no inner episode, whatever the base policy.
+// `inner` counts the base-policy decisions of the inner episodes: every apply_and_advance<true, true> below but each episode's first,
+// which is decision d itself (wave-uniform; the kernel stores it to inner_out once, at its end).
 // `h`, the hot header fields, is copied for the inner episodes and never changed; the cold ones travel with the record image.
 // The overflow count table is only ever touched by an agent's 17th abandonment of an episode, and is all zero while no agent has
 // had one (Sim::clear_spilled_counts): it is saved only if the env has spilled when the snapshot is taken, and after an inner
@@ -41,7 +50,8 @@
 template <class SimT>
 __device__ __forceinline__ int lookahead_action(const SimT& S, const HdrRegs& h, const KP& P, int lane, int leader,
                                                 const typename SimT::AMask& gm, uint64_t k1, uint64_t gd, int policy,
-                                                const typename SimT::XY& xy, unsigned char* snap, int e, int BA, int BT PH_ARGS) {
+                                                const typename SimT::XY& xy, unsigned char* snap, int e, int BA, int BT, int width,
+                                                int64_t& inner PH_ARGS) {
     const int T_ = S.T();
     auto unmasked = [](uint32_t info) { return !(info & T_FEAS) && ((int)(int8_t)((info >> 8) & 0xFF) > 0); };   // :199, as observe()
     int nfree = 0, lowest = -1;
@@ -53,6 +63,8 @@ __device__ __forceinline__ int lookahead_action(const SimT& S, const HdrRegs& h,
     }
     if (nfree == 0) return 0;
     if (nfree == 1) return lowest + 1;
+    if (width == 1) return S.pick_policy_action(lane, leader, DCM_POLICY_NEAREST, xy);
+    const bool all = width == 0 || width >= nfree;   // wave-uniform
 
     const Lay L = S.L();
     unsigned char* const img = snap + (size_t)e * ((size_t)L.rec_bytes() + 64u + 32u * (size_t)BA + abcnt_pitch(BA, BT));
@@ -73,8 +85,15 @@ __device__ __forceinline__ int lookahead_action(const SimT& S, const HdrRegs& h,
 
     int best = 0;
     double bn = -1.0, br = 0.0;
-    for (int t = lowest; t < T_; t++) {
-        if (!unmasked(uni(S.tinfo()[t]))) continue;
+    double pd = -1.0;   // the candidate cursor: in front of every task
+    for (int t = lowest - 1, n = 0;; n++) {
+        if (all) {
+            do t++; while (t < T_ && !unmasked(uni(S.tinfo()[t])));
+            if (t >= T_) break;
+        } else {
+            if (n == width) break;
+            t = S.next_nearest_task(lane, leader, pd, t, xy, pd);   // n < width < nfree: there is one
+        }
         HdrRegs hi = h;
         uint64_t gi = gd, k = k1;
         int ld = leader, act = t + 1;
@@ -88,6 +107,7 @@ __device__ __forceinline__ int lookahead_action(const SimT& S, const HdrRegs& h,
             ld = S.pick_leader(hi, lane, -1, k, g2);
             if (ld < 0) break;
             act = policy == DCM_POLICY_RANDOM ? S.pick_random_action(lane, k) : S.pick_policy_action(lane, ld, policy, xy);
+            inner++;
         }
         WSYNC();
         int nfin = 0;
@@ -96,7 +116,12 @@ __device__ __forceinline__ int lookahead_action(const SimT& S, const HdrRegs& h,
             nfin += __popcll(__ballot(u < T_ && (S.tinfo()[u < T_ ? u : 0] & T_FIN)));
         }
         const double cn = (double)nfin, cr = -hi.now;
-        if (cn > bn || (cn == bn && cr > br)) { best = t + 1; bn = cn; br = cr; }
+        // (one predicate and three selects, no branches: written as `if (cn > bn || (cn == bn && (...))) { best = ...; bn = cn; br = cr; }`
+        //  hipcc 7 structurises the nested short-circuit over these VGPR-held doubles so that the cn == bn arm keeps the OLD br)
+        const bool better = (cn > bn) | ((cn == bn) & ((cr > br) | ((cr == br) & (t + 1 < best))));
+        best = better ? t + 1 : best;
+        bn = better ? cn : bn;
+        br = better ? cr : br;
         // put the env back
         const bool spilled1 = spilled();
         WSYNC();

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define DCM_ABI_VERSION 5 /* v3: dcm_build_id, dcm_set_visibility, dcm_load_instances validates req on the device; v4: dcm_set_replay_placement; v5: DCM_PARAM_WIDE_MEMBERS; still v5, additions only: dcm_generate_instances, dcm_get_instances, dcm_generator_draws, dcm_set_instance_renewal, dcm_instance_index, DCM_PARAM_RENEW_SIZES, dcm_set_rollout_log, dcm_set_best_log, dcm_reduce_best, dcm_fork_envs, dcm_rollout_lookahead */
+#define DCM_ABI_VERSION 5 /* v3: dcm_build_id, dcm_set_visibility, dcm_load_instances validates req on the device; v4: dcm_set_replay_placement; v5: DCM_PARAM_WIDE_MEMBERS; still v5, additions only: dcm_generate_instances, dcm_get_instances, dcm_generator_draws, dcm_set_instance_renewal, dcm_instance_index, DCM_PARAM_RENEW_SIZES, dcm_set_rollout_log, dcm_set_best_log, dcm_reduce_best, dcm_fork_envs, dcm_rollout_lookahead, dcm_rollout_lookahead_width */
 
 typedef struct dcm_env dcm_env; /* opaque */
 
@@ -438,6 +438,34 @@ int dcm_rollout_explore(dcm_env *env, int32_t policy, uint64_t explore_q32, int3
 int dcm_rollout_lookahead(dcm_env *env, int32_t base_policy, int32_t episodes, int64_t max_decisions,
                           const int64_t *max_decisions_in, float *agents_out, float *tasks_out, uint8_t *mask_out,
                           int64_t *steps_out, void *stream);
+
+/* dcm_rollout_lookahead with a CANDIDATE LIST: a decision values only the `width` nearest unmasked tasks, and the launch reports what
+ * its inner episodes cost.  dcm_rollout_lookahead is this call with width = 0 and inner_out = NULL; every argument they share means
+ * the same, and everything said there about what a launch leaves behind holds here.
+ * The rule, for decision d of an env with n unmasked tasks and width = W >= 0:
+ *   n == 0: the depot.  n == 1: that task.  Neither costs a snapshot or an inner episode.
+ *   W == 0 or W >= n: dcm_rollout_lookahead's rule -- every unmasked action is valued, in ascending order, and the launch leaves byte
+ *     for byte what that entry leaves.
+ *   W == 1: DCM_POLICY_NEAREST's pick itself, whatever the base policy; no snapshot, no inner episode.
+ *   otherwise: the candidates are the W unmasked tasks DCM_POLICY_NEAREST would pick one after the other if each pick were masked for
+ *     the next one -- the W smallest by (distance from the leader, task index), compared lexicographically: the ROUNDED fp64 distances
+ *     (dist2, agent first), so two tasks at an equal distance rank by the lower index, also across the cut between the W-th and the
+ *     (W+1)-th.  The ranking is always NEAREST's; it does not depend on base_policy.  Each candidate is valued as in
+ *     dcm_rollout_lookahead: decision d takes it with the leader and followers the real step draws and base_policy plays to the end;
+ *     the largest (finished tasks, reward) wins, exact in fp64, and a tie of both goes to the LOWEST ACTION INDEX, whatever order the
+ *     candidates were valued in.
+ * inner_out[n_envs] (device, int64; may be NULL): the number of base-policy decisions the env took INSIDE inner episodes during this
+ * launch, over all its outer decisions and episodes: every decision of an inner episode but its first, which is decision d itself.
+ * An env that valued nothing (budget 0, width 1, never two unmasked tasks) gets 0.  Written once per launch like steps_out, which
+ * still counts the outer decisions only.  The candidate list is never stored (n_tasks goes up to 1023): the env is back bit for bit
+ * after every inner episode, so the next candidate is found again from the last one's (distance, index).
+ * Cost: about min(W, unmasked actions) x (decisions left in the episode) base-policy decisions per outer decision; inner_out is that
+ * number as played (DESIGN.md 6 has measured times beside it).
+ * Refusals, before anything is launched or written (steps_out and inner_out included), every message names
+ * dcm_rollout_lookahead_width: those of dcm_rollout_lookahead with the same status, and DCM_ERR_INVALID for width < 0. */
+int dcm_rollout_lookahead_width(dcm_env *env, int32_t base_policy, int32_t width, int32_t episodes, int64_t max_decisions,
+                                const int64_t *max_decisions_in, float *agents_out, float *tasks_out, uint8_t *mask_out,
+                                int64_t *steps_out, int64_t *inner_out, void *stream);
 
 /* Terminal results of the last finished episode (worker.py:87,103-108):
  * out[B,8] f64 = reward(-makespan), n_finished_tasks, success_rate, makespan, time_cost,

@@ -3,7 +3,7 @@
 and take the best -- for N instances in one handle.
 
     python tools/lookahead_plan.py [--agents 20 --tasks 50 --instance-seed 7000 | --golden I] [--instances 4] [--seed 11] [--cap 64]
-                                   [--out plan.yaml] [--device]
+                                   [--out plan.yaml] [--device [--width W]]
 
 Instance n -- generate_instance(agents, tasks, instance_seed + n), or the (I + n)-th of tests/golden/instances_20A50T.npz -- is env n
 of one handle of N envs, all with the seed env_seed(seed, 0), as in tools/sample_plan.py.  Lookahead.plan() forks the N envs into
@@ -18,7 +18,10 @@ Worker.generate_route writes (--out with one instance, plan_<n>.yaml next to it 
 env's wave values its own actions one after the other and takes the best, nothing returns to the host, and the plan is read from the
 rollout log.  Same rewards, same plan files; the JSON line then has lookahead_launches = 1, branches = 0 and decisions = the decisions
 of the plan itself (the inner episodes' are not counted on the device).  `--device cuda:N` with a value keeps its old meaning, the GPU
-of the host-driven run; --torch-device names the GPU for either."""
+of the host-driven run; --torch-device names the GPU for either.
+--width W (with bare --device): every decision values only the W unmasked tasks nearest to the leader (dcm_rollout_lookahead_width;
+0, the default: all of them).  Another, cheaper plan: the JSON line gains width and inner_decisions, the base-policy decisions the
+inner episodes played."""
 import argparse
 import json
 import os
@@ -49,10 +52,13 @@ def main():
     ap.add_argument("--device", nargs="?", default=None, const=True,
                     help="bare: plan with one persistent launch (the device form); with a value: the GPU, as --torch-device")
     ap.add_argument("--torch-device", default="cuda:0")
+    ap.add_argument("--width", type=int, default=None, help="with bare --device: value only the W nearest unmasked tasks (0: all)")
     args = ap.parse_args()
     if args.instances < 1:
         ap.error("--instances must be >= 1")
     on_device = args.device is True
+    if args.width is not None and (not on_device or args.width < 0):
+        ap.error("--width W >= 0 belongs to the device form: give a bare --device")
     args.device = args.torch_device if args.device in (None, True) else args.device
     N = args.instances
     if args.golden is not None:
@@ -75,11 +81,16 @@ def main():
     nearest = [pair(row) for row in greedy.summary().cpu().numpy()]
 
     env = BatchedTaskEnv(N, A, T, device=args.device).load_instances(*batch)
+    extra = {}
     if on_device:
         env.enable_rollout_log(args.cap)
         env.reset(seeds, observe=False)
         launches, branches = 1, 0
-        decisions = int(env.rollout("nearest", episodes=1, write_obs=False, lookahead=True).sum())
+        if args.width is None:
+            decisions = int(env.rollout("nearest", episodes=1, write_obs=False, lookahead=True).sum())
+        else:
+            steps, inner = env.rollout("nearest", episodes=1, write_obs=False, lookahead=True, width=args.width, return_inner=True)
+            decisions, extra = int(steps.sum()), dict(width=args.width, inner_decisions=int(inner.sum()))
         routes_of = env.rollout_routes
     else:
         env.enable_route_log(args.cap)
@@ -98,7 +109,7 @@ def main():
     one = lambda xs: xs[0] if N == 1 else xs
     print(json.dumps(dict(instance=one(sources), instances=N, nearest=one(nearest), lookahead=one(plan), lookahead_launches=launches,
                           branches=branches, decisions=decisions, improved=sum((p["finished"], p["reward"]) > (g["finished"], g["reward"])
-                                                                                  for p, g in zip(plan, nearest)), out=one(outs))))
+                                                                                  for p, g in zip(plan, nearest)), out=one(outs), **extra)))
 
 
 if __name__ == "__main__":
