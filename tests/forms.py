@@ -12,49 +12,64 @@ import oracle_ref as O
 
 
 @functools.lru_cache(maxsize=None)
-def _instances(A, T, B, ranges, uniform_base, ragged_base, choice_base):
+def _instances(A, T, B, ranges, uniform_base, ragged_base, choice_base, degen=False):
     from dcmrta_amd.choice import env_seeds
     from dcmrta_amd.instances import generate_batch, generate_batch_ranges
     inst = generate_batch(B, A, T, base_seed=uniform_base + 3 * A + T) if ranges is None \
         else generate_batch_ranges(range(ragged_base, ragged_base + B), *ranges)
-    return inst, env_seeds(choice_base, 0, B)
+    return (degenerate(inst) if degen else inst), env_seeds(choice_base, 0, B)
 
 
-def _new_sims(A, T, B, mwt, ranges, bases, policy):
-    inst, seeds = _instances(A, T, B, ranges, *bases)
+def degenerate(inst):
+    """A copy of a uniform generate_batch result with the edges an instance can have: task 2k+1 lies on task 2k (coincident pairs:
+    `nearest` ties at equal rounded distance, agents on different tasks share a position in the group scan), tasks 0 and 1 lie on the
+    depot (distance 0, travel time 0, arrival == now), and every third task has duration 0 (time_finish == time_start: it finishes in
+    the event that starts it).  The requirements stay as generated."""
+    out = {k: np.array(v, copy=True) for k, v in inst.items()}
+    xy, T = out["task_xy"], out["task_xy"].shape[1]
+    xy[:, 1:T:2] = xy[:, 0:T - 1:2]
+    xy[:, 0] = xy[:, 1] = out["depot"]
+    out["dur"][:, ::3] = 0.0
+    return out
+
+
+def _new_sims(A, T, B, mwt, ranges, bases, policy, max_time=100.0, degen=False):
+    inst, seeds = _instances(A, T, B, ranges, *bases, degen)
     sims = []
     for b in range(B):
         a, t = (A, T) if ranges is None else (int(inst["n_agents"][b]), int(inst["n_tasks"][b]))
-        sims.append(O.Sim(a, t, lambda j, one=O.one(inst, b, t): one, seeds[b], policy, mwt))
+        sims.append(O.Sim(a, t, lambda j, one=O.one(inst, b, t): one, seeds[b], policy, mwt, max_time))
     return sims
 
 
 @functools.lru_cache(maxsize=None)
-def _sims(A, T, B, mwt, ranges, budget, bases, policy, episodes):
-    sims = _new_sims(A, T, B, mwt, ranges, bases, policy)
+def _sims(A, T, B, mwt, ranges, budget, bases, policy, episodes, max_time=100.0, degen=False):
+    sims = _new_sims(A, T, B, mwt, ranges, bases, policy, max_time, degen)
     return sims, np.array([s.launch(episodes, budget) for s in sims], np.int64)
 
 
 class Forms:
-    def __init__(self, forms, big_forms, uniform_base, ragged_base, choice_base):
+    def __init__(self, forms, big_forms, uniform_base, ragged_base, choice_base, degenerate=()):
+        """degenerate: the ids of the forms that play degenerate() of their generated instances"""
         self.all, self.big, self.bases = {**forms, **big_forms}, big_forms, (uniform_base, ragged_base, choice_base)
+        self.degenerate = frozenset(degenerate)
 
     def instances(self, form):
         """(instances, choice seeds) of a form: computed once, shared, never changed."""
         A, T, B, _, ranges, _ = self.all[form]
-        return _instances(A, T, B, ranges, *self.bases)
+        return _instances(A, T, B, ranges, *self.bases, form in self.degenerate)
 
     def sims(self, form, policy, episodes):
         """The oracle's side of one launch of `episodes` episodes on a form under its budget, (Sim per env, steps per env): computed
         once, shared, never changed."""
         A, T, B, kw, ranges, budget = self.all[form]
-        return _sims(A, T, B, kw.get("max_waiting_time", 10.0), ranges, budget, self.bases, policy, episodes)
+        return _sims(A, T, B, kw.get("max_waiting_time", 10.0), ranges, budget, self.bases, policy, episodes, kw.get("max_time", 100.0), form in self.degenerate)
 
     def episodes(self, form, policy, episodes):
         """The oracle's episodes 0 .. episodes-1 of every env of a form, one per unlimited launch: [b][k] = an object with .o and .a."""
         A, T, B, kw, ranges, _ = self.all[form]
         out = []
-        for s in _new_sims(A, T, B, kw.get("max_waiting_time", 10.0), ranges, self.bases, policy):
+        for s in _new_sims(A, T, B, kw.get("max_waiting_time", 10.0), ranges, self.bases, policy, kw.get("max_time", 100.0), form in self.degenerate):
             eps = []
             for _ in range(episodes):
                 s.launch(1, -1)

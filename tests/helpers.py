@@ -57,6 +57,27 @@ def sized_env(gpu_device, A, T, inst, sizes=None, **kw):
     return env.load_instances(**inst)
 
 
+def rollout_mask_only(env, policy, episodes, budget):
+    """A persistent launch that is given the mask buffer alone (BatchedTaskEnv.rollout gives all three observation buffers or none): a
+    partial buffer set, which every shape plays in the general kernel.  budget: a scalar.  Returns steps int64[B] (numpy).  The
+    argument tail is checked against the bound signature, so that a change of the entry point fails here and not in a wrong call."""
+    import ctypes as C
+    import torch
+    from dcmrta_amd import _lib
+    from dcmrta_amd.batched_env import _ptr, check
+    vp = C.c_void_p
+    tail_types = [C.c_int32, C.c_int64, vp, vp, vp, vp, vp, vp]          # episodes, max_decisions, max_decisions_in, obs x3, steps, stream
+    assert _lib.SIGNATURES["dcm_rollout_random"][1] == [vp] + tail_types and _lib.SIGNATURES["dcm_rollout_policy"][1] == [vp, C.c_int32] + tail_types
+    steps = torch.empty((env.B,), dtype=torch.int64, device=env.device)
+    tail = (int(episodes), int(budget), None, None, None, _ptr(env._mask), _ptr(steps), env._stream())
+    with torch.cuda.device(env.device):
+        if policy == "random":
+            check(env._lib.dcm_rollout_random(env._h, *tail))
+        else:
+            check(env._lib.dcm_rollout_policy(env._h, env.POLICIES[policy], *tail))
+    return steps.cpu().numpy()
+
+
 def run_lockstep(env, seeds, policy, inject=None, max_iters=100000):
     """Drive a BatchedTaskEnv step by step (fused observe) and record per-env traces.
 

@@ -20,7 +20,7 @@ def shifted_seed(seed, d0):
     return (int(seed) + GAMMA * int(d0)) & MASK64
 
 
-def lookahead_walk(a, t, inst_one, seed, policy, mwt=10.0):
+def lookahead_walk(a, t, inst_one, seed, policy, mwt=10.0, max_time=LA.MAX_TIME):
     """LA.walk with the lookahead rule as action_of.  At decision d every unmasked action a is valued by the oracle's result of
     LA.policy_walk(..., forced={0: a_0, ..., d-1: a_{d-1}, d: a}) -- a_0 .. a_{d-1} the lookahead's own earlier choices -- and the
     largest LA.pair wins, ties to the lowest action (strict > in ascending order).
@@ -35,8 +35,8 @@ def lookahead_walk(a, t, inst_one, seed, policy, mwt=10.0):
     def action_of(c):
         best, best_pair = None, None
         for act in np.flatnonzero(c.mask == 0):
-            w = LA.policy_walk(a, t, inst_one, seed, policy, mwt, forced={**chosen, c.d: int(act)})
-            p = LA.pair(LA.result(a, t, inst_one, w, mwt))
+            w = LA.policy_walk(a, t, inst_one, seed, policy, mwt, forced={**chosen, c.d: int(act)}, max_time=max_time)
+            p = LA.pair(LA.result(a, t, inst_one, w, mwt, max_time))
             if best is None or p > best_pair:
                 best, best_pair = int(act), p
         assert best is not None, "the mask always allows an action: the depot when no task is unmasked"
@@ -45,9 +45,9 @@ def lookahead_walk(a, t, inst_one, seed, policy, mwt=10.0):
         nfree.append(int((c.mask == 0).sum()))
         return best
 
-    w = LA.walk(a, t, inst_one, seed, action_of, mwt)
+    w = LA.walk(a, t, inst_one, seed, action_of, mwt, max_time=max_time)
     assert w["ended"]
-    o = oracle.OracleEnv(a, t, max_waiting_time=mwt).load(inst_one["depot"], inst_one["task_xy"], inst_one["req"], inst_one["dur"])
+    o = oracle.OracleEnv(a, t, max_waiting_time=mwt, max_time=max_time).load(inst_one["depot"], inst_one["task_xy"], inst_one["req"], inst_one["dur"])
     r = o.rollout(0, 0, oracle.POLICY_INJECTED, cap_steps=max(w["n_steps"], 1), record=False, inj_leader=w["leader"],
                   inj_action=w["action"], inj_nfol=w["nfol"], inj_followers=w["followers"])
     assert r["n_steps"] == w["n_steps"]
@@ -118,11 +118,11 @@ def most_abandoned(o):
     return int(n.max())
 
 
-def replay(a, t, inst_one, w, mwt):
+def replay(a, t, inst_one, w, mwt, max_time=LA.MAX_TIME):
     """The oracle's own rollout of a walk's choices: (the OracleEnv, holding the route lists; its result; the flags the env's header holds
     after the episode, as lookahead_walk states them)."""
     import oracle
-    o = oracle.OracleEnv(a, t, max_waiting_time=mwt).load(inst_one["depot"], inst_one["task_xy"], inst_one["req"], inst_one["dur"])
+    o = oracle.OracleEnv(a, t, max_waiting_time=mwt, max_time=max_time).load(inst_one["depot"], inst_one["task_xy"], inst_one["req"], inst_one["dur"])
     r = o.rollout(0, 0, oracle.POLICY_INJECTED, cap_steps=max(w["n_steps"], 1), record=False, inj_leader=w["leader"],
                   inj_action=w["action"], inj_nfol=w["nfol"], inj_followers=w["followers"])
     assert r["n_steps"] == w["n_steps"]
@@ -130,7 +130,7 @@ def replay(a, t, inst_one, w, mwt):
     return o, r, flags
 
 
-def lookahead_window(a, t, inst_one, seed, policy, mwt, d0, k):
+def lookahead_window(a, t, inst_one, seed, policy, mwt, d0, k, max_time=LA.MAX_TIME):
     """LA.walk(..., stop=d0 + k): decisions < d0 take the base policy's pick, decisions d0 .. d0 + k - 1 the lookahead rule -- no
     unmasked task: the depot; exactly one: that task; otherwise every unmasked action is valued by the oracle's result of
     LA.policy_walk(..., forced={every earlier choice, d: act}), and the largest LA.pair wins, strict > in ascending order.
@@ -154,11 +154,11 @@ def lookahead_window(a, t, inst_one, seed, policy, mwt, d0, k):
         if len(free) > 1:
             pairs, most = [], []
             for act in free:
-                w = LA.policy_walk(a, t, inst_one, seed, policy, mwt, forced={**chosen, c.d: int(act)})
-                r = LA.result(a, t, inst_one, w, mwt)
+                w = LA.policy_walk(a, t, inst_one, seed, policy, mwt, forced={**chosen, c.d: int(act)}, max_time=max_time)
+                r = LA.result(a, t, inst_one, w, mwt, max_time)
                 pairs.append(LA.pair(r))
                 most.append(most_abandoned(w["o"]))
-                f["at_max_time"] += w["o"].now >= LA.MAX_TIME
+                f["at_max_time"] += w["o"].now >= max_time
                 f["truncated"] += bool(r["truncated"])
             best, best_pair = None, None
             for act, p in zip(free, pairs):
@@ -170,16 +170,16 @@ def lookahead_window(a, t, inst_one, seed, policy, mwt, d0, k):
         facts.append(f)
         return best
 
-    w = LA.walk(a, t, inst_one, seed, action_of, mwt, stop=d0 + k)
+    w = LA.walk(a, t, inst_one, seed, action_of, mwt, stop=d0 + k, max_time=max_time)
     return dict(w, chosen=chosen, facts=facts, a=a, t=t)
 
 
-def window_tail(a, t, inst_one, seed, policy, mwt, chosen):
+def window_tail(a, t, inst_one, seed, policy, mwt, chosen, max_time=LA.MAX_TIME):
     """The whole episode made of the prefix, the window (chosen: lookahead_window's) and the base policy to the end: the walk plus
     result, o (the OracleEnv of the oracle's replay, for its route lists), flags and a, as lookahead_walk returns them."""
-    w = LA.policy_walk(a, t, inst_one, int(seed), policy, mwt, forced=dict(chosen))
+    w = LA.policy_walk(a, t, inst_one, int(seed), policy, mwt, forced=dict(chosen), max_time=max_time)
     assert w["ended"]
-    o, r, flags = replay(a, t, inst_one, w, mwt)
+    o, r, flags = replay(a, t, inst_one, w, mwt, max_time)
     return dict(w, result=r, o=o, flags=flags, a=a)
 
 

@@ -60,29 +60,32 @@ def base_pick(policy, seed_of):
     return lambda mask, pos, task_xy, d: f(mask, pos, task_xy)
 
 
-def walk(a, t, inst_one, seed, action_of, mwt=10.0, switch=None, stop=None):
+def walk(a, t, inst_one, seed, action_of, mwt=10.0, switch=None, stop=None, max_time=MAX_TIME, after_task_update=None):
     """One oracle episode through the step-wise API (the loop of worker.py:45-87, as removal_ref.walk_episode restates it) with
     every decision's action given by action_of(c) -> action; c.d: the decision counter, c.mask, c.leader, c.pos: the deciding agent's
     fp64 location, c.task_xy, c.seed_of: d -> the seed decision d draws from, c.o: the OracleEnv in front of the decision.
     switch = (d_s, seed_2): decisions d >= d_s draw leader, action and followers from seed_2 -- a copy of the env made in front of
-    decision d_s and given that seed.  stop: walk only the first `stop` decisions.
+    decision d_s and given that seed.  stop: walk only the first `stop` decisions.  after_task_update(o): called behind every task_update
+    pass of the walk.
     Returns dict(leader, action, nfol, followers[n, a], mask: the mask in front of every decision taken, n_steps, ended,
     seed_of) -- the choices in the form OracleEnv.rollout injects -- and o, the OracleEnv where the walk left it (a walk that `stop`
     cut: in front of decision `stop`)."""
     import oracle
     from dcmrta_amd.choice import below, draw
     seed_of = (lambda d: seed) if switch is None else (lambda d: switch[1] if d >= switch[0] else seed)
-    o = oracle.OracleEnv(a, t, max_waiting_time=mwt).load(inst_one["depot"], inst_one["task_xy"], inst_one["req"], inst_one["dur"])
+    o = oracle.OracleEnv(a, t, max_waiting_time=mwt, max_time=max_time).load(inst_one["depot"], inst_one["task_xy"], inst_one["req"], inst_one["dur"])
     task_xy = np.asarray(inst_one["task_xy"], np.float64)
     pos = [(float(inst_one["depot"][0]), float(inst_one["depot"][1]))] * a
     pos = list(pos)
     leaders, actions, nfols, fols, masks = [], [], [], [], []
     finished, d, empty, cut = False, 0, 0, False
-    while not finished and o.now < MAX_TIME and not cut:                    # worker.py:45
+    while not finished and o.now < max_time and not cut:                    # worker.py:45
         ids, now = o.next_decision()                                        # :47
         groups = o.get_unique_group(ids) if len(ids) else []               # :48
         o.now = now                                                         # :49
         o.task_update()                                                     # :50
+        if after_task_update:
+            after_task_update(o)
         o.agent_update()                                                    # :51
         if not groups:
             empty += 1
@@ -109,6 +112,8 @@ def walk(a, t, inst_one, seed, action_of, mwt=10.0, switch=None, stop=None):
                     pos[m] = (float(task_xy[action - 1, 0]), float(task_xy[action - 1, 1])) if action >= 1 else \
                         (float(inst_one["depot"][0]), float(inst_one["depot"][1]))
                 o.task_update()                                             # :74
+                if after_task_update:
+                    after_task_update(o)
                 o.agent_update()                                            # :76
                 leaders.append(leader); actions.append(action); nfols.append(len(step) - 1); masks.append(mask)
                 fols.append(step[1:] + [-1] * (a - len(step) + 1))
@@ -123,46 +128,46 @@ def walk(a, t, inst_one, seed, action_of, mwt=10.0, switch=None, stop=None):
                 n_steps=n, ended=not cut, seed_of=seed_of, o=o)
 
 
-def result(a, t, inst_one, w, mwt=10.0):
+def result(a, t, inst_one, w, mwt=10.0, max_time=MAX_TIME):
     """The oracle's own rollout of a finished walk's choices, every one of them injected: the episode's terminal results
     (OracleEnv.rollout's dict; n_steps must come out as the walk's)."""
     import oracle
     assert w["ended"], "only a whole episode has a result"
-    o = oracle.OracleEnv(a, t, max_waiting_time=mwt).load(inst_one["depot"], inst_one["task_xy"], inst_one["req"], inst_one["dur"])
+    o = oracle.OracleEnv(a, t, max_waiting_time=mwt, max_time=max_time).load(inst_one["depot"], inst_one["task_xy"], inst_one["req"], inst_one["dur"])
     r = o.rollout(0, 0, oracle.POLICY_INJECTED, cap_steps=max(w["n_steps"], 1), record=False, inj_leader=w["leader"],
                   inj_action=w["action"], inj_nfol=w["nfol"], inj_followers=w["followers"])
     assert r["n_steps"] == w["n_steps"], ("the injected rollout took another number of decisions", r["n_steps"], w["n_steps"])
     return r
 
 
-def policy_walk(a, t, inst_one, seed, policy, mwt=10.0, switch=None, forced=None, stop=None):
+def policy_walk(a, t, inst_one, seed, policy, mwt=10.0, switch=None, forced=None, stop=None, max_time=MAX_TIME):
     """walk() under a base policy ("first", "nearest", "random"); forced = {d: action}: those decisions take that action instead."""
     forced = forced or {}
 
     def action_of(c):
         return forced[c.d] if c.d in forced else base_pick(policy, c.seed_of)(c.mask, c.pos, c.task_xy, c.d)
-    return walk(a, t, inst_one, seed, action_of, mwt, switch, stop)
+    return walk(a, t, inst_one, seed, action_of, mwt, switch, stop, max_time)
 
 
-def lookahead_values(a, t, inst_one, seed, d, policy="nearest", mwt=10.0):
+def lookahead_values(a, t, inst_one, seed, d, policy="nearest", mwt=10.0, max_time=MAX_TIME):
     """What Lookahead.values() returns for an env in front of decision d of its `policy` episode (the decisions before d taken by the
     policy): reward f64[t + 1], finished i32[t + 1], NaN / -1 where the mask in front of decision d forbids the action; and the mask.
     None when the episode has fewer than d + 1 decisions."""
-    head = policy_walk(a, t, inst_one, seed, policy, mwt, stop=d + 1)
+    head = policy_walk(a, t, inst_one, seed, policy, mwt, stop=d + 1, max_time=max_time)
     if head["n_steps"] <= d:
         return None
     mask = head["mask"][d]
     reward, finished = np.full(t + 1, np.nan), np.full(t + 1, -1, np.int32)
     for act in np.flatnonzero(mask == 0):
-        r = result(a, t, inst_one, policy_walk(a, t, inst_one, seed, policy, mwt, forced={d: int(act)}), mwt)
+        r = result(a, t, inst_one, policy_walk(a, t, inst_one, seed, policy, mwt, forced={d: int(act)}, max_time=max_time), mwt, max_time)
         reward[act], finished[act] = r["reward"], int(r["finished"].sum())
     return reward, finished, mask
 
 
-def routes_walk(a, t, inst_one, seed, route_task, mwt=10.0):
+def routes_walk(a, t, inst_one, seed, route_task, mwt=10.0, max_time=MAX_TIME):
     """walk() with every decision's action read from logged routes (route_task[a, cap], -1 = depot: the layout of enable_route_log):
     the leader's next entry -- every agent_step appends one to the route of the agent that takes it, in the oracle as in the log"""
-    return walk(a, t, inst_one, seed, lambda c: int(route_task[c.leader, len(c.o.route(c.leader)[0])]) + 1, mwt)
+    return walk(a, t, inst_one, seed, lambda c: int(route_task[c.leader, len(c.o.route(c.leader)[0])]) + 1, mwt, max_time=max_time)
 
 
 def pair(r):

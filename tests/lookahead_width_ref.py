@@ -24,7 +24,7 @@ def candidates(mask, pos, task_xy, width):
     return out
 
 
-def decide(a, t, inst_one, seed, policy, mwt, width, chosen, c):
+def decide(a, t, inst_one, seed, policy, mwt, width, chosen, c, max_time=LA.MAX_TIME):
     """Decision c.d under `lookahead, width`: (action, inner decisions, facts).  chosen: every earlier decision's action, forced in the
     inner walks.  An inner episode costs the decisions of its LA.policy_walk behind decision c.d: n_steps - d - 1.
     facts: n_unmasked, cand (the valued actions in the order they were valued; empty where nothing was), dist ({action: distance} of
@@ -41,8 +41,8 @@ def decide(a, t, inst_one, seed, policy, mwt, width, chosen, c):
     cand = tasks if (width == 0 or width >= len(tasks)) else candidates(c.mask, c.pos, c.task_xy, width)
     best, best_pair, inner = None, None, 0
     for act in cand:
-        w = LA.policy_walk(a, t, inst_one, seed, policy, mwt, forced={**chosen, c.d: act})
-        p = LA.pair(LA.result(a, t, inst_one, w, mwt))
+        w = LA.policy_walk(a, t, inst_one, seed, policy, mwt, forced={**chosen, c.d: act}, max_time=max_time)
+        p = LA.pair(LA.result(a, t, inst_one, w, mwt, max_time))
         inner += w["n_steps"] - c.d - 1
         f["pairs"][act] = p
         if best is None or p > best_pair or (p == best_pair and act < best):
@@ -51,7 +51,7 @@ def decide(a, t, inst_one, seed, policy, mwt, width, chosen, c):
     return best, inner, f
 
 
-def width_window(a, t, inst_one, seed, policy, mwt, width, d0=0, k=None):
+def width_window(a, t, inst_one, seed, policy, mwt, width, d0=0, k=None, max_time=LA.MAX_TIME):
     """LA.walk under the width-limited rule, built like LP.lookahead_window: decisions < d0 take the base policy's pick, decisions d0 ..
     d0 + k - 1 (k None: to the episode's end) the rule of decide().  Returns the walk's dict plus chosen {d: action}, facts (decide's,
     per window decision), inner (the inner decisions of the whole window), a and t."""
@@ -62,22 +62,22 @@ def width_window(a, t, inst_one, seed, policy, mwt, width, d0=0, k=None):
         if c.d < d0:
             chosen[c.d] = int(LA.base_pick(policy, c.seed_of)(c.mask, c.pos, c.task_xy, c.d))
             return chosen[c.d]
-        act, n, f = decide(a, t, inst_one, seed, policy, mwt, width, chosen, c)
+        act, n, f = decide(a, t, inst_one, seed, policy, mwt, width, chosen, c, max_time)
         chosen[c.d] = act
         inner[0] += n
         facts.append(f)
         return act
 
-    w = LA.walk(a, t, inst_one, seed, action_of, mwt, stop=None if k is None else d0 + k)
+    w = LA.walk(a, t, inst_one, seed, action_of, mwt, stop=None if k is None else d0 + k, max_time=max_time)
     return dict(w, chosen=chosen, facts=facts, inner=inner[0], a=a, t=t)
 
 
-def width_walk(a, t, inst_one, seed, policy, width, mwt=10.0):
+def width_walk(a, t, inst_one, seed, policy, width, mwt=10.0, max_time=LA.MAX_TIME):
     """A whole episode under the width-limited rule: LP.lookahead_walk's dict (result, o: the OracleEnv of the oracle's replay, flags,
     a) plus inner and facts."""
-    w = width_window(a, t, inst_one, seed, policy, mwt, width)
+    w = width_window(a, t, inst_one, seed, policy, mwt, width, max_time=max_time)
     assert w["ended"]
-    o, r, flags = LP.replay(a, t, inst_one, w, mwt)
+    o, r, flags = LP.replay(a, t, inst_one, w, mwt, max_time)
     return dict(w, result=r, o=o, flags=flags)
 
 

@@ -15,7 +15,7 @@ def one(inst, b, t=None):
     return dict(depot=inst["depot"][b], task_xy=inst["task_xy"][b, :t], req=inst["req"][b, :t], dur=inst["dur"][b, :t])
 
 
-def episodes(a, t, inst_one, seed, policy, n, mwt=10.0, record=False, d0=0):
+def episodes(a, t, inst_one, seed, policy, n, mwt=10.0, record=False, d0=0, max_time=100.0):
     """n consecutive oracle episodes of one env, the decision counter running on across them from d0.  inst_one: the env's instance, or
     a callable k -> the instance of episode k; where that returns (A_k, instance), episode k has that instance's own sizes."""
     import oracle
@@ -27,22 +27,22 @@ def episodes(a, t, inst_one, seed, policy, n, mwt=10.0, record=False, d0=0):
         if isinstance(i, tuple):
             ak, i = i
             tk = i["req"].shape[0]
-        r = oracle.OracleEnv(ak, tk, max_waiting_time=mwt).load(i["depot"], i["task_xy"], i["req"], i["dur"]) \
+        r = oracle.OracleEnv(ak, tk, max_waiting_time=mwt, max_time=max_time).load(i["depot"], i["task_xy"], i["req"], i["dur"]) \
             .rollout(int(seed), d0, opol(policy), cap_steps=20000, record=record)
         out.append(r)
         d0 += r["n_steps"]
     return out
 
 
-def episodes_first_recorded(a, t, inst_one, seed, policy, n, mwt=10.0):
+def episodes_first_recorded(a, t, inst_one, seed, policy, n, mwt=10.0, max_time=100.0):
     """episodes() on one instance with the first episode's decisions recorded and the later ones' not."""
-    first = episodes(a, t, inst_one, seed, policy, 1, mwt, record=True)
-    return first + episodes(a, t, inst_one, seed, policy, n - 1, mwt, d0=first[0]["n_steps"])
+    first = episodes(a, t, inst_one, seed, policy, 1, mwt, record=True, max_time=max_time)
+    return first + episodes(a, t, inst_one, seed, policy, n - 1, mwt, d0=first[0]["n_steps"], max_time=max_time)
 
 
-def two_episodes(inst, seeds, a, t, mwt=10.0):
+def two_episodes(inst, seeds, a, t, mwt=10.0, max_time=100.0):
     """(first-episode traces, second-episode results) of every env of a batch under the random policy, at the envs' sizes (a, t)."""
-    eps = [episodes_first_recorded(a, t, one(inst, b, t), seeds[b], "random", 2, mwt) for b in range(len(seeds))]
+    eps = [episodes_first_recorded(a, t, one(inst, b, t), seeds[b], "random", 2, mwt, max_time) for b in range(len(seeds))]
     return [e[0] for e in eps], [e[1] for e in eps]
 
 
@@ -57,12 +57,12 @@ def assert_summary(sm, ref, name):
         assert sm[2 + i] == ref["metrics"][i], f"{name}: metric {i} {sm[2 + i]!r} != {ref['metrics'][i]!r}"
 
 
-def play(a, t, one, seed, d0, policy, cap, mwt):
+def play(a, t, one, seed, d0, policy, cap, mwt, max_time=100.0):
     """One oracle episode of at most `cap` decisions (None: to its end) from decision counter d0.  Returns (the OracleEnv, whose
     route() lists are those of the decisions taken; decisions taken; whether the episode ended).  The raw return value tells a cap
     that cut the episode (-1) from an episode of exactly `cap` decisions."""
     import oracle
-    o = oracle.OracleEnv(a, t, max_waiting_time=mwt).load(one["depot"], one["task_xy"], one["req"], one["dur"])
+    o = oracle.OracleEnv(a, t, max_waiting_time=mwt, max_time=max_time).load(one["depot"], one["task_xy"], one["req"], one["dur"])
     n = oracle.lib().orc_rollout(o._h, C.c_uint64(int(seed)), C.c_uint64(int(d0)), opol(policy), 1 << 40 if cap is None else int(cap),
                                  *([None] * 12))
     return (o, int(cap), False) if n < 0 else (o, int(n), True)
@@ -74,8 +74,8 @@ class Sim:
     restart -- unless its budget is spent, and a spent budget stops it where it is.  `.o` is the OracleEnv of the episode the log
     should hold."""
 
-    def __init__(self, a, t, inst_of, seed, policy, mwt=10.0):
-        self.a, self.t, self.inst_of, self.seed, self.policy, self.mwt = a, t, inst_of, seed, policy, mwt
+    def __init__(self, a, t, inst_of, seed, policy, mwt=10.0, max_time=100.0):
+        self.a, self.t, self.inst_of, self.seed, self.policy, self.mwt, self.max_time = a, t, inst_of, seed, policy, mwt, max_time
         self.j, self.d0, self.k, self.done, self.o = 0, 0, 0, False, None
 
     def launch(self, episodes, budget):
@@ -91,7 +91,7 @@ class Sim:
             elif left == 0:
                 break
             o, k, ended = play(self.a, self.t, self.inst_of(self.j), self.seed, self.d0, self.policy,
-                               None if left is None else self.k + left, self.mwt)
+                               None if left is None else self.k + left, self.mwt, self.max_time)
             taken += k - self.k
             if left is not None:
                 left -= k - self.k

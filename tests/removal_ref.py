@@ -10,7 +10,7 @@ MAX_TIME = 100.0
 TASK_KEYS = ("n_members", "n_abandoned", "feasible", "finished", "time_start", "time_finish")
 
 
-def walk_episode(o, req, seed_e):
+def walk_episode(o, req, seed_e, max_time=MAX_TIME):
     """One episode of the oracle through its step-wise API (the loop of worker.py:45-87 restated).  Returns (snaps, removals): the
     state in front of every decision, and one entry (task, rule, members before, positions that left) per task and task_update call
     that removed somebody."""
@@ -37,7 +37,7 @@ def walk_episode(o, req, seed_e):
         state.update(f)
 
     finished, d, empty = False, 0, 0
-    while not finished and o.now < MAX_TIME:                               # worker.py:45
+    while not finished and o.now < max_time:                               # worker.py:45
         ids, t = o.next_decision()                                         # :47
         groups = o.get_unique_group(ids) if len(ids) else []              # :48
         o.now = t                                                          # :49
@@ -152,7 +152,7 @@ def read_batch(env, obs=None):
                 obs=tuple(x.cpu().numpy() for x in (o.agents, o.tasks, o.mask, o.leader, o.active)))
 
 
-def assert_handover(tag, got, b, d, snaps, lists, a, t, inst_one, seed, mwt):
+def assert_handover(tag, got, b, d, snaps, lists, a, t, inst_one, seed, mwt, max_time=MAX_TIME):
     """Env b of a handle (got: read_batch) against the walk's snapshot in front of decision d (snaps: the env's list; d == len(snaps): the
     episode is over): leader, now, the decision counter and the active bit; assert_state, with nothing in the rows beyond the env's own
     sizes; assert_obs; and the agent side against the oracle's own episode stopped in front of that decision."""
@@ -170,7 +170,7 @@ def assert_handover(tag, got, b, d, snaps, lists, a, t, inst_one, seed, mwt):
         assert_obs(tag, s, a, t, ag[b], tk[b], mk[b])
     # dcm_get_agents / dcm_get_tasks compute the waiting sums on read, at the state the env is in; the oracle computes them when an episode
     # ends (env/task_env.py:344-364, :421), so an episode that the cap stopped is given that one call here -- it changes nothing else
-    o, _, ended = O.play(a, t, inst_one, seed, 0, "random", d, mwt)
+    o, _, ended = O.play(a, t, inst_one, seed, 0, "random", d, mwt, max_time)
     if not ended:
         import oracle
         oracle.lib().orc_finish_episode(o._h)

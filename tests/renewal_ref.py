@@ -27,12 +27,12 @@ def host_instance(ar, tr, seed, mcs):
 
 
 @functools.lru_cache(maxsize=None)
-def oracle_chain(ar, tr, inst_seed, stride, choice_seed, mcs=5, n=EPISODES, indices=None):
+def oracle_chain(ar, tr, inst_seed, stride, choice_seed, mcs=5, n=EPISODES, indices=None, policy="random", mwt=10.0, max_time=100.0):
     """Episodes 0..n-1 of one env under renewal: (rollout results, (A_k, instance) per episode), computed once per env and shared.
     indices: episode k plays the instance of index indices[k] instead of k (an env whose renewal was turned off on the way)."""
     from dcmrta_amd.instances import renewal_seeds
     insts = [host_instance(ar, tr, int(renewal_seeds(inst_seed, k, stride)), mcs) for k in (range(n) if indices is None else indices)]
-    eps = [dict(n_steps=r["n_steps"], row=O.summary_row(r)) for r in O.episodes(None, None, insts.__getitem__, choice_seed, "random", len(insts))]
+    eps = [dict(n_steps=r["n_steps"], row=O.summary_row(r)) for r in O.episodes(None, None, insts.__getitem__, choice_seed, policy, len(insts), mwt, max_time=max_time)]
     return eps, insts
 
 
