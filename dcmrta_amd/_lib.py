@@ -18,6 +18,7 @@ MAX_MEMBERS_WIDE = 16    # DCM_PARAM_WIDE_MEMBERS handles
 PARAM_NO_GROUPING, PARAM_AUTO_RESET, PARAM_STRICT_MASK, PARAM_WIDE_MEMBERS = 1, 2, 4, 8
 PARAM_RENEW_SIZES = 16    # set_instance_renewal also on a ragged generated batch: the sizes are renewed with the instances
 POLICY_RANDOM, POLICY_FIRST, POLICY_NEAREST = 0, 1, 2    # dcm_rollout_policy
+KERNEL_ROLLOUT, KERNEL_STEP = 0, 1    # dcm_kernel_name
 MAX_AGENTS = 128
 MAX_TASKS = 1023
 
@@ -42,6 +43,7 @@ SIGNATURES = {
     "dcm_last_error": (C.c_char_p, []),
     "dcm_abi_version": (C.c_int, []),
     "dcm_build_id": (C.c_char_p, []),
+    "dcm_kernel_name": (C.c_char_p, [_vp, _i32]),   # env, entry (KERNEL_ROLLOUT / KERNEL_STEP)
     "dcm_create": (C.c_int, [C.POINTER(DcmParams), C.POINTER(_vp)]),
     "dcm_destroy": (C.c_int, [_vp]),
     "dcm_load_instances": (C.c_int, [_vp] * 6),

@@ -154,6 +154,7 @@ class BatchedTaskEnv:
             raise DcmError("instance arrays have the wrong shape")
         if (n_tasks is None) != (self.n_tasks is None):
             self.graph_epoch += 1
+        kernels = self._kernel_names()
         with torch.cuda.device(self.device):
             if n_tasks is None:
                 check(self._lib.dcm_load_instances(self._h, _ptr(d), _ptr(xy), _ptr(rq), _ptr(du), self._stream()))
@@ -164,7 +165,29 @@ class BatchedTaskEnv:
                                                           self._stream()))
                 self.n_agents, self.n_tasks = na.copy(), nt.copy()
         self._instances = (d, xy, rq, du)  # keep alive until the kernel ran
+        self._kernels_since(kernels)
         return self
+
+    # ------------------------------------------------------------------ which kernels (dcm_kernel_name)
+    def kernel_name(self, entry="rollout"):
+        """The kernel a plain launch takes as things stand: entry "rollout" = rollout_random with all observation buffers or none,
+        "step" = step() without overrides.  A loaded batch in which two points of an env are closer than some 1e-116 without
+        coinciding runs the general kernels ("k_rollout_random", "k_step") instead of the register-resident ones: same results."""
+        which = {"rollout": _lib.KERNEL_ROLLOUT, "step": _lib.KERNEL_STEP}.get(entry)
+        if which is None:
+            raise DcmError('kernel_name: entry is "rollout" or "step"')
+        name = self._lib.dcm_kernel_name(self._h, which)
+        if name is None:
+            check(-1)
+        return name.decode()
+
+    def _kernel_names(self):
+        return self.kernel_name("rollout"), self.kernel_name("step")
+
+    def _kernels_since(self, before):
+        # a captured dcm_step has its kernel baked in: new instances that change the family end the graphs' epoch
+        if self._kernel_names() != before:
+            self.graph_epoch += 1
 
     @staticmethod
     def _range(r, dim):
@@ -195,6 +218,7 @@ class BatchedTaskEnv:
         # the library's own rule (dcm_generate_instances), from lo alone: it rejects lo > hi and hi > dim before anything changes, so
         # lo == dim leaves hi == dim, and where it rejects, check() raises before `ragged` is used
         ragged = not (a_lo == self.A and t_lo == self.T)
+        kernels = self._kernel_names()
         with torch.cuda.device(self.device):
             check(self._lib.dcm_generate_instances(self._h, _ptr(s), a_lo, a_hi, t_lo, t_hi, int(max_coalition_size),
                                                    float(max_duration), self._stream()))
@@ -208,6 +232,7 @@ class BatchedTaskEnv:
             else:
                 self.n_agents = self.n_tasks = None
         self._instances = (s,)  # keep alive until the kernel ran
+        self._kernels_since(kernels)
         return self
 
     def set_instance_renewal(self, stride):
@@ -690,8 +715,10 @@ class BatchedTaskEnv:
         if buf.numel() * buf.element_size() != n.value:
             raise DcmError(f"restore_state: the snapshot holds {buf.numel() * buf.element_size()} bytes, this env's state is {n.value} "
                            "(taken from another env, or before the batch changed between uniform and ragged)")
+        kernels = self._kernel_names()
         with torch.cuda.device(self.device):
             check(self._lib.dcm_restore_state(self._h, _ptr(buf), self._stream()))
+        self._kernels_since(kernels)
 
     # ------------------------------------------------------------------ per-env copy (dcm_fork_envs)
     def fork_from(self, src, index, seeds=None, check=False):
@@ -730,8 +757,10 @@ class BatchedTaskEnv:
         if seeds is not None:
             s = seeds.to(self.device).contiguous() if isinstance(seeds, torch.Tensor) else torch.from_numpy(seeds.view(np.int64)).to(self.device)
         ok = torch.empty((self.B,), dtype=torch.uint8, device=self.device) if check else None
+        kernels = self._kernel_names()
         with torch.cuda.device(self.device):
             _lib.check(self._lib.dcm_fork_envs(self._h, src._h, _ptr(idx), _ptr(s), _ptr(ok), self._stream()))
+        self._kernels_since(kernels)
         self._fork_args = (idx, s)      # keep alive until the kernel ran
         if check:
             bad = torch.nonzero(ok == 0).flatten().cpu().numpy()

@@ -444,6 +444,30 @@ __device__ __forceinline__ double dist2(double ax, double ay, double bx, double 
     const double dx = ax - bx, dy = ay - by;
     return sqrt(__builtin_fma(dy, dy, dx * dx));
 }
+// The same distance for squares that are 0 or >= 2^-767 (DIST2_INRANGE_MIN) -- what a handle's instances must satisfy to run the
+// Fast<> kernels at all (plan::Shape::inrange; k_points_inrange below is the load-time check).  sqrt() of an f64 compiles to
+// v_rsq_f64 and two Newton steps, wrapped in range scaling for arguments below 2^-767 (compare, two selects, ldexp by 256 in front,
+// ldexp by -128 behind): five VALU on the dependent chain of every decision that do nothing for such an argument -- ldexp by 0 is the
+// identity.  This is that sequence, operation for operation, without the five; the select that passes +-0 and +inf through stays.
+// Bit-equal to sqrt() on the whole range (tests/test_gpu_sqrt_inrange.py).  Fast<> alone uses it: apply, and the greedy pick of
+// decide_policy / decide_logged (with sqrt() there those forms hold both sequences' constants: a VGPR more than they had).
+constexpr double DIST2_INRANGE_MIN = 0x1p-767;
+__device__ __forceinline__ double dist2_inrange(double ax, double ay, double bx, double by) {
+    const double dx = ax - bx, dy = ay - by;
+    const double x = __builtin_fma(dy, dy, dx * dx);
+    const double y = __builtin_amdgcn_rsq(x);
+    double g = x * y, h = y * 0.5;
+    const double e = __builtin_fma(-h, g, 0.5);
+    g = __builtin_fma(g, e, g);
+    h = __builtin_fma(h, e, h);
+    g = __builtin_fma(__builtin_fma(-g, g, x), h, g);
+    g = __builtin_fma(__builtin_fma(-g, g, x), h, g);
+    // -0, +0, +inf pass through.  (The class mask on the scalar unit: left to itself the compiler keeps it in a VGPR for the whole
+    //  kernel, the e32 encoding's second operand.)
+    int zero_or_inf = 0x260;
+    asm("" : "+s"(zero_or_inf));
+    return __builtin_amdgcn_class(x, zero_or_inf) ? x : g;
+}
 // travel_time = distance / velocity with velocity 0.2 (env/task_env.py:99,315).  The IEEE quotient d / 0.2 costs an
 // 11-instruction v_div_scale / v_rcp_f64 / v_div_fmas sequence; Markstein's division by a constant gives the same
 // correctly rounded result in three: 5.0 = RN(1/0.2) (1/0.2 = 5 - 2.8e-16, half an ulp below 5 is 4.4e-16),
@@ -566,6 +590,10 @@ struct dcm_env {
     double* summary = nullptr;       // [B][8]
     uint16_t* ablog = nullptr;       // [B][A][AB_CAP] abandonment log (side table of the state)
     bool loaded = false, reset_done = false;
+    // plan::Shape::inrange of the instances the records hold: true for a generated batch, k_points_inrange's answer for a loaded or
+    // restored one, both handles' for the target of dcm_fork_envs (inrange_bad: the kernel's device word, allocated at its first run)
+    bool inrange = true;
+    uint32_t* inrange_bad = nullptr;
     // instance renewal (dcm_set_instance_renewal): what dcm_generate_instances was last called with.  `generated` while the records'
     // instances came from it; renew_stride != 0 while renewal is on (only ever with generated, and with !sizes unless the handle has
     // DCM_PARAM_RENEW_SIZES: the kernels then rewrite `sizes` at restarts)

@@ -1569,6 +1569,33 @@ __global__ __launch_bounds__(WAVE) void k_load_instances(int A, int T, int PA, i
     }
 }
 
+#ifndef DCM_DEVICE_ONLY_TU   // the host API's unit only
+// The load-time check behind plan::Shape::inrange: does any env hold two of its T_e + 1 points (the depot, then its tasks) whose squared
+// distance -- formed as dist2 forms it; the square of a negated difference is the same number -- lies strictly between 0 and
+// DIST2_INRANGE_MIN?  Such a square is the only argument on which dist2_inrange differs from dist2 (NaN and inf pass through both
+// alike).  Sets *bad; one wave per env over the i < j pairs of its own record.
+__global__ __launch_bounds__(WAVE) void k_points_inrange(int A, int T, int PA, int PT, int PC, const unsigned char* state, const int32_t* sizes,
+                                                        uint32_t* bad) {
+    const int e = blockIdx.x, lane = threadIdx.x;
+    int eA, eT;
+    env_dims<0, 0, false>(sizes, e, A, T, eA, eT);
+    const Lay L{PA, PT, PC};
+    const unsigned char* rec = state + (size_t)e * L.rec_bytes();
+    const double *tx = (const double*)(rec + L.tx()), *ty = (const double*)(rec + L.ty());
+    const Hdr* h = (const Hdr*)rec;
+    bool out = false;
+    for (int j = lane; j < eT; j += WAVE) {                  // point j + 1 = task j against the depot and the tasks below it
+        const double bx = tx[j], by = ty[j];
+        for (int i = -1; i < j; i++) {
+            const double dx = (i < 0 ? h->depot_x : tx[i]) - bx, dy = (i < 0 ? h->depot_y : ty[i]) - by;
+            const double q = __builtin_fma(dy, dy, dx * dx);
+            out = out || (q > 0.0 && q < DIST2_INRANGE_MIN);
+        }
+    }
+    if (__any(out) && lane == 0) atomicOr(bad, 1u);
+}
+#endif
+
 // dynamic LDS of a k_reset / k_observe / k_step launch: the record image (MC moves no section of it)
 template <int CA, int CT, bool RS>
 constexpr uint32_t env_kernel_lds_bytes(Lay L) { return Sim<CA, CT, RS>::lds_image_bytes(L); }
@@ -1886,7 +1913,7 @@ auto with_bool(bool b, F&& f) { return b ? f(std::true_type{}) : f(std::false_ty
 #define DIMS(env) (env)->A, (env)->T, (env)->L.A, (env)->L.T
 
 // what plan.hpp reads of a handle
-plan::Shape shape_of(const dcm_env* env) { return {env->A, env->T, env->sizes != nullptr, env->L.C > M, env->kp.mwt > 0.0}; }
+plan::Shape shape_of(const dcm_env* env) { return {env->A, env->T, env->sizes != nullptr, env->L.C > M, env->kp.mwt > 0.0, env->inrange}; }
 plan::SimKind sim_of(const dcm_env* env) { return plan::sim_kind(shape_of(env)); }
 
 // dcm_create / dcm_destroy run on the handle's device but leave the caller's current device as they found it
@@ -2101,6 +2128,27 @@ plan::RenewForm renewing_launch(dcm_env* env, void* stream) {
 // the handle's instances no longer come from dcm_generate_instances, or come from a new call of it: renewal is off
 void renewal_off(dcm_env* env, bool generated) { env->generated = generated; env->renew_stride = 0; }
 
+// plan::Shape::inrange of the records as they stand, for instances that were not made on the device: one small kernel over the
+// records and one word read back, so the call waits for the stream -- where instances are loaded or a state is restored, never at a
+// launch.  Only a handle whose shape could take the Fast<> kernels at all is looked at.  Under stream capture nothing can be read
+// back: the handle then takes the general kernels until its instances are next loaded, generated or restored.
+int check_points_inrange(dcm_env* env, void* stream) {
+    env->inrange = true;
+    if (!plan::one_chunk_ok(shape_of(env))) return DCM_OK;
+    env->inrange = false;
+    if (stream_capturing(stream)) return DCM_OK;
+    if (!env->inrange_bad) HIP_TRY(hipMalloc((void**)&env->inrange_bad, sizeof(uint32_t)));
+    HIP_TRY(hipMemsetAsync(env->inrange_bad, 0, sizeof(uint32_t), (hipStream_t)stream));
+    hipLaunchKernelGGL(k_points_inrange, GRID(env), 0, (hipStream_t)stream, DIMS(env), env->L.C, (const unsigned char*)env->state,
+                       (const int32_t*)env->sizes, env->inrange_bad);
+    LAUNCH_OK();
+    uint32_t bad = 1;
+    HIP_TRY(hipMemcpyAsync(&bad, env->inrange_bad, sizeof(uint32_t), hipMemcpyDeviceToHost, (hipStream_t)stream));
+    HIP_TRY(hipStreamSynchronize((hipStream_t)stream));
+    env->inrange = bad == 0;
+    return DCM_OK;
+}
+
 // the common tail of dcm_load_instances / dcm_load_instances_ragged (env->sizes: the per-env sizes of a ragged batch, or nullptr)
 int launch_load(dcm_env* env, const double* depot, const double* task_xy, const int32_t* req, const double* dur, void* stream) {
     hipLaunchKernelGGL(k_load_instances, GRID(env), 0, (hipStream_t)stream, DIMS(env), env->L.C, env->state, depot, task_xy,
@@ -2109,7 +2157,7 @@ int launch_load(dcm_env* env, const double* depot, const double* task_xy, const 
     env->loaded = true;
     env->reset_done = false;
     renewal_off(env, false);
-    return DCM_OK;
+    return check_points_inrange(env, stream);
 }
 
 // dcm_env_status / dcm_env_episodes: header fields of every env (layout dims: only the record pitch matters)
@@ -2244,6 +2292,19 @@ int dcm_abi_version(void) { return DCM_ABI_VERSION; }
 #define DCM_BUILD_ID "unknown"
 #endif
 const char* dcm_build_id(void) { return DCM_BUILD_ID; }
+// plan.hpp's answer for the handle as it stands, by the kernel's base name
+const char* dcm_kernel_name(dcm_env* env, int32_t entry) {
+    if (!env) { (void)dcm::fail(DCM_ERR_INVALID, "null env handle"); return nullptr; }
+    const plan::Shape shape = shape_of(env);
+    if (entry == DCM_KERNEL_STEP) return plan::one_chunk_ok(shape) ? "k_step_fast" : "k_step";
+    if (entry != DCM_KERNEL_ROLLOUT) { (void)dcm::fail(DCM_ERR_INVALID, "dcm_kernel_name: unknown entry"); return nullptr; }
+    switch (plan::rollout_kind(shape, true)) {
+    case plan::Rollout::Fast: return "k_rollout_fast";
+    case plan::Rollout::FastMc: return "k_rollout_fast_mc";
+    case plan::Rollout::FastG: return "k_rollout_fast_g";
+    default: return "k_rollout_random";
+    }
+}
 #ifdef DCM_COUNT_PATHS
 // developer build only (tools/path_counts.py): read and clear the dynamic path counts of the register-resident rollout kernel
 int dcm_debug_path_counts(unsigned long long* out32) {
@@ -2342,7 +2403,7 @@ int dcm_destroy(dcm_env* env) {
     if (!env) return DCM_OK;
     DeviceGuard guard(env->p.device);
     void* const owned[] = {env->state, env->summary, env->ablog, env->gscratch, env->routes, env->route_len,
-                           env->rmarr, env->sizes, env->side, env->pendq, env->init, env->inst_seeds, env->la_snap};
+                           env->rmarr, env->sizes, env->side, env->pendq, env->init, env->inst_seeds, env->la_snap, env->inrange_bad};
     for (void* p : owned)
         if (p) (void)hipFree(p);
     delete env;
@@ -2405,6 +2466,7 @@ int dcm_generate_instances(dcm_env* env, const uint64_t* inst_seeds, int32_t age
     env->loaded = true;
     env->reset_done = false;
     env->gen = g;
+    env->inrange = true;              // coordinates are multiples of 2^-53 (plan::Shape::inrange), renewed instances included
     renewal_off(env, true);
     return DCM_OK;
 }
@@ -2696,6 +2758,7 @@ int dcm_fork_envs(dcm_env* dst, dcm_env* src, const int32_t* src_index, const ui
     LAUNCH_OK();
     dst->init_valid = false;          // the restart image of k_step_fast belongs to the old instances
     renewal_off(dst, false);          // the records no longer match dst's inst_seeds: not a generated batch any more
+    dst->inrange = dst->inrange && src->inrange;   // dst now holds instances of both (src_index -1 keeps its own)
     return DCM_OK;
 }
 
@@ -2893,7 +2956,7 @@ int dcm_restore_state(dcm_env* env, const void* src, void* stream) {
     env->loaded = true;
     env->reset_done = true;
     env->init_valid = false;          // (the restored records may belong to other instances)
-    return DCM_OK;
+    return check_points_inrange(env, stream);
 }
 
 int dcm_distance(const double* ax, const double* ay, const double* bx, const double* by, double* dist_out, double* time_out,

@@ -180,7 +180,8 @@ __global__ __launch_bounds__(WAVE, 4) void KNAME(int A, int T, int PA, int PT, K
             for (;;) {
                 FPHK(f, 12);
                 CNT(0);
-                const uint64_t k1 = rl(kv, ki), k2 = rl(kv2, ki);
+                const uint64_t k1 = rl(kv, ki);
+                const Key2 k2{kv2, ki};                  // (the second key is read where the follower draws are: Fast<>::apply)
 #ifdef KEXPLORES
                 // the decision explores iff its explore word < explore_q32: then the random policy's action (protocol slot 1), else the base pick
                 const bool explores = x_all || rl(xv, ki) < x_q;

@@ -14,7 +14,11 @@ constexpr int LANES = 64;   // one wavefront per env: a lane chunk of agents or 
 // max_waiting_time > 0.  The register-resident kernels skip the task_update pass of a QUIET join on the ground that a member who
 // has just joined has not waited max_waiting_time yet (env/task_env.py:269), which needs max_waiting_time > 0 (the reference's
 // 10 / 100): a handle with max_waiting_time <= 0 (or NaN) takes the general kernels, which evaluate the rule literally.
-struct Shape { int A, T; bool ragged, wide, quiet; };
+// inrange: every env's squared distance between any two of its T + 1 points (the depot and its tasks; fma(dy, dy, dx * dx) as dist2
+// forms it) is 0 or >= 2^-767.  Fast<>::apply takes the square root without the range scaling that smaller arguments need
+// (common.hpp, dist2_inrange): a handle that holds a smaller square takes the general kernels.  True by construction for instances
+// made on the device (coordinates are multiples of 2^-53), checked on the device for loaded ones (dcmrta_env.hip, k_points_inrange).
+struct Shape { int A, T; bool ragged, wide, quiet; bool inrange = true; };
 
 // Record layout dims: Lay{20,50} for every shape inside the reference's training range A <= 20, T <= 50 (parameters.py:15-16),
 // Lay{64,64} for the other shapes with one lane per agent / task, so that those shapes share constant-offset kernel instantiations;
@@ -44,7 +48,8 @@ inline SimKind sim_kind(const Shape& s) {
 
 // The one-chunk register-resident kernels (k_step_fast, k_terminal_flush, k_rollout_fast) need one lane per agent and per task,
 // with lane 63 free for the depot; sim_kind is then one of the first three.  (dcm_step adds its call-shape conditions.)
-inline bool one_chunk_ok(const Shape& s) { return s.quiet && !s.wide && s.A <= LANES && s.T <= LANES - 1; }
+// They are the kernels of Fast<>, persistent and lockstep: in-range distances only (Shape::inrange).
+inline bool one_chunk_ok(const Shape& s) { return s.quiet && s.inrange && !s.wide && s.A <= LANES && s.T <= LANES - 1; }
 
 // Instance renewal (dcm_set_instance_renewal with a non-zero stride): the handle's instances must have come from
 // dcm_generate_instances (`generated`: the handle then holds the seeds and scalar arguments the next instances are drawn from), and the

@@ -43,6 +43,13 @@ struct FastLog {
     int32_t len;      // lane-owned: entries appended to this lane's agent in the env's current episode (may exceed cap)
 };
 
+// The second keys of the persistent kernels' decisions live one per lane beside the first ones (k_rollout_fast.inc: kv2, ki).  Only a
+// decision with follower draws needs its own, so apply() fetches it (two v_readlane) inside that branch and not at the loop's top.
+struct Key2 {
+    uint64_t kv2;     // lane-owned: the second key of the decision whose first key this lane holds
+    int ki;           // wave-uniform: the lane of the current decision
+};
+
 // TRK (lockstep kernel): the fast path records which task sections of the record it has changed (Sim::DIRTY_* bits), so that
 // the write-back can skip the others
 template <int CA, int CT, bool RS, bool OBS, bool TRK = false>
@@ -249,18 +256,26 @@ struct Fast {
                 const int t = __ffsll((unsigned long long)todo) - 1;
                 todo &= todo - 1ull;
                 const uint64_t g = rl(gone, t);
-                if (lane_of(g)) {                                                // this lane's agent was dropped by task t
-                    const uint32_t nth_ = r.ai >> 16;
-                    r.ai += 1u << 16;
-                    // (Both side tables live in HBM.  The LDS image keeps generic pointers to them, so the compiler emitted FLAT
-                    //  instructions, which count on lgkmcnt as well as vmcnt: the next lgkmcnt(0) also waited for this store.  With
-                    //  the cast to the global address space they are global_store_short / global_atomic_add.)
-                    if (nth_ < (uint32_t)AB_CAP) ((__attribute__((address_space(1))) uint16_t*)r.ab)[nth_] = (uint16_t)t;
-                    else {
+                // the dropped agents whose log still has room: the count (bits 16-31 of ainfo) below AB_CAP, one compare of the word
+                const uint64_t room = g & __ballot(r.ai < ((uint32_t)AB_CAP << 16));
+                const uint32_t nth_ = r.ai >> 16;
+                // (Both side tables live in HBM.  The LDS image keeps generic pointers to them, so the compiler emitted FLAT
+                //  instructions, which count on lgkmcnt as well as vmcnt: the next lgkmcnt(0) also waited for this store.  With
+                //  the cast to the global address space they are global_store_short / global_atomic_add.)
+                // The store is the one arm under the lanes' own predicate; an agent past AB_CAP abandonments in one episode is the rare
+                // case and sits behind ONE wave-uniform test (as an if / else per lane the two arms cost every trip two exec saves, an
+                // exec flip, two branches and the load of the count table's pointer).
+                if (lane_of(room)) ((__attribute__((address_space(1))) uint16_t*)r.ab)[nth_] = (uint16_t)t;
+                const uint64_t over = g & ~room;
+                if (over) {
+                    if (lane_of(over)) {
                         const uint32_t ci = (uint32_t)(la * S.T() + t);
                         __hip_atomic_fetch_add((__attribute__((address_space(1))) uint32_t*)S.abcnt() + (ci >> 1), 1u << (16 * (ci & 1)),
                                                __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
                     }
+                }
+                if (lane_of(g)) {                                                // this lane's agent was dropped by task t
+                    r.ai += 1u << 16;
                     if (r.cur == t) r.ai &= ~A_MEMBER;                           // no longer `agent in current_task['members']` :230
                 }
             } while (todo);
@@ -270,6 +285,10 @@ struct Fast {
         const uint32_t info_f = info | ((now >= tfin) ? T_FIN : 0u);             // :273-274
         info = feas0 ? info_f : info_i;
         r.ti = info;
+        // (The guard stays.  Tried: the lanes that own no task write through a pointer of their own to a dead word, task 0's id word --
+        //  the loop 4 instructions shorter, but the pointer is a second address register beside 4 * lt, which reload() keeps: 108 VGPRs
+        //  for 106.  And time_start / time_finish below leave in ONE ds_write2_b64 off ONE address register, 8 CT bytes apart, while
+        //  the id section is 8 CT bytes long: no two dead words lie that far apart.  profiles/HISTORY.md, last section.)
         if (inT) S.tinfo()[lt] = info;
         uint64_t over_already = 0ull;                                            // the tasks that became feasible and are over at `now`
         if (bec) {
@@ -360,10 +379,10 @@ struct Fast {
         h.flags |= bad & (uint32_t)(DCM_FLAG_BAD_LEADER | DCM_FLAG_DONE);
         return nth(gm, below((uint32_t)(k1 >> 32), glen + (int)(bad & 1u)));
     }
-    // k2p: the decision's second key mix64(k1 + GAMMA) (the first two follower draws) if the caller has it, else nullptr
+    // k2p: where the decision's second key mix64(k1 + GAMMA) (the first two follower draws) is, if the caller has it, else nullptr
     // nvp: receives the number of unmasked tasks the decision saw (the launch's wave-priority estimate of the work left)
     __device__ __forceinline__ int decide(R& r, HdrRegs& h, const KP& P, int lane, uint64_t k1, float* agrow, float* tkrow, uint8_t* mkp,
-                                          const uint64_t* k2p = nullptr, int* nvp = nullptr) const {
+                                          const Key2* k2p = nullptr, int* nvp = nullptr) const {
         uint64_t gm;
         // (no early return: an exit from the middle of a decision would keep the whole register set of the agent / task state alive
         //  in a second copy -- 15 v_mov per decision at the loop latch.  An empty group is unreachable; if it ever happened the env
@@ -389,7 +408,7 @@ struct Fast {
     // is the NaN-ignoring wave minimum of the ROUNDED distances (masked lanes hold NaN) and a ballot of the lanes equal to it, whose
     // lowest bit is the lowest task index: strict < in the oracle's policy_pick.  No unmasked task: the depot.
     __device__ __forceinline__ int decide_policy(R& r, HdrRegs& h, const KP& P, int lane, uint64_t k1, float* agrow, float* tkrow, uint8_t* mkp,
-                                                 const uint64_t* k2p, int policy) const {
+                                                 const Key2* k2p, int policy) const {
         uint64_t gm;
         const int leader = pick_leader_flagged(r, h, k1, gm);
         FPH(0);
@@ -398,7 +417,7 @@ struct Fast {
         uint64_t pick = bm;
         if (policy == DCM_POLICY_NEAREST) {
             const double lx = rl(r.ax, leader), ly = rl(r.ay, leader);
-            const double dd = dist2(lx, ly, r.tx, r.ty);
+            const double dd = dist2_inrange(lx, ly, r.tx, r.ty);
             const bool open = lane_of(bm);
             const double m = wave_nanmin_n<CT>(open ? dd : __builtin_nan(""));
             pick = bm & __ballot(dd == m);
@@ -411,7 +430,7 @@ struct Fast {
     // first -- decide()'s draw or decide_policy()'s pick -- and ONE apply follows, the logging one (a branch between decide and
     // decide_policy would inline apply twice into the loop).
     __device__ __forceinline__ int decide_logged(R& r, HdrRegs& h, const KP& P, int lane, uint64_t k1, float* agrow, float* tkrow, uint8_t* mkp,
-                                                 const uint64_t* k2p, int policy, FastLog& lg) const {
+                                                 const Key2* k2p, int policy, FastLog& lg) const {
         uint64_t gm;
         const int leader = pick_leader_flagged(r, h, k1, gm);
         FPH(0);
@@ -426,7 +445,7 @@ struct Fast {
         uint64_t pick = bm;
         if (policy == DCM_POLICY_NEAREST) {
             const double lx = rl(r.ax, leader), ly = rl(r.ay, leader);
-            const double dd = dist2(lx, ly, r.tx, r.ty);
+            const double dd = dist2_inrange(lx, ly, r.tx, r.ty);
             const bool open = lane_of(bm);
             const double m = wave_nanmin_n<CT>(open ? dd : __builtin_nan(""));
             pick = bm & __ballot(dd == m);
@@ -442,7 +461,7 @@ struct Fast {
     // LOG (the k_lg_* kernel forms alone): every member lane appends (task id, arrival) to its agent's row of the rollout log
     template <bool LOG = false>
     __device__ __forceinline__ int apply(R& r, const HdrRegs& h, const KP& P, int lane, uint64_t k1, uint64_t gm, int leader, int action,
-                                         const uint64_t* k2p = nullptr, FastLog* lg = nullptr) const {
+                                         const Key2* k2p = nullptr, FastLog* lg = nullptr) const {
         const double now = h.now;
         uint64_t rest = gm & ~(1ull << leader);                                  // :328
         int rlen = __popcll(gm) - 1;
@@ -461,11 +480,14 @@ struct Fast {
         auto go = [&]() __attribute__((always_inline)) { int c = act_; asm("" : "+s"(c)); return c != 0; };
         static_assert(DL == 63, "task & DL");
         const int tl = task & DL;                                                // lane that owns the target: the task's, or (-1 & 63) the depot's
+        // the target's status word, read ONCE for the vacancy and for the join below (nothing writes r.ti between the two; the depot
+        // lane's word is read too and not used)
+        const uint32_t tiw = (uint32_t)__builtin_amdgcn_readlane((int)r.ti, tl);
         if (!go()) {                                                               // vacancy = len(group) :327 (Q9)
             CNT(2);
             mm |= rest; nm += rlen; rlen = 0;
         } else if (rlen != 0) {
-            const int vacancy = (int)(int8_t)(((uint32_t)__builtin_amdgcn_readlane((int)r.ti, tl) >> 8) & 0xFF);   // :327 (may be stale)
+            const int vacancy = (int)(int8_t)((tiw >> 8) & 0xFF);                  // :327 (may be stale)
             const int nf = (vacancy > 1) ? ((vacancy - 1 < rlen) ? vacancy - 1 : rlen) : 0;   // :330-331
             uint64_t kk = k1;
             auto draw = [&](uint32_t rr) {
@@ -483,7 +505,7 @@ struct Fast {
             // :331 choice without replacement, two draws per trip: one key serves the draw from its high word and, if there is one,
             // the draw from its low word
             for (int j = 0; j < nf; j += 2) {
-                kk = (j == 0 && k2p) ? *k2p : mix64(kk + GAMMA);
+                kk = (j == 0 && k2p) ? rl(k2p->kv2, k2p->ki) : mix64(kk + GAMMA);
                 draw((uint32_t)(kk >> 32));
                 if (j + 1 < nf) draw((uint32_t)kk);
             }
@@ -492,7 +514,7 @@ struct Fast {
         const double tx_ = rl(r.tx, tl), ty_ = rl(r.ty, tl);
         // agent_step :300-324 on ALL lanes (fp64 VALU work with fewer than 16 active lanes is 4x slower on gfx950; the asm
         // statement keeps the compiler from sinking the chain into the members-only block below)
-        double d = dist2(r.ax, r.ay, tx_, ty_);
+        double d = dist2_inrange(r.ax, r.ay, tx_, ty_);                          // (a handle with a smaller square never gets here: plan.hpp)
         double arrv = now + over_velocity(d);                                    // :315,:318
         asm volatile("" : "+v"(d), "+v"(arrv));
         FPH(4);
@@ -501,7 +523,7 @@ struct Fast {
         int slot = 0;
         if (go()) {
             // :321-322 members.append unless already listed (Q4: a re-joining agent keeps its slot, its arrival is overwritten)
-            kinfo = (uint32_t)__builtin_amdgcn_readlane((int)r.ti, tl);
+            kinfo = tiw;
             ids = rl(r.ids, tl);
             n = (kinfo >> 16) & 0xFF;
             slot = n + mypos;

@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define DCM_ABI_VERSION 5 /* v3: dcm_build_id, dcm_set_visibility, dcm_load_instances validates req on the device; v4: dcm_set_replay_placement; v5: DCM_PARAM_WIDE_MEMBERS; still v5, additions only: dcm_generate_instances, dcm_get_instances, dcm_generator_draws, dcm_set_instance_renewal, dcm_instance_index, DCM_PARAM_RENEW_SIZES, dcm_set_rollout_log, dcm_set_best_log, dcm_reduce_best, dcm_fork_envs, dcm_rollout_lookahead, dcm_rollout_lookahead_width */
+#define DCM_ABI_VERSION 5 /* v3: dcm_build_id, dcm_set_visibility, dcm_load_instances validates req on the device; v4: dcm_set_replay_placement; v5: DCM_PARAM_WIDE_MEMBERS; still v5, additions only: dcm_generate_instances, dcm_get_instances, dcm_generator_draws, dcm_set_instance_renewal, dcm_instance_index, DCM_PARAM_RENEW_SIZES, dcm_set_rollout_log, dcm_set_best_log, dcm_reduce_best, dcm_fork_envs, dcm_rollout_lookahead, dcm_rollout_lookahead_width, dcm_kernel_name */
 
 typedef struct dcm_env dcm_env; /* opaque */
 
@@ -142,6 +142,23 @@ int dcm_destroy(dcm_env *env);
  * req is validated on the device: an env with a requirement outside the range gets DCM_FLAG_BAD_INSTANCE and stays frozen. */
 int dcm_load_instances(dcm_env *env, const double *depot, const double *task_xy, const int32_t *req,
                        const double *dur, void *stream);
+/* Distances in range.  The register-resident kernels of the one-chunk shapes (k_rollout_fast and its forms, k_step_fast) take the
+ * square root of a squared distance without the scaling that arguments below 2^-767 need.  Instances made by dcm_generate_instances
+ * never hold such a distance (coordinates are multiples of 2^-53).  For loaded instances dcm_load_instances /
+ * dcm_load_instances_ragged (and dcm_restore_state, whose records may hold any instances) check every env on the device -- the
+ * squared distance fma(dy, dy, dx * dx) between any two of the env's T + 1 points, depot included, must be 0 or >= 2^-767 -- and
+ * read one word back, so these calls wait for the stream.  A handle that holds an env with a smaller non-zero squared distance
+ * (two points some 1e-116 apart) runs the general code: k_rollout_random and k_step, same results, slower.  Inside a stream
+ * capture the word cannot be read: the handle then runs the general code until its instances are next loaded outside one.
+ * dcm_kernel_name tells which it is. */
+
+/* The kernel a plain launch of the handle takes as things stand: entry 0 = dcm_rollout_random with all three observation buffers or
+ * none ("k_rollout_fast", "k_rollout_fast_mc", "k_rollout_fast_g", "k_rollout_random"), entry 1 = dcm_step without leader / follower
+ * overrides and without a route log ("k_step_fast", "k_step").  The base name: the renewing, logging and policy forms share it.
+ * NULL (and dcm_last_error) for a null handle or another entry.  Host-side. */
+#define DCM_KERNEL_ROLLOUT 0
+#define DCM_KERNEL_STEP 1
+const char *dcm_kernel_name(dcm_env *env, int32_t entry);
 
 /* Ragged batch: TaskEnv(agents_range=(lo,hi), tasks_range=(lo,hi)) draws its own sizes per env
  * (env/task_env.py:58-65), which is what Runner.testing(seed) does with the default ranges
