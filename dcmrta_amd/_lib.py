@@ -59,6 +59,7 @@ SIGNATURES = {
     "dcm_rollout_random": (C.c_int, [_vp, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),   # env, episodes, max_decisions, max_decisions_in, obs x3, steps, stream
     "dcm_rollout_policy": (C.c_int, [_vp, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),   # env, policy, then as dcm_rollout_random
     "dcm_rollout_explore": (C.c_int, [_vp, _i32, C.c_uint64, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),   # env, base policy, explore_q32, then as dcm_rollout_random
+    "dcm_rollout_individual": (C.c_int, [_vp, _i32, C.c_uint64, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),   # as dcm_rollout_explore; policy: any of the three
     "dcm_rollout_lookahead": (C.c_int, [_vp, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),   # env, base policy, then as dcm_rollout_random
     # env, base policy, width, then as dcm_rollout_random up to steps_out; inner_out, stream
     "dcm_rollout_lookahead_width": (C.c_int, [_vp, _i32, _i32, _i32, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),

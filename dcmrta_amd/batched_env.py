@@ -330,7 +330,7 @@ class BatchedTaskEnv:
     POLICIES = {"random": _lib.POLICY_RANDOM, "first": _lib.POLICY_FIRST, "nearest": _lib.POLICY_NEAREST}
 
     def rollout(self, policy="random", episodes=1, write_obs=True, max_decisions=-1, *, explore=None, explore_q32=None, lookahead=False,
-                width=0, return_inner=False):
+                width=0, return_inner=False, individual=False):
         """`episodes` full episodes per env in one persistent launch under a device policy (dcm_rollout_policy): "random" (uniform
         over the unmasked tasks: the config-2 hot path), "first" (the lowest unmasked task) or "nearest" (the unmasked task closest
         to the deciding agent, ties to the lowest index).
@@ -352,9 +352,22 @@ class BatchedTaskEnv:
         values all, 1 is "nearest" itself.  The best (finished tasks, reward) wins, a tie to the lowest action index.
         return_inner=True (with lookahead=True): also return inner int64[B], the base-policy decisions each env took inside inner
         episodes during this call -- what the launch cost beside its outer decisions.
+        individual=True (dcm_rollout_individual; a handle created with individual_selection=True): the launch plays the reference's
+        individual-selection protocol, Worker.run_test_IS -- the deciders of an event act one by one in ascending id, each alone, no
+        followers, and the depot action moves that agent only.  A decision is then one agent's step: steps, max_decisions and the
+        decision counter count those.  Any of the three policies; explore / explore_q32 as above; not with lookahead / width /
+        return_inner or the best log.  A launch stopped by its budget is carried on by step() and the other way round.
         Returns steps int64[B] (device tensor), or (steps, inner) with return_inner=True."""
         if policy not in self.POLICIES:
             raise DcmError("policy must be one of %s" % ", ".join(repr(p) for p in self.POLICIES))
+        if individual:
+            if lookahead:
+                raise DcmError("individual=True has no lookahead form: give lookahead=False")
+            if width != 0 or return_inner:
+                raise DcmError("width / return_inner belong to the lookahead form, which individual=True does not have")
+            if not self.individual_selection:
+                raise DcmError("individual=True needs a handle created with individual_selection=True (reset() and step() group the "
+                               "deciders by location otherwise)")
         if lookahead and (explore is not None or explore_q32 is not None):
             raise DcmError("lookahead=True takes the base policy's own decisions inside its rollouts: it cannot be combined with explore / explore_q32")
         if isinstance(width, (bool, np.bool_)) or not isinstance(width, (int, np.integer)) or width < 0:
@@ -394,6 +407,10 @@ class BatchedTaskEnv:
             elif lookahead:
                 check(self._lib.dcm_rollout_lookahead(self._h, self.POLICIES[policy], int(episodes), int(max_decisions), _ptr(per_env),
                                                       *[_ptr(x) for x in o], _ptr(steps), self._stream()))
+            elif individual:
+                check(self._lib.dcm_rollout_individual(self._h, self.POLICIES[policy], 0 if q32 is None else q32, int(episodes),
+                                                       int(max_decisions), _ptr(per_env), *[_ptr(x) for x in o], _ptr(steps),
+                                                       self._stream()))
             elif q32 is None:
                 check(self._lib.dcm_rollout_policy(self._h, self.POLICIES[policy], int(episodes), int(max_decisions), _ptr(per_env),
                                                    *[_ptr(x) for x in o], _ptr(steps), self._stream()))

@@ -30,7 +30,7 @@
 
 using namespace dcm;
 
-// Translation units (Makefile).  The library is built from this file seven times; every unit but the main one holds device code and
+// Translation units (Makefile).  The library is built from this file eight times; every unit but the main one holds device code and
 // its launchers only, and the main unit reaches them through the dcm::launch_rollout_* functions declared below.
 //   unit    macro          holds                                                          options
 //   env     -DDCM_SPLIT_G  the host API and every kernel that is not in a unit below      SPLIT SCHED
@@ -40,11 +40,13 @@ using namespace dcm;
 //   env_e   -DDCM_TU_E     the epsilon-greedy forms k_ex_* / k_exrn_* (rollout_explore.hpp)  SPLIT SCHED
 //   env_b   -DDCM_TU_B     the best-keeping form k_bs_* (rollout_best.hpp)                 SPLIT SCHED
 //   env_a   -DDCM_TU_A     the lookahead form k_la_* / k_larn_* (rollout_lookahead.hpp)    SPLIT SCHED
+//   env_i   -DDCM_TU_I     the individual-selection form k_is_* / k_isrn_* (rollout_individual.hpp)  SPLIT SCHED
 // SPLIT (-mllvm -phi-elim-split-all-critical-edges=1) costs k_rollout_fast_g 4 % (8.19 -> 8.53 ms per 4096 x 70A/130T launch) while it
 // buys the one-chunk and the 50A/200T kernel 2.1 % / 1.3 %: hence env_g.  The form units exist so that every kernel that was there
 // before them compiles from the text, and to the code, it had without them.  With none of the macros (the developer tools'
 // one-command builds) everything is in one unit.
-#if defined(DCM_TU_G) || defined(DCM_TU_P) || defined(DCM_TU_L) || defined(DCM_TU_E) || defined(DCM_TU_B) || defined(DCM_TU_A)
+#if defined(DCM_TU_G) || defined(DCM_TU_P) || defined(DCM_TU_L) || defined(DCM_TU_E) || defined(DCM_TU_B) || defined(DCM_TU_A) || \
+    defined(DCM_TU_I)
 #define DCM_DEVICE_ONLY_TU 1
 #elif !defined(DCM_SPLIT_G)
 #define DCM_ONE_UNIT 1
@@ -66,6 +68,9 @@ using namespace dcm;
 #endif
 #if defined(DCM_TU_A) || defined(DCM_ONE_UNIT)
 #define DCM_HAVE_LOOKAHEAD 1  // ... the lookahead form and its launcher
+#endif
+#if defined(DCM_TU_I) || defined(DCM_ONE_UNIT)
+#define DCM_HAVE_INDIVIDUAL 1 // ... the individual-selection form and its launcher
 #endif
 namespace dcm {
 #if !defined(DCM_DEVICE_ONLY_TU)
@@ -114,11 +119,15 @@ using FormLauncher = int(plan::SimKind kind, bool fast, bool obs, unsigned grid,
 // The lookahead form (k_la_* / k_larn_*) takes a.policy (any of the three), a.lg (set or not), a.snap, a.width and a.inner_out; it
 // exists for the general kernel text alone: `fast` and `obs` are ignored.
 FormLauncher launch_rollout_policy, launch_rollout_log, launch_rollout_explore, launch_rollout_best, launch_rollout_lookahead;
+// The individual-selection form (k_is_* / k_isrn_*) takes the epsilon-greedy forms' arguments, a.policy being any of the three; like the
+// lookahead form it exists for the general kernel text alone.
+FormLauncher launch_rollout_individual;
 void allow_lds_policy(int lds);
 void allow_lds_log(int lds);
 void allow_lds_explore(int lds);
 void allow_lds_best(int lds);
 void allow_lds_lookahead(int lds);
+void allow_lds_individual(int lds);
 }  // namespace dcm
 
 namespace {
@@ -1746,6 +1755,9 @@ constexpr uint32_t rollout_random_lds_bytes(Lay L) {
 #ifdef DCM_HAVE_LOOKAHEAD
 #include "rollout_lookahead.hpp"
 #endif
+#ifdef DCM_HAVE_INDIVIDUAL
+#include "rollout_individual.hpp"
+#endif
 
 __global__ __launch_bounds__(WAVE) void k_env_status(int PA, int PT, int PC, const unsigned char* state, int B, uint32_t* flags_out,
                                                     int64_t* dec_out, double* now_out, int32_t* episodes_out) {
@@ -2063,6 +2075,25 @@ void dcm::allow_lds_lookahead(int lds) {
     });
 }
 #endif
+// The individual-selection form likewise: the general family alone (no k_is_rollout_fast)
+#ifdef DCM_HAVE_INDIVIDUAL
+namespace {
+struct individual_general { DCM_FORMS(k_is_rollout_random, k_isrn_rollout_random) };
+}
+int dcm::launch_rollout_individual(plan::SimKind kind, bool, bool, unsigned grid, Lay L, hipStream_t stream, const RolloutArgs& a) {
+    return with_sim(kind, [&](auto s) {
+        using S = decltype(s);
+        return launch_family<individual_general, false, SIM_ARGS(S), S::MC>(a.form, grid, rollout_random_lds_bytes<SIM_ARGS(S)>(L), stream,
+                                                                            a.kernel_args(), a.rn, a.policy, a.explore_q32, a.lg);
+    });
+}
+void dcm::allow_lds_individual(int lds) {
+    for_each_sim([&](auto s) {
+        using S = decltype(s);
+        allow_lds(lds, individual_general::plain<SIM_ARGS(S), S::MC>(), individual_general::renewing<SIM_ARGS(S), S::MC>());
+    });
+}
+#endif
 #undef DCM_FORMS
 #undef DCM_FORM
 
@@ -2191,7 +2222,8 @@ dcm::RolloutArgs rollout_args(const dcm_env* env, plan::RenewForm form, int32_t 
 // (keeps_best: the best-keeping form, which rollout_form also refuses without the rollout log and while any renewal stride is set)
 // (lookahead: the lookahead form, which has no one-chunk kernels -- every shape takes the general text -- and whose snapshot buffer
 //  rollout_form allocates at the first launch)
-struct RolloutForm { dcm::FormLauncher* launch; const char* no_sizes_form; bool keeps_best = false; bool lookahead = false; };
+// (general_only: the lookahead and the individual-selection form, which have no one-chunk kernels -- every shape takes the general text)
+struct RolloutForm { dcm::FormLauncher* launch; const char* no_sizes_form; bool keeps_best = false; bool lookahead = false; bool general_only = lookahead; };
 const RolloutForm FORM_POLICY{dcm::launch_rollout_policy,
     "%s: no greedy policy while a ragged batch renews its sizes (DCM_PARAM_RENEW_SIZES with a stride set): "
     "clear the stride with dcm_set_instance_renewal(env, 0), or use DCM_POLICY_RANDOM"};
@@ -2207,6 +2239,9 @@ const RolloutForm FORM_BEST{dcm::launch_rollout_best,
 const RolloutForm FORM_LOOKAHEAD{dcm::launch_rollout_lookahead,
     "%s: no lookahead while a ragged batch renews its sizes (DCM_PARAM_RENEW_SIZES with a stride set): clear the stride with "
     "dcm_set_instance_renewal(env, 0)", false, true};
+const RolloutForm FORM_INDIVIDUAL{dcm::launch_rollout_individual,
+    "%s: no individual-selection launch while a ragged batch renews its sizes (DCM_PARAM_RENEW_SIZES with a stride set): clear the "
+    "stride with dcm_set_instance_renewal(env, 0)", false, false, true};
 // the form an entry point takes: the best-keeping one while dcm_set_best_log is set, else its own
 const RolloutForm& form_of(const dcm_env* env, const RolloutForm& own) { return env->best_log.episode ? FORM_BEST : own; }
 
@@ -2249,7 +2284,7 @@ int rollout_form(dcm_env* env, const char* fn, const RolloutForm& form, int32_t 
     ra.inner_out = inner_out;
     const bool all_obs = agents_out && tasks_out && mask_out, no_obs = !agents_out && !tasks_out && !mask_out;
     const plan::Shape shape = shape_of(env);
-    const bool fast = !form.lookahead && plan::form_rollout_kind(shape, all_obs || no_obs) == plan::Rollout::Fast;
+    const bool fast = !form.general_only && plan::form_rollout_kind(shape, all_obs || no_obs) == plan::Rollout::Fast;
     return launched(form.launch(plan::sim_kind(shape), fast, all_obs, (unsigned)env->p.n_envs, env->L, (hipStream_t)stream, ra));
 }
 
@@ -2395,6 +2430,7 @@ int dcm_create(const dcm_params* params, dcm_env** out) {
     dcm::allow_lds_explore(lds);
     dcm::allow_lds_best(lds);
     dcm::allow_lds_lookahead(lds);
+    dcm::allow_lds_individual(lds);
     allow_lds(lds, k_get_tasks<M>, k_get_agents<M>, k_get_tasks<MW>, k_get_agents<MW>);
     return DCM_OK;
 }
@@ -2843,6 +2879,31 @@ int dcm_rollout_explore(dcm_env* env, int32_t policy, uint64_t explore_q32, int3
     DCM_TRY(need_budget(env, "dcm_rollout_explore", max_decisions, max_decisions_in));
     return rollout_form(env, "dcm_rollout_explore", form_of(env, FORM_EXPLORE), policy, explore_q32, episodes, max_decisions, max_decisions_in, agents_out,
                         tasks_out, mask_out, steps_out, stream);
+}
+
+int dcm_rollout_individual(dcm_env* env, int32_t policy, uint64_t explore_q32, int32_t episodes, int64_t max_decisions,
+                           const int64_t* max_decisions_in, float* agents_out, float* tasks_out, uint8_t* mask_out, int64_t* steps_out,
+                           void* stream) {
+    CHECK_ENV(env);
+    if (policy != DCM_POLICY_RANDOM && policy != DCM_POLICY_FIRST && policy != DCM_POLICY_NEAREST)
+        return fail(DCM_ERR_INVALID, "dcm_rollout_individual: unknown policy (DCM_POLICY_RANDOM, DCM_POLICY_FIRST, DCM_POLICY_NEAREST)");
+    if (explore_q32 > (1ull << 32)) return fail(DCM_ERR_INVALID, "dcm_rollout_individual: explore_q32 must be <= 2^32");
+    if (policy == DCM_POLICY_RANDOM && explore_q32 != 0)
+        return fail(DCM_ERR_INVALID, "dcm_rollout_individual: explore_q32 needs a greedy base policy (DCM_POLICY_RANDOM explores at every "
+                                     "decision already): give 0");
+    if (episodes < 1) return fail(DCM_ERR_INVALID, "dcm_rollout_individual: episodes must be >= 1");
+    if (policy != DCM_POLICY_RANDOM) DCM_TRY(need_budget(env, "dcm_rollout_individual", max_decisions, max_decisions_in));
+    // dcm_reset and dcm_step form the one-group event and take the lowest pending id only under the flag: a budget-stopped launch must
+    // be continuable by dcm_step and the other way round
+    if (!(env->p.flags & DCM_PARAM_NO_GROUPING))
+        return fail(DCM_ERR_STATE, "dcm_rollout_individual: the handle was not created with DCM_PARAM_NO_GROUPING (dcm_reset and dcm_step "
+                                   "group its deciders by location)");
+    if (!env->reset_done) return fail(DCM_ERR_STATE, "dcm_rollout_individual: call dcm_reset first");
+    if (env->best_log.episode)
+        return fail(DCM_ERR_STATE, "dcm_rollout_individual: the best log is set and there is no best-keeping individual-selection form: "
+                                   "clear it with dcm_set_best_log(env, NULL, NULL, NULL, NULL, NULL)");
+    return rollout_form(env, "dcm_rollout_individual", FORM_INDIVIDUAL, policy, explore_q32, episodes, max_decisions, max_decisions_in,
+                        agents_out, tasks_out, mask_out, steps_out, stream);
 }
 
 int dcm_rollout_lookahead(dcm_env* env, int32_t base_policy, int32_t episodes, int64_t max_decisions, const int64_t* max_decisions_in,

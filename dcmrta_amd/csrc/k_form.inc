@@ -6,7 +6,7 @@
 //     #include "k_form.inc"
 // in front of its kernel, declares it as KNAME(..., KSIZES, ... int retcap KRENEW_PARAM KPOLICY_PARAM), and ends with
 // #include "k_form_end.inc".  Whoever includes the text sets DCM_RENEW and at most one of DCM_POLICY, DCM_LOG, DCM_EXPLORE, DCM_BEST,
-// DCM_LOOKAHEAD.
+// DCM_LOOKAHEAD, DCM_INDIVIDUAL.
 //
 //   DCM_RENEW   KNAME          launched                                            KRENEW_PARAM   KSIZES
 //   0           k_<base>       without a renewal stride                            --             const int32_t* sizes
@@ -24,6 +24,7 @@
 //   DCM_BEST      k_bs_<base> / --               any of the three, dcm_set_best_log   , int policy, uint64_t explore_q32, RouteLog lg, BestLog best
 //   DCM_LOOKAHEAD k_la_<base> / k_larn_<base>    dcm_rollout_lookahead[_width]        , int policy, RouteLog lg, unsigned char* snap,
 //                                                                                       int width, int64_t* inner_out
+//   DCM_INDIVIDUAL k_is_<base> / k_isrn_<base>   dcm_rollout_individual               , int policy, uint64_t explore_q32, RouteLog lg
 // Greedy: the action comes from `policy` (wave-uniform) instead of protocol slot 1.  Logging: `policy` covers all three policies
 // (DCM_POLICY_RANDOM takes slot 1 as the plain form does) and every agent_step is appended to the log.  Epsilon-greedy: the logging
 // form with explore_q32; the log may be unset there (lg.len null).  These forms exist for k_rollout_fast and k_rollout_random only,
@@ -37,6 +38,9 @@
 // wave snapshots its env into its slice of `snap`, plays one inner episode per unmasked action and restores -- and the logging code
 // rides along as in the epsilon-greedy forms (lg.len null: no log).  `width` (0: all) limits the valued actions to the nearest ones;
 // `inner_out` (null: not wanted) takes per env the inner episodes' decisions.  k_rollout_random only; no size-renewing form.
+// Individual selection (rollout_individual.hpp): the epsilon-greedy form's arguments, `policy` covering all three as in the logging
+// form, with the deciders of an event taken one by one in ascending id instead of grouped by location: no leader draw, no
+// followers, the depot action moves the deciding agent alone (Worker.run_test_IS).  k_rollout_random only; no size-renewing form.
 // KEXPLORES (defined here, for the texts): the form draws explore words -- DCM_EXPLORE or DCM_BEST.
 //
 // Two kernels from one text leave the first as it was: a form holds nothing of the others and compiles to the code it had before
@@ -50,6 +54,15 @@
 #endif
 #if (defined(DCM_POLICY) || defined(DCM_LOG) || defined(DCM_EXPLORE) || defined(DCM_BEST)) && !defined(KPOLICY_FORMS)
 #error "this kernel text has no greedy, logging, epsilon-greedy or best-keeping form"
+#endif
+#if defined(DCM_INDIVIDUAL) && (defined(DCM_POLICY) || defined(DCM_LOG) || defined(DCM_EXPLORE) || defined(DCM_BEST) || defined(DCM_LOOKAHEAD))
+#error "DCM_INDIVIDUAL stands alone: no other form macro beside it"
+#endif
+#if defined(DCM_INDIVIDUAL) && !defined(KINDIVIDUAL_FORM)
+#error "the individual-selection form exists for k_rollout_random only"
+#endif
+#if defined(DCM_INDIVIDUAL) && DCM_RENEW == 2
+#error "no size-renewing individual-selection form"
 #endif
 #if defined(DCM_LOOKAHEAD) && !defined(KLOOKAHEAD_FORM)
 #error "the lookahead form exists for k_rollout_random only"
@@ -95,6 +108,9 @@
 #elif defined(DCM_LOOKAHEAD)
 #define KPREFIX KFORM_PICK(k_la_, k_larn_)
 #define KPOLICY_PARAM , int policy, RouteLog lg, unsigned char* snap, int width, int64_t* inner_out
+#elif defined(DCM_INDIVIDUAL)
+#define KPREFIX KFORM_PICK(k_is_, k_isrn_)
+#define KPOLICY_PARAM , int policy, uint64_t explore_q32, RouteLog lg
 #elif DCM_RENEW == 2
 #define KPREFIX k_rs_
 #define KPOLICY_PARAM

@@ -10,4 +10,5 @@
 #undef KFORM_PICK
 #undef KPOLICY_FORMS
 #undef KLOOKAHEAD_FORM
+#undef KINDIVIDUAL_FORM
 #undef KBASE

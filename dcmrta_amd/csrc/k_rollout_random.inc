@@ -1,6 +1,6 @@
 // k_rollout_random.inc -- the kernel k_rollout_random and all its forms (k_form.inc), compiled once per form: the plain, renewing and
-// size-renewing ones by dcmrta_env.hip, the others by rollout_policy.hpp, rollout_log.hpp, rollout_explore.hpp, rollout_best.hpp and
-// rollout_lookahead.hpp.
+// size-renewing ones by dcmrta_env.hip, the others by rollout_policy.hpp, rollout_log.hpp, rollout_explore.hpp, rollout_best.hpp,
+// rollout_lookahead.hpp and rollout_individual.hpp.
 // Logging forms: apply_and_advance appends to the log, and the env zeroes its lengths when it restarts an episode.
 // Epsilon-greedy forms: a decision whose explore word (mix64(key_1 ^ EXPLORE_SALT) >> 32) is below explore_q32 takes
 // pick_random_action, every other one pick_policy_action of the base policy (FIRST / NEAREST).  The budget is the greedy forms'
@@ -11,9 +11,13 @@
 // decisions' -- with lookahead_action in the place of the policy's pick: the wave plays one inner episode per unmasked action
 // between two snapshots of its env and takes the action whose episode ends best.  `width` limits the valued actions to the nearest
 // ones (0: all of them), and `inner_out`, if set, takes the env's count of the inner episodes' decisions beside steps_out.
+// Individual-selection form (rollout_individual.hpp): the epsilon-greedy loop with `policy` covering DCM_POLICY_RANDOM and the budget
+// rule of the logging forms, and three call sites changed: pick_leader takes the lowest pending id (no draw), and apply_and_advance
+// and both advance calls run with no_grouping -- no followers, the depot action moves the decider alone, ONE group per event.
 #define KBASE rollout_random
 #define KPOLICY_FORMS 1
 #define KLOOKAHEAD_FORM 1
+#define KINDIVIDUAL_FORM 1
 #include "k_form.inc"
 template <int CA, int CT, bool RS, int MC = M>
 __global__ __launch_bounds__(WAVE, 3) void KNAME(int A, int T, int PA, int PT, KP P, unsigned char* state, int episodes,
@@ -49,7 +53,7 @@ __global__ __launch_bounds__(WAVE, 3) void KNAME(int A, int T, int PA, int PT, K
     double* row = summary + (size_t)e * 8;
 #if defined(DCM_POLICY) || defined(DCM_EXPLORE)
     const int left0 = rollout_budget_policy(e, budget_all, budget_in, P);
-#elif defined(DCM_LOG) || defined(DCM_BEST) || defined(DCM_LOOKAHEAD)
+#elif defined(DCM_LOG) || defined(DCM_BEST) || defined(DCM_LOOKAHEAD) || defined(DCM_INDIVIDUAL)
     const int left0 = policy == DCM_POLICY_RANDOM ? rollout_budget(e, budget_all, budget_in) : rollout_budget_policy(e, budget_all, budget_in, P);
 #else
     const int left0 = rollout_budget(e, budget_all, budget_in);
@@ -73,13 +77,17 @@ __global__ __launch_bounds__(WAVE, 3) void KNAME(int A, int T, int PA, int PT, K
 #elif DCM_RENEW
             wave_renew_instance_call(S, rec, rn, e, lane, xy);
 #endif
-#if defined(KEXPLORES) || defined(DCM_LOOKAHEAD)
+#if defined(KEXPLORES) || defined(DCM_LOOKAHEAD) || defined(DCM_INDIVIDUAL)
             if (lg.len) for (int a = lane; a < S.A(); a += WAVE) lg.len[(size_t)e * BA + a] = 0;   // the log, if set, is the new episode's
 #elif defined(DCM_LOG)
             for (int a = lane; a < S.A(); a += WAVE) lg.len[(size_t)e * BA + a] = 0;   // the log is the new episode's (as k_step's restart)
 #endif
             S.reset_state(h, lane);
+#ifdef DCM_INDIVIDUAL
+            S.advance(h, P, lane, row PH_PASS, true);   // every decider of the event in ONE group
+#else
             S.advance(h, P, lane, row PH_PASS);
+#endif
             PH_MARK(10);
         }
         // (the budget test rides on the loop's own scalar branch; testing it between observe and the action pick instead
@@ -88,7 +96,11 @@ __global__ __launch_bounds__(WAVE, 3) void KNAME(int A, int T, int PA, int PT, K
             AMask gm;
             const uint64_t k1 = mix64(gd);   // (computing the next decision's key early, under the LDS latency of apply, measured
                                              //  0.9 % SLOWER: two more live registers across the whole decision)
+#ifdef DCM_INDIVIDUAL
+            const int leader = S.pick_leader(h, lane, -1, k1, gm, true);   // the lowest pending id: protocol slot 0 is not consumed
+#else
             const int leader = S.pick_leader(h, lane, -1, k1, gm);
+#endif
             if (leader < 0) break;
             PH_MARK(0);
             if (all_obs) { __builtin_assume(ag != nullptr); __builtin_assume(tk != nullptr); __builtin_assume(mk != nullptr); S.observe(h, lane, leader, ag, tk, mk, xy); }
@@ -102,6 +114,10 @@ __global__ __launch_bounds__(WAVE, 3) void KNAME(int A, int T, int PA, int PT, K
 #else
             const int action = explores ? S.pick_random_action(lane, k1) : S.pick_policy_action(lane, leader, policy, xy);
 #endif
+#elif defined(DCM_INDIVIDUAL)
+            // the epsilon-greedy decision, `policy` covering DCM_POLICY_RANDOM (explore_q32 = 0 there)
+            const bool explores = (uint64_t)(uint32_t)(mix64(k1 ^ EXPLORE_SALT) >> 32) < explore_q32;
+            const int action = (explores || policy == DCM_POLICY_RANDOM) ? S.pick_random_action(lane, k1) : S.pick_policy_action(lane, leader, policy, xy);
 #elif defined(DCM_LOOKAHEAD)
             const int action = lookahead_action(S, h, P, lane, leader, gm, k1, gd, policy, xy, snap, e, BA, BT, width, inner PH_PASS);
 #elif defined(DCM_POLICY)
@@ -112,7 +128,10 @@ __global__ __launch_bounds__(WAVE, 3) void KNAME(int A, int T, int PA, int PT, K
             const int action = S.pick_random_action(lane, k1);
 #endif
             PH_MARK(2);
-#if defined(DCM_LOG) || defined(KEXPLORES) || defined(DCM_LOOKAHEAD)
+#ifdef DCM_INDIVIDUAL
+            // no_grouping: no followers and no follower draws, action 0 moves `leader` alone, and the next event is one group again
+            S.template apply_and_advance<true>(h, P, lane, leader, gm, action, k1, -1, nullptr, row PH_PASS, lg, e * BA, true, 0, true, false, &xy);
+#elif defined(DCM_LOG) || defined(KEXPLORES) || defined(DCM_LOOKAHEAD)
             S.template apply_and_advance<true>(h, P, lane, leader, gm, action, k1, -1, nullptr, row PH_PASS, lg, e * BA, false, 0, true, false, &xy);
 #else
             S.template apply_and_advance<true>(h, P, lane, leader, gm, action, k1, -1, nullptr, row PH_PASS, RouteLog{nullptr, nullptr, nullptr, 0}, 0, false, 0, true, false, &xy);

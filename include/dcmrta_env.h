@@ -33,7 +33,7 @@
 extern "C" {
 #endif
 
-#define DCM_ABI_VERSION 5 /* v3: dcm_build_id, dcm_set_visibility, dcm_load_instances validates req on the device; v4: dcm_set_replay_placement; v5: DCM_PARAM_WIDE_MEMBERS; still v5, additions only: dcm_generate_instances, dcm_get_instances, dcm_generator_draws, dcm_set_instance_renewal, dcm_instance_index, DCM_PARAM_RENEW_SIZES, dcm_set_rollout_log, dcm_set_best_log, dcm_reduce_best, dcm_fork_envs, dcm_rollout_lookahead, dcm_rollout_lookahead_width, dcm_kernel_name */
+#define DCM_ABI_VERSION 5 /* v3: dcm_build_id, dcm_set_visibility, dcm_load_instances validates req on the device; v4: dcm_set_replay_placement; v5: DCM_PARAM_WIDE_MEMBERS; still v5, additions only: dcm_generate_instances, dcm_get_instances, dcm_generator_draws, dcm_set_instance_renewal, dcm_instance_index, DCM_PARAM_RENEW_SIZES, dcm_set_rollout_log, dcm_set_best_log, dcm_reduce_best, dcm_fork_envs, dcm_rollout_lookahead, dcm_rollout_lookahead_width, dcm_kernel_name, dcm_rollout_individual */
 
 typedef struct dcm_env dcm_env; /* opaque */
 
@@ -70,7 +70,8 @@ typedef enum {
 /* dcm_params.flags: individual selection (Worker.run_test_IS, worker.py:159-198, skips get_unique_group) -- all agents
  * deciding at an event form ONE group and act one by one in ascending id, each alone: unless a leader / follower count is
  * injected, dcm_observe / dcm_step take the lowest pending id as the deciding agent and no followers.
- * Honoured by dcm_reset / dcm_observe / dcm_step; dcm_rollout_random always groups by location. */
+ * Honoured by dcm_reset / dcm_observe / dcm_step, and by dcm_rollout_individual, the persistent launch of this protocol, which
+ * needs the flag; dcm_rollout_random / _policy / _explore / _lookahead* group by location on every handle. */
 #define DCM_PARAM_NO_GROUPING 1u
 /* dcm_params.flags: auto-reset for the lockstep API -- when a dcm_step ends an env's episode (terminal box of worker.py:87,
  * results written to its dcm_summary row), the same call restarts the env from the instance its record holds -- or, with
@@ -423,6 +424,28 @@ int dcm_rollout_policy(dcm_env *env, int32_t policy, int32_t episodes, int64_t m
 int dcm_rollout_explore(dcm_env *env, int32_t policy, uint64_t explore_q32, int32_t episodes, int64_t max_decisions,
                         const int64_t *max_decisions_in, float *agents_out, float *tasks_out, uint8_t *mask_out,
                         int64_t *steps_out, void *stream);
+
+/* The same persistent launch under INDIVIDUAL SELECTION, the reference's second evaluation protocol (Worker.run_test_IS,
+ * worker.py:159-198): the deciders of an event are not grouped by location; they act one by one in ascending id, each alone through
+ * agent_step, task_update and agent_update behind each, and the depot action moves the deciding agent only.  A DECISION under this
+ * form is one agent's agent_step: steps_out, max_decisions, max_decisions_in and the decision counter of the choice protocol count
+ * those, and the observation buffers hold what the last deciding agent saw.
+ * `policy` is any of DCM_POLICY_RANDOM, DCM_POLICY_FIRST, DCM_POLICY_NEAREST; explore_q32 in [0, 2^32] makes FIRST / NEAREST
+ * epsilon-greedy by dcm_rollout_explore's rule (explore word of key_1 below explore_q32: the random policy's action, protocol slot 1)
+ * and must be 0 with DCM_POLICY_RANDOM, which takes slot 1 at every decision.  Slot 0 (the leader draw) and the follower slots are
+ * never consumed.  episodes, the budgets, the rollout log (set or not), the return log, the abandonment log, instance renewal with a
+ * uniform stride and ragged batches work as in dcm_rollout_explore.  One kernel text serves every shape (k_is_rollout_random /
+ * k_isrn_rollout_random): there is no register-resident form.
+ * The handle must have been created with DCM_PARAM_NO_GROUPING: dcm_reset and dcm_step form the one-group event and take the lowest
+ * pending id only under it, so a launch stopped by its budget in the middle of an event is carried on by dcm_step (or by another
+ * launch) and the other way round.  The other dcm_rollout_* entry points keep grouping by location on such a handle.
+ * Refusals, nothing launched and nothing changed.  DCM_ERR_INVALID: an unknown policy; explore_q32 > 2^32; explore_q32 != 0 with
+ * DCM_POLICY_RANDOM; episodes < 1; FIRST / NEAREST on a handle with max_waiting_time <= 0 without a decision budget (a negative
+ * entry of max_decisions_in counts as 0 there).  DCM_ERR_STATE: a handle without DCM_PARAM_NO_GROUPING; no dcm_reset yet; the best
+ * log is set (there is no best-keeping form); a launch that would renew a ragged batch's SIZES. */
+int dcm_rollout_individual(dcm_env *env, int32_t policy, uint64_t explore_q32, int32_t episodes, int64_t max_decisions,
+                           const int64_t *max_decisions_in, float *agents_out, float *tasks_out, uint8_t *mask_out,
+                           int64_t *steps_out, void *stream);
 
 /* The same persistent launch with every decision chosen by ONE-STEP LOOKAHEAD over a base policy: the rollout algorithm, on the device.
  * Every argument other than base_policy means what it means in dcm_rollout_policy; base_policy is any of DCM_POLICY_RANDOM,

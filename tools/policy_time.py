@@ -17,7 +17,14 @@ the greedy policies k_hp_rollout_fast, which has none.  Prints one JSON line per
 times the epsilon-greedy forms (dcm_rollout_explore) against the forms they equal at the two ends, within this build, interleaved,
 `rounds` alternations of `reps` calls each: explore_q32 = 0 against rollout("nearest") (k_ex_rollout_fast / k_hp_rollout_fast), and
 explore_q32 = 2^32 against the random policy's unprioritised form -- with the rollout log set (k_lg_rollout_fast, 4096 envs) and,
-without it, at 4095 envs, where rollout("random") takes k_rollout_fast without wave priorities.  One JSON line per pair."""
+without it, at 4095 envs, where rollout("random") takes k_rollout_fast without wave priorities.  One JSON line per pair.
+
+    python tools/policy_time.py --individual [--events] [--reps 1 --warmup 1]
+
+plays the same calls under individual selection (Worker.run_test_IS): the handle is created with individual_selection=True and
+every call is rollout(policy, individual=True) -- k_is_rollout_random / k_isrn_rollout_random for every policy, where a decision is
+one agent's step.  --events (with or without --individual) takes the time between two device events around the call instead of the
+host clock; every line also gives decisions per second."""
 import argparse
 import json
 import os
@@ -34,19 +41,22 @@ from dcmrta_amd.choice import env_seeds  # noqa: E402
 B, A, T, EPISODES = 4096, 20, 50, 3
 
 
-def timed_rollouts(env, seeds, policy, stride, reps, warmup):
+def timed_rollouts(env, seeds, policy, stride, reps, warmup, individual=False, events=False):
     """(median seconds, decisions of one call) of rollout(policy, EPISODES) from a fresh generate_instances + reset."""
     out, steps = [], 0
+    start, stop = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     for i in range(warmup + reps):
         env.generate_instances(0)
         env.set_instance_renewal(stride)
         env.reset(seeds, observe=False)
         torch.cuda.synchronize(env.device)
         t = time.perf_counter()
-        s = env.rollout(policy, episodes=EPISODES)
+        start.record()
+        s = env.rollout(policy, episodes=EPISODES, individual=individual)
+        stop.record()
         torch.cuda.synchronize(env.device)
         if i >= warmup:
-            out.append(time.perf_counter() - t)
+            out.append(start.elapsed_time(stop) * 1e-3 if events else time.perf_counter() - t)
         steps = int(s.sum())
     return statistics.median(out), steps
 
@@ -95,19 +105,23 @@ def main():
     ap.add_argument("--device", default="cuda:0")
     ap.add_argument("--explore", action="store_true", help="time the epsilon-greedy forms against their twins instead")
     ap.add_argument("--rounds", type=int, default=5, help="--explore: alternations per pair")
+    ap.add_argument("--individual", action="store_true", help="individual selection: individual_selection=True handle, rollout(individual=True)")
+    ap.add_argument("--events", action="store_true", help="device events around the call instead of the host clock")
     args = ap.parse_args()
     if args.reps < 1:
         ap.error("--reps must be >= 1")
     if args.explore:
         return explore_pairs(args)
-    env = BatchedTaskEnv(B, A, T, device=args.device)
+    env = BatchedTaskEnv(B, A, T, device=args.device, individual_selection=args.individual)
     seeds = env_seeds(1, 0, B)
     for policy in ("random", "first", "nearest"):
         for mode, stride in (("off", 0), ("on", B)):
-            sec, steps = timed_rollouts(env, seeds, policy, stride, args.reps, args.warmup)
+            with torch.cuda.device(env.device):
+                sec, steps = timed_rollouts(env, seeds, policy, stride, args.reps, args.warmup, individual=args.individual, events=args.events)
             assert int(env.instance_index().min()) == int(env.instance_index().max()) == (EPISODES - 1 if stride else 0)
-            row = dict(shape=f"{B}x{A}A{T}T", policy=policy, renewal=mode, episodes=EPISODES, ms=round(sec * 1e3, 4), decisions=steps,
-                       ns_per_decision=round(sec * 1e9 / steps, 4), reps=args.reps)
+            row = dict(shape=f"{B}x{A}A{T}T", policy=policy, individual=args.individual, renewal=mode, episodes=EPISODES,
+                       clock="device events" if args.events else "host", ms=round(sec * 1e3, 4), decisions=steps,
+                       ns_per_decision=round(sec * 1e9 / steps, 4), decisions_per_s=round(steps / sec, 1), reps=args.reps)
             sm = env.summary()
             row.update(mean_finished_tasks=round(float(sm[:, 1].mean()), 3), mean_makespan=round(float(sm[:, 3].mean()), 3))
             print(json.dumps(row), flush=True)
